@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark of the 2G-GCN hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR]
   (N > 1: one rank per GPU over RCCL -- either launched by torch.distributed.run (WORLD_SIZE set), or, when started
   bare, bench.py starts the N ranks itself as child processes before touching the GPU and exits with their code)
 
@@ -357,6 +357,28 @@ def log(msg):
     print(f'[bench {time.strftime("%H:%M:%S")}] {msg}', file=sys.stderr, flush=True)
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """Writes each (name, tensor) as dirname/<name>.npy in float32. An array larger than its share of the 64 MB budget
+    is replaced by a fixed sample of its flattened elements (sorted indices drawn by numpy's default_rng(0), so the same
+    element count always gives the same indices): two builds stay comparable element for element."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 4 // max(1, len(arrays))
+    total = 0
+    for name, t in arrays:
+        a = t.detach().to('cpu', torch.float32).numpy()
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+        total += a.nbytes
+    assert total <= DUMP_BUDGET_BYTES, total
+    log(f'dumped {len(arrays)} arrays ({total / 2**20:.1f} MB) to {dirname}')
+
+
 def launch_ranks(n):
     """Starts `n` ranks of this script through torch.distributed.run (one process per GPU, rendezvous on 127.0.0.1 at a
     free port) as a child process and returns its exit code. Must run before anything initialises the GPU."""
@@ -389,7 +411,12 @@ def main():
     ap.add_argument('--scaling', choices=['weak', 'strong'], default='weak',
                     help='weak: the workload\'s batch per GPU (global = batch * N); strong: the workload\'s batch is the '
                          'GLOBAL batch, batch / N clips per GPU (SURVEY 8e: fixed global bs64 = 8 x 8 at N = 8)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (model outputs, loss, seeded '
+                         'samples of the updated parameters and the gradients) as DIR/<name>.npy, float32, at most 64 MB')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
     wl = select_workload(args.workload)
     args.workload_batch = args.batch   # as given (None = the workload's): the other scaling mode is derived from it
     if args.batch is None:
@@ -465,13 +492,15 @@ def main():
         seg_target = torch.zeros(nb, T, H, device=device)
         loss_targets = [seg_target, seg_target, targets[0], targets[1], targets[0], targets[1]]
 
-        def step():
+        def step(keep=None):
             dp.zero_grad()
             out = model(x_human, x_objects, mask, human_segmentation=seg)
             loss = sum(criterion(out, loss_targets))
             loss.backward()
             dp.all_reduce_gradients()
             opt.step(dp.grad_scale)
+            if keep is not None:   # --dump-outputs, last timed step only: what a caller of the model received
+                keep['out'] = [o.detach() if torch.is_tensor(o) else o for o in out]
             # detached: a caller that keeps the returned loss must not keep the step's autograd node (and the ~3 GB of
             # buffers it saved) alive into the next step -- the next step's buffers would land at other addresses, i.e.
             # under other hipGraph keys: first-sighting launches and a fresh capture of every time loop inside the timed
@@ -480,6 +509,22 @@ def main():
         return step, (x_human, x_objects, mask, seg, loss_targets)
 
     step, (x_human, x_objects, mask, seg, loss_targets) = make_step(bs)
+    # the training state as created; restored in place (same addresses) in front of the timed steps, so that they start
+    # from the same parameters, Adam moments, batch-norm statistics and noise generator however many warm-up steps ran:
+    # the timed steps compute the same values in every run (--dump-outputs)
+    init_state = dict(flat=dp.flat.flat.clone(), buffers=[b.clone() for b in model.buffers()],
+                      cpu_rng=torch.get_rng_state(), cuda_rng=torch.cuda.get_rng_state(device))
+
+    def restore_initial_state():
+        with torch.no_grad():
+            dp.flat.flat.copy_(init_state['flat'])
+            for b, b0 in zip(model.buffers(), init_state['buffers']):
+                b.copy_(b0)
+            opt.exp_avg.zero_()
+            opt.exp_avg_sq.zero_()
+        opt.step_count = 0
+        torch.set_rng_state(init_state['cpu_rng'])
+        torch.cuda.set_rng_state(init_state['cuda_rng'], device)
 
     def barrier():
         if world > 1:
@@ -560,20 +605,26 @@ def main():
         else:
             gc_log.append((info['generation'], (time.perf_counter() - gc_t0[0]) * 1e3))
     gc.callbacks.append(_gc_watch)
+    restore_initial_state()
     barrier()
     torch.cuda.synchronize()
     step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     import contextlib
     with (GemmProfiler(K, pool) if instrument_timed else contextlib.nullcontext()) as prof:
+        kept = {}
         t0 = time.perf_counter()
         step_ev[0].record()
         for i in range(args.steps):
-            loss = step()
+            loss = step(kept if args.dump_outputs and i == args.steps - 1 else None)
             step_ev[i + 1].record()
         torch.cuda.synchronize()
         barrier()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [(f'output_{j}', o) for j, o in enumerate(kept['out']) if torch.is_tensor(o)]
+                     + [('loss', loss), ('parameters', dp.flat.flat), ('gradients', dp.flat.grad)])
+    del kept
     if not instrument_timed:
         with GemmProfiler(K, pool) as prof:
             for i in range(prof_steps):

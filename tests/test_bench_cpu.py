@@ -34,3 +34,30 @@ def test_bare_start_launches_n_ranks(monkeypatch):
     assert cmd[cmd.index('--master-addr') + 1] == '127.0.0.1'
     assert cmd[-4:] == ['--gpus', '8', '--steps', '3'] and cmd[-5].endswith('bench.py')
     assert seen['env'].get('HSA_ENABLE_IPC_MODE_LEGACY') == '0'
+
+
+def test_dump_outputs_float32_within_budget_fixed_sample(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    big = torch.arange(20_000_000, dtype=torch.float64)
+    arrays = [('loss', torch.tensor(2.5)), ('out', torch.randn(3, 4).t()), ('big', big)]
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    total = 0
+    for name, t in arrays:
+        a, b = np.load(tmp_path / 'a' / f'{name}.npy'), np.load(tmp_path / 'b' / f'{name}.npy')
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        total += a.nbytes
+        if name != 'big':   # small arrays are written whole, in their shape
+            assert a.shape == tuple(t.shape) and np.array_equal(a, t.float().numpy())
+    assert total <= 64 << 20
+    s = np.load(tmp_path / 'a' / 'big.npy')   # the sample: elements in ascending index order
+    assert 0 < s.size < big.numel() and np.all(np.diff(s) >= 0) and s[0] < s[-1]
+
+
+def test_steps_below_one_is_refused():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], cwd=ROOT,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and '--steps' in r.stderr

@@ -52,3 +52,25 @@ def test_bench_world_size_mismatch_is_refused():
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2'], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 2 and 'WORLD_SIZE' in r.stderr
+
+
+def test_bench_dump_outputs_same_in_every_run(tmp_path):
+    """--dump-outputs: the last timed step's outputs, identical in two runs with the same arguments (the warm-up phase
+    runs a variable number of steps; the timed steps start from the restored initial state), and --steps is honoured."""
+    import numpy as np
+    runs = []
+    for d in ('a', 'b'):
+        r = _bench('--gpus', '1', '--steps', '3', '--warmup', '1', '--workload', 'c5', '--no-cpu-baseline',
+                   '--dump-outputs', str(tmp_path / d))
+        assert r['steps'] == 3 and r['ms_per_step'] > 0
+        runs.append(tmp_path / d)
+    names = sorted(p.name for p in runs[0].iterdir())
+    assert names == sorted(p.name for p in runs[1].iterdir())
+    assert {'loss.npy', 'parameters.npy', 'gradients.npy', 'output_4.npy', 'output_5.npy'} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(runs[0] / n), np.load(runs[1] / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
