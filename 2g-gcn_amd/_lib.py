@@ -61,6 +61,18 @@ class BiGruBwd(C.Structure):  # twog_bigru_bwd_t
                 ('E', C.c_int32), ('pad_', C.c_int32)]
 
 
+class EntityPool(C.Structure):  # twog_entity_pool_t
+    _fields_ = [('hfr', C.c_void_p), ('ofr', C.c_void_p), ('mask', C.c_void_p), ('hin', C.c_void_p), ('oin', C.c_void_p),
+                ('bs', C.c_int32), ('T', C.c_int32), ('H', C.c_int32), ('O', C.c_int32), ('W', C.c_int32),
+                ('pad_', C.c_int32)]
+
+
+class EntityPoolBwd(C.Structure):  # twog_entity_pool_bwd_t
+    _fields_ = [('d_hin', C.c_void_p), ('d_oin', C.c_void_p), ('mask', C.c_void_p), ('d_hfr', C.c_void_p),
+                ('d_ofr', C.c_void_p), ('bs', C.c_int32), ('T', C.c_int32), ('H', C.c_int32), ('O', C.c_int32),
+                ('W', C.c_int32), ('pad_', C.c_int32)]
+
+
 class Attn(C.Structure):  # twog_attn_t
     _fields_ = [('feat_h', Rows), ('feat_o', Rows), ('msg_hh', Rows), ('msg_ho', Rows), ('msg_oh', Rows),
                 ('msg_oo', Rows), ('msg_so', Rows), ('msg_sh', Rows), ('out_hh', Rows), ('out_oh', Rows),
@@ -195,6 +207,10 @@ SIGNATURES = {
     'twog_bigru_bwd_persistent_supported': [C.POINTER(BiGruBwd), _I, _I, _I],
     'twog_bigru_bwd_persistent': [C.POINTER(BiGruBwd), _I, _I, _I, _I, _P, _P],
     'twog_bigru_bwd': [C.POINTER(BiGruBwd), _I, _I, _I, _I, _P, C.c_size_t, _P],
+    'twog_gru_seq_fwd': [C.POINTER(BiGru), _I, _I, _I, _I, _P, C.c_size_t, _P],
+    'twog_gru_seq_bwd': [C.POINTER(BiGruBwd), _I, _I, _I, _I, _P, C.c_size_t, _P],
+    'twog_entity_pool_fwd': [C.POINTER(EntityPool), _P],
+    'twog_entity_pool_bwd': [C.POINTER(EntityPoolBwd), _P],
     'twog_attn_fwd': [C.POINTER(Attn), _I, _P],
     'twog_attn_limits': [C.POINTER(C.c_int), C.POINTER(C.c_int)],
     'twog_attn_bwd': [C.POINTER(AttnBwd), _I, _P],

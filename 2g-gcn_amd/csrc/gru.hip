@@ -235,7 +235,11 @@ extern "C" int twog_gru_step_bwd(const twog_gru_step_bwd_t* steps, int n_steps, 
 
 // ---------------------------------------------------------------------------------------------------------------
 // Frame-level BiGRU recurrence for up to 4 entity types at once (humans, objects, geometry).
+// ND = 2: both directions (twog_bigru_*); ND = 1: the forward direction alone (twog_gru_seq_*, the baselines'
+// bidirectional=False), rows of width ND * h (outputs) and ND * 3h (gate pre-activations). The ND = 2 instantiation is
+// the code these entry points always ran.
 // ---------------------------------------------------------------------------------------------------------------
+template <int ND>
 static int bigru_fwd_impl(const twog_bigru_t* types, int n_types, int bs, int T, int hidden, void* chain_ws,
                           size_t chain_ws_bytes, void* stream) {
     if (n_types > 4) return -1;
@@ -247,12 +251,12 @@ static int bigru_fwd_impl(const twog_bigru_t* types, int n_types, int bs, int T,
         for (int k = 0; k < n_types; ++k) {
             const twog_bigru_t& Y = types[k];
             const int E = Y.E, rows = bs * E;
-            for (int dir = 0; dir < 2; ++dir) {
+            for (int dir = 0; dir < ND; ++dir) {
                 const int t = dir == 0 ? s : T - 1 - s;
                 const int tp = dir == 0 ? t - 1 : t + 1;
                 float* tmp = Y.tmp_gh + (int64_t)dir * rows * 3 * h;
                 twog_rows_t hprev = s == 0 ? rows_plain(Y.zeros, h)
-                                           : rows_be(Y.out + (int64_t)tp * E * 2 * h + dir * h, E, 2 * h, T);
+                                           : rows_be(Y.out + (int64_t)tp * E * ND * h + dir * h, E, ND * h, T);
                 twog_gemm_t& G = gm[n];
                 G.A = hprev;
                 G.B = rows_plain((dir == 0 ? Y.w_hh_f : Y.w_hh_r), h);
@@ -261,12 +265,12 @@ static int bigru_fwd_impl(const twog_bigru_t* types, int n_types, int bs, int T,
                 G.M = rows; G.N = 3 * h; G.K = h; G.act = 0; G.accumulate = 0; G.batch = 1;
                 G.a_batch_stride = G.b_batch_stride = G.c_batch_stride = 0; G.a_colsum = nullptr; G.a_colsum_accumulate = 0; G.pad2_ = 0;
                 twog_gru_step_t& S = st[n];
-                S.gi = rows_be(Y.gi + (int64_t)t * E * 6 * h + dir * 3 * h, E, 6 * h, T);
+                S.gi = rows_be(Y.gi + (int64_t)t * E * ND * 3 * h + dir * 3 * h, E, ND * 3 * h, T);
                 S.gi2.ptr = nullptr; S.gi2.inner = 1; S.gi2.ld_inner = S.gi2.ld_outer = 0;
                 S.gh = rows_plain(tmp, 3 * h);
                 S.h_prev = hprev;
                 if (s == 0) S.h_prev.ptr = nullptr;
-                S.h_out = rows_be(Y.out + (int64_t)t * E * 2 * h + dir * h, E, 2 * h, T);
+                S.h_out = rows_be(Y.out + (int64_t)t * E * ND * h + dir * h, E, ND * h, T);
                 S.save = rows_be(Y.save + ((int64_t)dir * bs * T * E + (int64_t)t * E) * 4 * h, E, 4 * h, T);
                 S.u = nullptr; S.u_ld_outer = S.u_ld_inner = 0; S.u_inner = 1;
                 S.rows = rows; S.hidden = h;
@@ -286,8 +290,9 @@ static int bigru_fwd_impl(const twog_bigru_t* types, int n_types, int bs, int T,
     return 0;
 }
 
-// Backward through time. d_out: gradient wrt `out` [bs][T][E][2h]; writes d_gi [bs][T][E][6h] and
-// d_gh [bs][T][E][6h] (the caller turns them into dX / dW_ih / dW_hh / biases with large GEMMs).
+// Backward through time. d_out: gradient wrt `out` [bs][T][E][ND*h]; writes d_gi [bs][T][E][ND*3h] and
+// d_gh [bs][T][E][ND*3h] (the caller turns them into dX / dW_ih / dW_hh / biases with large GEMMs).
+template <int ND>
 static int bigru_bwd_impl(const twog_bigru_bwd_t* types, int n_types, int bs, int T, int hidden, void* chain_ws,
                           size_t chain_ws_bytes, void* stream) {
     if (n_types > 4) return -1;
@@ -298,20 +303,20 @@ static int bigru_bwd_impl(const twog_bigru_bwd_t* types, int n_types, int bs, in
         for (int k = 0; k < n_types; ++k) {
             const twog_bigru_bwd_t& Y = types[k];
             const int E = Y.E, rows = bs * E;
-            for (int dir = 0; dir < 2; ++dir) {
+            for (int dir = 0; dir < ND; ++dir) {
                 const int t = dir == 0 ? s : T - 1 - s;
                 const int tp = dir == 0 ? t - 1 : t + 1;
                 float* carry = Y.carry + (int64_t)dir * rows * h;
                 twog_gru_step_bwd_t& S = st[n];
-                S.dh = rows_be(Y.d_out + (int64_t)t * E * 2 * h + dir * h, E, 2 * h, T);
+                S.dh = rows_be(Y.d_out + (int64_t)t * E * ND * h + dir * h, E, ND * h, T);
                 if (s == T - 1) { S.dh2.ptr = nullptr; S.dh2.inner = 1; S.dh2.ld_inner = S.dh2.ld_outer = 0; }
                 else S.dh2 = rows_plain(carry, h);
                 S.save = rows_be(Y.save + ((int64_t)dir * bs * T * E + (int64_t)t * E) * 4 * h, E,
                                  4 * h, T);
                 if (s == 0) { S.h_prev.ptr = nullptr; S.h_prev.inner = 1; S.h_prev.ld_inner = S.h_prev.ld_outer = 0; }
-                else S.h_prev = rows_be(Y.out + (int64_t)tp * E * 2 * h + dir * h, E, 2 * h, T);
-                S.dgi = rows_be(Y.d_gi + (int64_t)t * E * 6 * h + dir * 3 * h, E, 6 * h, T);
-                S.dgh = rows_be(Y.d_gh + (int64_t)t * E * 6 * h + dir * 3 * h, E, 6 * h, T);
+                else S.h_prev = rows_be(Y.out + (int64_t)tp * E * ND * h + dir * h, E, ND * h, T);
+                S.dgi = rows_be(Y.d_gi + (int64_t)t * E * ND * 3 * h + dir * 3 * h, E, ND * 3 * h, T);
+                S.dgh = rows_be(Y.d_gh + (int64_t)t * E * ND * 3 * h + dir * 3 * h, E, ND * 3 * h, T);
                 S.dh_prev = rows_plain(carry, h);
                 S.u = nullptr; S.du = nullptr; S.u_ld_outer = S.u_ld_inner = 0; S.u_inner = 1;
                 S.rows = rows; S.hidden = h; S.dh_prev_accumulate = 0;
@@ -367,7 +372,7 @@ extern "C" int twog_bigru_fwd(const twog_bigru_t* types, int n_types, int bs, in
     twog_graph::Desc key;
     key.pod(dims).add(types, sizeof(twog_bigru_t) * n_types).pod(chain_ws).pod(chain_ws_bytes);
     return twog_graph::run(key, (hipStream_t)stream, [&](hipStream_t st) {
-        return bigru_fwd_impl(types, n_types, bs, T, hidden, chain_ws, chain_ws_bytes, st);
+        return bigru_fwd_impl<2>(types, n_types, bs, T, hidden, chain_ws, chain_ws_bytes, st);
     });
 }
 
@@ -378,6 +383,30 @@ extern "C" int twog_bigru_bwd(const twog_bigru_bwd_t* types, int n_types, int bs
     twog_graph::Desc key;
     key.pod(dims).add(types, sizeof(twog_bigru_bwd_t) * n_types).pod(chain_ws).pod(chain_ws_bytes);
     return twog_graph::run(key, (hipStream_t)stream, [&](hipStream_t st) {
-        return bigru_bwd_impl(types, n_types, bs, T, hidden, chain_ws, chain_ws_bytes, st);
+        return bigru_bwd_impl<2>(types, n_types, bs, T, hidden, chain_ws, chain_ws_bytes, st);
+    });
+}
+
+// Single-direction frame recurrence (include/twog_gcn.h): the ND = 1 instantiation of the loops above, with graph keys of
+// its own.
+extern "C" int twog_gru_seq_fwd(const twog_bigru_t* types, int n_types, int bs, int T, int hidden, void* chain_ws,
+                                size_t chain_ws_bytes, void* stream) {
+    if (n_types > 4 || n_types < 0) return -1;
+    const int dims[6] = {0x13, n_types, bs, T, hidden, twog_internal_gru_fwd_mode()};
+    twog_graph::Desc key;
+    key.pod(dims).add(types, sizeof(twog_bigru_t) * n_types).pod(chain_ws).pod(chain_ws_bytes);
+    return twog_graph::run(key, (hipStream_t)stream, [&](hipStream_t st) {
+        return bigru_fwd_impl<1>(types, n_types, bs, T, hidden, chain_ws, chain_ws_bytes, st);
+    });
+}
+
+extern "C" int twog_gru_seq_bwd(const twog_bigru_bwd_t* types, int n_types, int bs, int T, int hidden, void* chain_ws,
+                                size_t chain_ws_bytes, void* stream) {
+    if (n_types > 4 || n_types < 0) return -1;
+    const int dims[5] = {0x24, n_types, bs, T, hidden};
+    twog_graph::Desc key;
+    key.pod(dims).add(types, sizeof(twog_bigru_bwd_t) * n_types).pod(chain_ws).pod(chain_ws_bytes);
+    return twog_graph::run(key, (hipStream_t)stream, [&](hipStream_t st) {
+        return bigru_bwd_impl<1>(types, n_types, bs, T, hidden, chain_ws, chain_ws_bytes, st);
     });
 }

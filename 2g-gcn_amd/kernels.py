@@ -655,6 +655,82 @@ class HipKernels:
         self._check(self.lib.twog_bigru_bwd(arr, n, bs, T, h, *self.chain_workspace(dev), self._stream()), 'twog_bigru_bwd')
         return outs
 
+    # ---------------------------------------------------------------- single-direction frame GRU (baseline models)
+    def gru_seq_fwd(self, types, bs, T, h):
+        """types: list of dicts {gi (bs,T,E,3h), w_hh, b_hh (or None)}. Returns [(out (bs,T,E,h), save (bs,T,E,4h))].
+        The forward direction of bigru_fwd alone (twog_gru_seq_fwd); there is no persistent form."""
+        n = len(types)
+        arr = (L.BiGru * n)()
+        outs, keep = [], []
+        for i, y in enumerate(types):
+            gi = y['gi']
+            E = gi.shape[2]
+            dev = gi.device
+            assert gi.is_contiguous() and gi.shape == (bs, T, E, 3 * h)
+            out = torch.empty(bs, T, E, h, dtype=torch.float32, device=dev)
+            save = torch.empty(bs, T, E, 4 * h, dtype=torch.float32, device=dev)
+            tmp = torch.empty(bs * E, 3 * h, dtype=torch.float32, device=dev)
+            zeros = self.zeros(bs * E, h, device=dev)
+            keep += [tmp, zeros]
+            a = arr[i]
+            a.gi, a.w_hh_f, a.b_hh_f, a.w_hh_r, a.b_hh_r = gi.data_ptr(), y['w_hh'].data_ptr(), _ptr(y.get('b_hh')), 0, 0
+            a.out, a.save, a.tmp_gh, a.zeros, a.E = out.data_ptr(), save.data_ptr(), tmp.data_ptr(), zeros.data_ptr(), E
+            outs.append((out, save))
+        self._check(self.lib.twog_gru_seq_fwd(arr, n, bs, T, h, *self.chain_workspace(dev), self._stream()), 'twog_gru_seq_fwd')
+        return outs
+
+    def gru_seq_bwd(self, types, bs, T, h):
+        """types: list of dicts {d_out (bs,T,E,h), save, out, w_hh}. Returns [(d_gi, d_gh)] each (bs,T,E,3h)."""
+        n = len(types)
+        arr = (L.BiGruBwd * n)()
+        outs, keep = [], []
+        for i, y in enumerate(types):
+            d_out = y['d_out']
+            E = d_out.shape[2]
+            dev = d_out.device
+            assert d_out.is_contiguous() and d_out.shape == (bs, T, E, h)
+            d_gi = torch.empty(bs, T, E, 3 * h, dtype=torch.float32, device=dev)
+            d_gh = torch.empty(bs, T, E, 3 * h, dtype=torch.float32, device=dev)
+            carry = torch.empty(bs * E, h, dtype=torch.float32, device=dev)
+            keep.append(carry)
+            a = arr[i]
+            a.d_out, a.save, a.out = d_out.data_ptr(), y['save'].data_ptr(), y['out'].data_ptr()
+            a.w_hh_f, a.w_hh_r = y['w_hh'].data_ptr(), 0
+            a.d_gi, a.d_gh, a.carry, a.E = d_gi.data_ptr(), d_gh.data_ptr(), carry.data_ptr(), E
+            outs.append((d_gi, d_gh))
+        self._check(self.lib.twog_gru_seq_bwd(arr, n, bs, T, h, *self.chain_workspace(dev), self._stream()), 'twog_gru_seq_bwd')
+        return outs
+
+    # ---------------------------------------------------------------- entity pool + concat (baseline models)
+    def entity_pool_fwd(self, hfr, ofr, mask, object_head):
+        """hfr (bs,T,H,W), ofr (bs,T,O,W), mask (bs,O) -> hin (bs,T,H,2W) = [hfr | masked mean of ofr], and with
+        object_head oin (bs,T,O,2W) = [ofr | sum of hfr] (else None)."""
+        bs, T, H, W = hfr.shape
+        O = ofr.shape[2]
+        assert hfr.is_contiguous() and ofr.is_contiguous() and mask.is_contiguous() and mask.dtype == torch.float32
+        assert ofr.shape == (bs, T, O, W) and mask.shape == (bs, O)
+        hin = torch.empty(bs, T, H, 2 * W, dtype=torch.float32, device=hfr.device)
+        oin = torch.empty(bs, T, O, 2 * W, dtype=torch.float32, device=hfr.device) if object_head else None
+        d = L.EntityPool()
+        d.hfr, d.ofr, d.mask, d.hin, d.oin = hfr.data_ptr(), ofr.data_ptr(), mask.data_ptr(), hin.data_ptr(), _ptr(oin)
+        d.bs, d.T, d.H, d.O, d.W = bs, T, H, O, W
+        self._check(self.lib.twog_entity_pool_fwd(C.byref(d), self._stream()), 'twog_entity_pool_fwd')
+        return hin, oin
+
+    def entity_pool_bwd(self, d_hin, d_oin, mask, O):
+        """Gradients of entity_pool_fwd: returns (d_hfr (bs,T,H,W), d_ofr (bs,T,O,W)). d_oin None: no object head."""
+        bs, T, H, W2 = d_hin.shape
+        W = W2 // 2
+        assert d_hin.is_contiguous() and mask.is_contiguous() and mask.shape == (bs, O)
+        assert d_oin is None or (d_oin.is_contiguous() and d_oin.shape == (bs, T, O, W2))
+        d_hfr = torch.empty(bs, T, H, W, dtype=torch.float32, device=d_hin.device)
+        d_ofr = torch.empty(bs, T, O, W, dtype=torch.float32, device=d_hin.device)
+        d = L.EntityPoolBwd()
+        d.d_hin, d.d_oin, d.mask, d.d_hfr, d.d_ofr = d_hin.data_ptr(), _ptr(d_oin), mask.data_ptr(), d_hfr.data_ptr(), d_ofr.data_ptr()
+        d.bs, d.T, d.H, d.O, d.W = bs, T, H, O, W
+        self._check(self.lib.twog_entity_pool_bwd(C.byref(d), self._stream()), 'twog_entity_pool_bwd')
+        return d_hfr, d_ofr
+
     # ---------------------------------------------------------------- single GRU gate steps (general segment loop)
     @staticmethod
     def _u_fields(g, u):

@@ -241,6 +241,47 @@ int twog_bigru_bwd(const twog_bigru_bwd_t* types, int n_types, int bs, int T, in
 int twog_bigru_bwd_persistent_supported(const twog_bigru_bwd_t* types, int n_types, int bs, int hidden);
 int twog_bigru_bwd_persistent(const twog_bigru_bwd_t* types, int n_types, int bs, int T, int hidden, void* sync, void* stream);
 
+/* Single-direction frame recurrence: nn.GRU(bidirectional=False) applied per entity slice by the baseline models'
+ * _process_frame_level_rnn (vhoi/models.py:70-87, :157-175; modules :25-28, :102-105). The same descriptors and the
+ * same per-step machinery as twog_bigru_fwd / twog_bigru_bwd with the forward direction only, so every row is h (not 2h)
+ * wide and the reverse weights are not read (w_hh_r / b_hh_r may be NULL):
+ *   twog_bigru_t:     gi [bs][T][E][3h], out [bs][T][E][h], save [bs][T][E][4h], tmp_gh [bs*E][3h], zeros [bs*E][h]
+ *   twog_bigru_bwd_t: d_out [bs][T][E][h], d_gi / d_gh [bs][T][E][3h], carry [bs*E][h]
+ * There is no persistent form. */
+int twog_gru_seq_fwd(const twog_bigru_t* types, int n_types, int bs, int T, int hidden, void* chain_ws,
+                     size_t chain_ws_bytes, void* stream);
+int twog_gru_seq_bwd(const twog_bigru_bwd_t* types, int n_types, int bs, int T, int hidden, void* chain_ws,
+                     size_t chain_ws_bytes, void* stream);
+
+/* Entity pooling + concatenation of the baseline models (vhoi/models.py:59-68 BimanualBaseline, :132-154 CAD120Baseline):
+ *   hin[b][t][h] = [ hfr[b][t][h] | sum_o mask[b][o] ofr[b][t][o] / max(sum_o mask[b][o], 1) ]            [2W]
+ *   oin[b][t][o] = [ ofr[b][t][o] | sum_h hfr[b][t][h] ]      (CAD-120 only: oin NULL skips it)         [2W]
+ * hfr [bs][T][H][W], ofr [bs][T][O][W] (W = directions x hidden), mask [bs][O]. One launch; fixed-order reductions, no
+ * atomics. H >= 1, O >= 1, any W >= 1. */
+typedef struct {
+    const float* hfr;
+    const float* ofr;
+    const float* mask;
+    float* hin;
+    float* oin;
+    int32_t bs, T, H, O, W;
+    int32_t pad_;
+} twog_entity_pool_t;
+int twog_entity_pool_fwd(const twog_entity_pool_t* p, void* stream);
+/* Backward of the above: d_hfr = d_hin[:, :W] (+ sum_o d_oin[o][W:]),
+ * d_ofr[o] = (d_oin[o][:W]) + mask[o] / max(sum mask, 1) * sum_h d_hin[h][W:]   (the d_oin terms only if d_oin != NULL).
+ * Both outputs are written, not accumulated. */
+typedef struct {
+    const float* d_hin;
+    const float* d_oin;
+    const float* mask;
+    float* d_hfr;
+    float* d_ofr;
+    int32_t bs, T, H, O, W;
+    int32_t pad_;
+} twog_entity_pool_bwd_t;
+int twog_entity_pool_bwd(const twog_entity_pool_bwd_t* p, void* stream);
+
 /* ===============================================================================================================
  * Fusion-level attention message passing (vhoi/models.py:1004-1475, :1693-1754) for message_type 'v2', granularity
  * 'v1' (generic), aggregation 'att', attention styles 'v2'/'v3' (dot / scaled dot product).
