@@ -176,6 +176,21 @@ REL_MSG_SENDER, REL_MSG_PAIR = 0, 1
 
 LOSS_MAX_TERMS, LOSS_BLOCKS = 16, 64  # TWOG_LOSS_MAX_TERMS, TWOG_LOSS_BLOCKS
 
+NORM_MAX_RANGES, NORM_BLOCKS = 8, 2048   # TWOG_NORM_MAX_RANGES, TWOG_NORM_BLOCKS
+
+
+class Ranges(C.Structure):  # twog_ranges_t
+    _fields_ = [('begin', C.c_int64 * NORM_MAX_RANGES), ('end', C.c_int64 * NORM_MAX_RANGES), ('n_ranges', C.c_int32),
+                ('pad_', C.c_int32)]
+
+
+MTL_PASS, MTL_SOFTMAX, MTL_MSE, MTL_MAE = 0, 1, 2, 3   # TWOG_MTL_*
+MTL_MAX_TERMS = 16   # TWOG_MTL_MAX_TERMS
+
+
+class Mtl(C.Structure):  # twog_mtl_t
+    _fields_ = [('kind', C.c_int32 * MTL_MAX_TERMS), ('n', C.c_int32), ('pad_', C.c_int32)]
+
 # name -> (argtypes) ; every function returns int except twog_version
 _I, _L, _F, _P = C.c_int, C.c_int64, C.c_float, C.c_void_p
 SIGNATURES = {
@@ -257,6 +272,10 @@ SIGNATURES = {
     'twog_adam_step': [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P],
     'twog_multitask_loss_fwd': [C.POINTER(Loss), _I, _P, _P, _P, _P],
     'twog_multitask_loss_bwd': [C.POINTER(Loss), _I, _P, _P, _P],
+    'twog_grad_norm': [_P, C.POINTER(Ranges), _F, _F, _P, _P, _P],
+    'twog_adam_step_coef': [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P, _P],
+    'twog_mtl_weight_fwd': [C.POINTER(Mtl), _P, _P, _P, _P],
+    'twog_mtl_weight_bwd': [C.POINTER(Mtl), _P, _P, _P, _P, _P, _I, _P],
     'twog_predict_labels': [_P, _I, _I, _I, _I, _I, _I, _P, _P],
     'twog_f1_at_k': [_P, _P, _I, _I, _I, C.c_double, _L, _I, _P, _P, _P, _P],
 }

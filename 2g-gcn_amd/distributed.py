@@ -47,13 +47,19 @@ def _drop_extras(model_ref, wrapper_ref, installed):
 class FlatParameters:
     """Re-homes every parameter of `module` as a view into one flat buffer; same for the gradients."""
 
-    def __init__(self, module: torch.nn.Module, stage_of=None):
+    def __init__(self, module: torch.nn.Module, stage_of=None, extra_modules=()):
         """stage_of (optional): name -> int; parameters are laid out by ascending stage (stable), and
-        `stage_ranges[stage] = (begin, end)` gives each stage's slice of the flat buffers."""
+        `stage_ranges[stage] = (begin, end)` gives each stage's slice of the flat buffers.
+        extra_modules: further modules (the multi-task loss learner) whose parameters follow the model's, in a stage of
+        their own after the model's last one. `module_ranges[0]` is the model's (begin, end) slice, `module_ranges[1 + j]`
+        that of extra_modules[j]."""
         named = list(module.named_parameters())
         if stage_of is not None:
             named.sort(key=lambda kv: stage_of(kv[0]))
-        params = [p for _, p in named]
+        groups = [named] + [list(m.named_parameters()) for m in extra_modules]
+        params = [p for g in groups for _, p in g]
+        if len({id(p) for p in params}) != len(params):
+            raise ValueError('a parameter belongs to the model and to an extra module (or to two extra modules)')
         dev = params[0].device
         sizes = [(p.numel() + 3) // 4 * 4 for p in params]  # keep every view 16-byte aligned for the kernels
         total = sum(sizes)
@@ -71,6 +77,14 @@ class FlatParameters:
         from . import ops
         ops.enable_grad_sinks(params)   # the backward kernels add straight into these flat gradient views
         self.numel = total
+        self.module_ranges = []
+        off = k = 0
+        for g in groups:
+            b = off
+            for _ in g:
+                off += sizes[k]
+                k += 1
+            self.module_ranges.append((b, off))
         self.stage_ranges = {}
         if stage_of is not None:
             off = 0
@@ -79,6 +93,8 @@ class FlatParameters:
                 b, _e = self.stage_ranges.get(st, (off, off))
                 self.stage_ranges[st] = (b, off + n)
                 off += n
+            if len(groups) > 1:   # the extra modules' gradients are final as soon as the backward pass begins
+                self.stage_ranges[max(self.stage_ranges, default=-1) + 1] = (self.module_ranges[1][0], total)
 
     def zero_grad(self):
         K = get_kernels()
@@ -92,18 +108,37 @@ class FlatParameters:
 
 
 class FusedAdam:
-    """torch.optim.Adam semantics (reference train.py:39) as one fused kernel over the flat buffers."""
+    """torch.optim.Adam semantics (reference train.py:39) as one fused kernel over the flat buffers.
 
-    def __init__(self, flat: FlatParameters, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    max_grad_norm > 0: the reference's `clip_gradient_at` (train_utils.py:149-153), torch.nn.utils.clip_grad_norm_ over the
+    MODEL's parameters between backward() and step(), folded into the step: one norm over the model's slice of the (already
+    all-reduced) gradient buffer, measured on the averaged gradient g * grad_scale, then Adam reading the clip coefficient
+    from the device. The slices of extra modules (FlatParameters(extra_modules=...): the loss learner) are stepped without
+    it. step() then returns the pre-clip norm as a 0-d device tensor (what clip_grad_norm_ returns); nothing is read on
+    the host."""
+
+    def __init__(self, flat: FlatParameters, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0):
+        if not max_grad_norm >= 0.0:
+            raise ValueError(f'max_grad_norm must be >= 0, got {max_grad_norm}')
         self.flat, self.lr, self.betas, self.eps, self.wd = flat, lr, betas, eps, weight_decay
+        self.max_grad_norm = float(max_grad_norm)
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
         self.step_count = 0
 
     def step(self, grad_scale=1.0):
         self.step_count += 1
-        get_kernels().adam_step(self.flat.flat, self.flat.grad, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0],
-                                self.betas[1], self.eps, self.wd, self.step_count, grad_scale)
+        K, f = get_kernels(), self.flat
+        args = (self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, grad_scale)
+        if not self.max_grad_norm:
+            K.adam_step(f.flat, f.grad, self.exp_avg, self.exp_avg_sq, *args)
+            return None
+        b, e = f.module_ranges[0]
+        out = K.grad_norm(f.grad, [(b, e)], grad_scale, self.max_grad_norm)
+        K.adam_step_coef(f.flat[b:e], f.grad[b:e], self.exp_avg[b:e], self.exp_avg_sq[b:e], *args, out[1:2])
+        if e < f.numel:   # the extra modules: never clipped
+            K.adam_step(f.flat[e:], f.grad[e:], self.exp_avg[e:], self.exp_avg_sq[e:], *args)
+        return out[0]
 
 
 def _ranks_share_a_device(group, world):
@@ -130,7 +165,7 @@ class DataParallel:
 
     def __init__(self, model: torch.nn.Module, process_group=None, bucket_mb: int = 64, broadcast: bool = True,
                  sync_bn: bool = False, global_noise_seed: int = None, overlap: bool = True,
-                 count_weighted_loss: bool = False, force_collectives: bool = False):
+                 count_weighted_loss: bool = False, force_collectives: bool = False, extra_modules=()):
         """sync_bn: the geometric-level BatchNorm uses the statistics of the GLOBAL batch (one all-reduce of 2*4N fp64
         sums per step). count_weighted_loss: every term of the criterion (losses.multi_task_loss) is
         normalised by the GLOBAL number of valid (non-ignored) targets instead of the rank's own (one all-reduce of the
@@ -141,8 +176,13 @@ class DataParallel:
         (standard DDP semantics; equal-length synthetic clips make the counts equal anyway).
         force_collectives: run every collective (broadcast, stage-hooked asynchronous all-reduces, count / statistics
         reductions) even in a process group of ONE rank, where they are identities -- lets a single-GPU box execute the
-        RCCL path itself (tests/test_distributed_gpu.py)."""
+        RCCL path itself (tests/test_distributed_gpu.py).
+        extra_modules: modules trained beside the model (the multi-task loss learner, multi_task.MultiTaskLossLearner):
+        their parameters live in the same flat buffers after the model's, are broadcast and all-reduced with them and
+        stepped by the same FusedAdam (the reference's optimizer.add_param_group, train.py:42-46); FusedAdam's clipping
+        leaves them out."""
         self.model = model
+        self.extra_modules = list(extra_modules)
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
         if force_collectives and not (dist.is_available() and dist.is_initialized()):
@@ -190,7 +230,8 @@ class DataParallel:
             self._installed['noise_shard'] = shard
         # gradients are laid out in the order the backward pass finishes them (ops.grad_ready_stage), so that each
         # stage's all-reduce can start from inside the backward pass and overlap with the rest of it
-        self.flat = FlatParameters(model, stage_of=ops.grad_ready_stage if overlap else None)
+        self.flat = FlatParameters(model, stage_of=ops.grad_ready_stage if overlap else None,
+                                   extra_modules=self.extra_modules)
         self.bucket = max(1, bucket_mb) * (1 << 20) // 4
         if overlap and self.collective:
             # scoped to this model; close() removes it. A WeakMethod: the table must not own the wrapper (see above)
@@ -198,8 +239,9 @@ class DataParallel:
         weakref.finalize(self, _drop_extras, weakref.ref(model), me_ref, self._installed)
         if self.collective and broadcast:
             dist.broadcast(self.flat.flat, src=0, group=self.group)
-            for b in model.buffers():
-                dist.broadcast(b, src=0, group=self.group)
+            for m in [model] + self.extra_modules:
+                for b in m.buffers():
+                    dist.broadcast(b, src=0, group=self.group)
             self.collective_calls += 1
 
     def close(self):

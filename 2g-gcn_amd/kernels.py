@@ -1228,6 +1228,65 @@ class HipKernels:
                                             exp_avg_sq.data_ptr(), param.numel(), lr, beta1, beta2, eps, weight_decay,
                                             step, grad_scale, self._stream()), 'twog_adam_step')
 
+    # ---------------------------------------------------------------- training-step options (csrc/train_opts.hip)
+    def grad_norm(self, buf, ranges, scale, max_norm, out=None):
+        """Global L2 norm of buf[b:e] for (b, e) in ranges, times |scale|, and the clip coefficient
+        max_norm / (norm + 1e-6): out [2] fp32 = (norm, coef), on the device (no host read)."""
+        assert buf.dtype == torch.float32 and buf.dim() == 1 and buf.is_contiguous()
+        ranges = [(int(b), int(e)) for b, e in ranges]
+        if len(ranges) > L.NORM_MAX_RANGES:
+            raise ValueError(f'at most {L.NORM_MAX_RANGES} ranges per call')
+        R = L.Ranges()
+        for i, (b, e) in enumerate(ranges):
+            if not 0 <= b <= e <= buf.numel():
+                raise ValueError(f'range {(b, e)} outside a buffer of {buf.numel()} elements')
+            R.begin[i], R.end[i] = b, e
+        R.n_ranges = len(ranges)
+        if out is None:
+            out = torch.empty(2, dtype=torch.float32, device=buf.device)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= 2
+        partials = self.workspace(L.NORM_BLOCKS * 8, buf.device, 'norm')
+        self._check(self.lib.twog_grad_norm(buf.data_ptr(), C.byref(R), float(scale), float(max_norm), partials.data_ptr(),
+                                            out.data_ptr(), self._stream()), 'twog_grad_norm')
+        return out
+
+    def adam_step_coef(self, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
+                       coef):
+        """adam_step with the gradient multiplied by min(coef[0], 1) (coef: a device fp32 scalar; NaN: no clipping)."""
+        n = param.numel()
+        assert grad.numel() == exp_avg.numel() == exp_avg_sq.numel() == n and coef.dtype == torch.float32
+        self._check(self.lib.twog_adam_step_coef(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(),
+                                                 exp_avg_sq.data_ptr(), n, lr, beta1, beta2, eps, weight_decay, step,
+                                                 grad_scale, coef.data_ptr(), self._stream()), 'twog_adam_step_coef')
+
+    @staticmethod
+    def _mtl_spec(kinds):
+        if len(kinds) > L.MTL_MAX_TERMS:
+            raise ValueError(f'at most {L.MTL_MAX_TERMS} loss terms')
+        spec = L.Mtl()
+        for i, k in enumerate(kinds):
+            spec.kind[i] = int(k)
+        spec.n = len(kinds)
+        return spec
+
+    def mtl_weight_fwd(self, kinds, losses, log_sds):
+        """The multi-task loss learner's forward over [n] losses (kinds: MTL_PASS / _SOFTMAX / _MSE / _MAE per term)."""
+        assert losses.is_contiguous() and log_sds.is_contiguous() and losses.numel() == log_sds.numel() == len(kinds)
+        out = torch.empty_like(losses)
+        self._check(self.lib.twog_mtl_weight_fwd(C.byref(self._mtl_spec(kinds)), losses.data_ptr(), log_sds.data_ptr(),
+                                                 out.data_ptr(), self._stream()), 'twog_mtl_weight_fwd')
+        return out
+
+    def mtl_weight_bwd(self, kinds, losses, log_sds, dout, dlog_sds, accumulate):
+        """Returns d(losses) [n]; d(log_sds) is added into (accumulate) or stored in `dlog_sds`."""
+        dout = dout.contiguous()
+        assert dlog_sds.is_contiguous() and dlog_sds.numel() == len(kinds)
+        dlosses = torch.empty_like(losses)
+        self._check(self.lib.twog_mtl_weight_bwd(C.byref(self._mtl_spec(kinds)), losses.data_ptr(), log_sds.data_ptr(),
+                                                 dout.data_ptr(), dlosses.data_ptr(), dlog_sds.data_ptr(), int(accumulate),
+                                                 self._stream()), 'twog_mtl_weight_bwd')
+        return dlosses
+
 
     # ---------------------------------------------------------------- multi-task loss
     def _loss_terms(self, terms, dinputs=None):

@@ -711,6 +711,52 @@ int twog_multitask_loss_bwd(const twog_loss_t* terms, int n_terms, const double*
                             void* stream);
 
 /* ===============================================================================================================
+ * Training-step options of the reference's trainer on the fused step (pyrutils/torch/train_utils.py:149-153,
+ * train.py:42-46; csrc/train_opts.hip).
+ *
+ * twog_grad_norm: the global L2 norm of clip_grad_norm_(model.parameters(), max_norm) over the flat gradient buffer `buf`
+ *   restricted to ranges [begin[r], end[r]) (element indices), of the gradient g * scale (scale: the step's 1 / world_size):
+ *     norm = fp32( sqrt( sum_r sum_i (double) buf[i]^2 ) * |scale| )      (fp64 sum: finite for every finite fp32 input)
+ *     coef = max_norm * (1 / (norm + 1e-6))                                (fp32, torch's max_norm / (total_norm + 1e-6))
+ *   out[0] = norm, out[1] = coef. The sum has a fixed order (TWOG_NORM_BLOCKS partial sums in `partials`, then one
+ *   workgroup): bit-identical results from run to run; no atomics. Two launches, no host synchronisation.
+ * twog_adam_step_coef: twog_adam_step with every gradient read as fl(fl(g * grad_scale) * k), k = coef[0] if coef[0] < 1
+ *   else 1 (a NaN coefficient does not clip: the rule of the reference's torch 1.5.1). k = 1 gives exactly
+ *   twog_adam_step's result. A sub-range is stepped by offsetting the four pointers.
+ * twog_mtl_weight_fwd / _bwd: the multi-task loss learner (Kendall et al.; pyrutils/torch/multi_task.py:10-75) over the
+ *   n loss scalars in one launch each. Per term i, with s = log_sds[i], L = losses[i]:
+ *     kind SOFTMAX  w = exp(-2 s)        MSE  w = 0.5 exp(-2 s)        MAE  w = sqrt(2) exp(-s)
+ *     forward   out[i] = w L + s                      (kind PASS: out[i] = L, the term is not learned)
+ *     backward  dlosses[i] = dout[i] w,  dlog_sds[i] (+)= dout[i] (w' L + 1)   (PASS: dlosses[i] = dout[i], dlog_sds 0)
+ *   dlog_sds is accumulated into when `accumulate` is non-zero (the flat gradient buffer), stored otherwise; dlosses may be
+ *   NULL.
+ * =============================================================================================================== */
+#define TWOG_NORM_MAX_RANGES 8
+#define TWOG_NORM_BLOCKS 2048
+typedef struct {
+    int64_t begin[TWOG_NORM_MAX_RANGES];
+    int64_t end[TWOG_NORM_MAX_RANGES];
+    int32_t n_ranges;
+    int32_t pad_;
+} twog_ranges_t;
+/* partials: workspace of TWOG_NORM_BLOCKS doubles; out: 2 floats. */
+int twog_grad_norm(const float* buf, const twog_ranges_t* ranges, float scale, float max_norm, double* partials, float* out,
+                   void* stream);
+int twog_adam_step_coef(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                        float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                        const float* coef, void* stream);
+enum { TWOG_MTL_PASS = 0, TWOG_MTL_SOFTMAX = 1, TWOG_MTL_MSE = 2, TWOG_MTL_MAE = 3 };
+#define TWOG_MTL_MAX_TERMS 16
+typedef struct {
+    int32_t kind[TWOG_MTL_MAX_TERMS];
+    int32_t n;
+    int32_t pad_;
+} twog_mtl_t;
+int twog_mtl_weight_fwd(const twog_mtl_t* spec, const float* losses, const float* log_sds, float* out, void* stream);
+int twog_mtl_weight_bwd(const twog_mtl_t* spec, const float* losses, const float* log_sds, const float* dout, float* dlosses,
+                        float* dlog_sds, int accumulate, void* stream);
+
+/* ===============================================================================================================
  * Inference post-processing on the device.
  * twog_predict_labels: predict.py:64-70 (repeat_interleave by `downsampling` along time, match_shape :95-116 to T_out
  *   steps) + :195-201 (argmax over classes; ties -> first index): logp [bs][C][T][E] -> labels int64 [bs][T_out][E],
