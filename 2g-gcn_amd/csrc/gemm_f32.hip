@@ -52,7 +52,7 @@ struct Group {
     int xcd_split;   // split-K launches with splitk % 8 == 0: XCD x works the k-splits x, x + 8, ... of ALL tiles (see gemm_tile)
     float* slabs;    // split-K partials: [problem-tile-major] see below
     float* cs_part;  // split-K launches with a_colsum requests: [split][tile][128] partial column sums (tiles with tn == 0)
-    unsigned* xcnt;  // XS kernels (split-K over workgroups, combined in the launch): arrival ticket per tile, zero between launches
+    unsigned* xcnt;  // XS / XL chain kernels (split-K over workgroups, combined in the launch): arrival ticket per tile, zero between launches
     int xs_early;    // XS: every slice requests the epilogue operands before its reduction loop (small launches: the
                      // combining workgroup then has them when it draws the last ticket; large ones fetch them once, late)
 };
@@ -403,7 +403,7 @@ __device__ __forceinline__ void gemm_mainloop(const twog_rows_t A, const twog_ro
 // of the largest output for K = 512 ... 61 440); adding the two products m l and l m (exact to 2^-30) changes no digit of
 // that error and costs 15 % (TWOG_X3_PRODUCTS=8 at build time; the shipped default is 6). The truncating split makes the
 // dropped terms carry the sign of a b -- a bias towards zero of ~2^-24 |a b| per product, far below what the accumulate
-// itself does (see TMPACC in compute()). Six bf16 MFMAs of 16 k-steps cost 192 cycles per
+// itself does (see TTMP in compute()). Six bf16 MFMAs of 16 k-steps cost 192 cycles per
 // 32x32 block where the fp32 MFMA (32x32x2) needs 512: 2.67x the matrix rate for the same result to fp32 rounding.
 //
 // Structure: 128x128 tile, 8 waves of 32x64, k-tiles of 16 (one bf16 MFMA k-step), the same branch-free 16-byte global
@@ -445,13 +445,11 @@ __device__ __forceinline__ void split3(const f32x4 v, i32x2& ph, i32x2& pm, i32x
 #ifndef TWOG_X3_PRODUCTS
 #define TWOG_X3_PRODUCTS 6
 #endif
-#ifndef TWOG_X3_TMPACC
-#define TWOG_X3_TMPACC 0   // 1: 128x128 class with each k-step's products through a fresh accumulator, added by fp32 VALU adds (see
-#endif                     // compute()): removes the accumulate bias, but at 128 VGPRs (two workgroups per CU) the temporary spills
-// (TTMP, a template flag of the TT kernels selected at run time by TWOG_X3_DW_SPLIT_ACC=1: the same fresh-accumulator form with
-// ONE workgroup per CU -- 256 VGPRs, no spill, four register stages kept. Same-sign K = 61 440: bias -2.07e-6 -> -4.5e-8, rms
-// 2.08e-6 -> 9.3e-8 (the fp32-MFMA kernel: 1.07e-7); the dW launches +18 ... 25 %, the bs64 step 65.9 -> 68.9 ms: off by default,
-// profiles/r05_dw_split_accumulator.txt)
+// TTMP, a template flag of the TT kernels selected at run time by TWOG_X3_DW_SPLIT_ACC=1: each k-step's products through a
+// fresh accumulator, added by fp32 VALU adds (see compute()), with ONE workgroup per CU -- 256 VGPRs, no spill, four register
+// stages kept (at two workgroups per CU the temporary spills: profiles/HISTORY.md section 8). Same-sign K = 61 440: bias
+// -2.07e-6 -> -4.5e-8, rms 2.08e-6 -> 9.3e-8 (the fp32-MFMA kernel: 1.07e-7); the dW launches +18 ... 25 %, the bs64 step
+// 65.9 -> 68.9 ms: off by default, profiles/r05_dw_split_accumulator.txt
 
 constexpr int X3_PRODUCTS = TWOG_X3_PRODUCTS;  // chunk products per element product: 8 (exact to 2^-30) or 6 (drops m l, l m)
 constexpr int X3_BK = 16;                    // one v_mfma_f32_32x32x16_bf16 k-step per k-tile
@@ -464,30 +462,17 @@ __device__ __forceinline__ int x3_swz(int k) { return ((k & 3) << 2) | ((k >> 2)
 
 // cs (k-major A only): when cs_on, every thread also adds the A values it stages (4 consecutive tile columns of one k row per
 // k-tile) into cs -- the column sums of A over this workgroup's k-range, finished by gemm_tile (twog_gemm_t::a_colsum).
-// KU (round 6): k-tiles per barrier interval, KU sub-images per LDS stage -- for launches of at most one tile per CU (the
-// segment level's per-step projection: 240 tiles), where ONE workgroup per CU moves through a barrier every 12 MFMAs per wave
-// and nothing else hides the fragment reads and the barrier's skew. KU = 2 needs 2 x 2 x 24 KB of LDS and ~64 more registers:
-// one workgroup per CU, which is what such a launch has anyway. Same MFMA sequence into the same accumulators: bit-identical.
-// KS = 2 (round 6): SIXTEEN waves = two k-groups of eight, each with its own pair of LDS stages and its own half of the
-// reduction (the caller passes the group's k-range; both halves hold the same number of k-tiles, so the workgroup-wide
-// barriers match) -- four waves per SIMD for launches of at most ONE tile per CU, which is what the two co-resident
-// workgroups of a big launch have and an 8-wave tile alone on its CU has not. gemm_tile adds the two partial tiles.
-// PIPE (round 6): the fragment reads of k-tile t + 1 are issued BEFORE the MFMAs of k-tile t (two fragment sets in registers,
-// three LDS stages: tile t + 1 is read and tile t + 2 stored while tile t is multiplied). Without it every wave of the
-// workgroup reads its nine fragments right behind the barrier and multiplies afterwards: the CU's LDS phase (768 cycles per
-// k-tile) and its MFMA phase (768 per SIMD) alternate. ~36 more registers: ONE workgroup per CU (the launches of at most one
-// tile per CU). Same MFMA sequence into the same accumulators: bit-identical.
-template <bool AKM, bool BKM, bool KG, bool TTMP = false, int KU = 1, int KS = 1, bool PIPE = false>
+// (Built, measured and dropped in round 6, all bit-identical and none faster for the launches of at most one tile per CU:
+// two k-tiles per barrier interval, sixteen waves as two k-groups on one tile, fragment reads one k-tile ahead of the MFMAs;
+// profiles/r06_gemm128_*.txt.)
+template <bool AKM, bool BKM, bool KG, bool TTMP = false>
 __device__ __forceinline__ void gemm_mainloop_x3(const twog_rows_t A, const twog_rows_t B, int M, int N, int m0, int n0,
                                                  int k_begin, int k_end, float* smem, f32x16 (&acc)[1][2], f32x4& cs, bool cs_on) {
     constexpr int BM = 128, BN = 128, NT = 512, XK = X3_BK;
-    constexpr bool TMP = TWOG_X3_TMPACC || TTMP;
-    static_assert(KU == 1 || (!AKM && !BKM && !KG && !TMP), "KU > 1: the row-major (forward) form only");
-    static_assert(KS == 1 || (KS == 2 && KU == 1 && !AKM && !BKM && !KG && !TMP), "KS = 2: the row-major (forward) form only");
     constexpr int PA = AKM ? X3_TPLANE : X3_RPLANE, PB = BKM ? X3_TPLANE : X3_RPLANE;
-    // stage b: A planes at b * X3_STAGE, B planes behind them (k-group 1: behind k-group 0's two stages)
-    char* lds = reinterpret_cast<char*>(smem) + (KS == 2 ? (int)(threadIdx.x >> 9) * 2 * KU * X3_STAGE : 0);
-    const int tid = KS == 2 ? (int)(threadIdx.x & 511) : (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // stage b: A planes at b * X3_STAGE, B planes behind them
+    char* lds = reinterpret_cast<char*>(smem);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = (wave >> 1) * 32, wn = (wave & 1) * 64;
     using ARegs = TileRegs<(AKM ? XK : BM), (AKM ? BM : XK), NT>;
     using BRegs = TileRegs<(BKM ? XK : BN), (BKM ? BN : XK), NT>;
@@ -517,7 +502,7 @@ __device__ __forceinline__ void gemm_mainloop_x3(const twog_rows_t A, const twog
             sb_off = 3 * PA + rr * X3_RROW + 16 * ((cq >> 1) ^ ((rr >> 4) & 1)) + 8 * (cq & 1);
         }
     }
-    struct Stage { f32x4 a, b; f32x4 a2[KU > 1 ? KU - 1 : 1], b2[KU > 1 ? KU - 1 : 1]; };   // (a2 / b2: k-tiles 1 .. KU-1 of the interval)
+    struct Stage { f32x4 a, b; };
     // KG: a k-major operand whose rows (= k) are (outer, inner) grouped, e.g. "all but the first time step of every clip":
     // the (outer, inner) position of this thread's row is carried from k-tile to k-tile (k only moves forward; the clamped
     // tail repeats the last tile), no division in the loop. Offsets stay below 2^32 bytes (vec_ok).
@@ -550,18 +535,10 @@ __device__ __forceinline__ void gemm_mainloop_x3(const twog_rows_t A, const twog
             const int sb = (int)(BKM ? (uint32_t)k0 * (uint32_t)B.ld_outer * 4u : (uint32_t)k0 * 4u);
             r.b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, (int)ob, sb, 0));
         }
-        if constexpr (KU > 1) {
-#pragma unroll
-            for (int u = 1; u < KU; ++u) {
-                const int su = (int)((uint32_t)(k0 + u * XK) * 4u);
-                r.a2[u - 1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, (int)oa, su, 0));
-                r.b2[u - 1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, (int)ob, su, 0));
-            }
-        }
     };
-    const int nkt = (k_end - k_begin) / (XK * KU);
+    const int nkt = (k_end - k_begin) / XK;
     auto split_store = [&](const Stage& r, int buf, int t) {   // t: index of the k-tile held by r (clamped repeats: t >= nkt)
-        char* base = lds + buf * KU * X3_STAGE;
+        char* base = lds + buf * X3_STAGE;
         i32x2 ph, pm, pl;
         if constexpr (AKM && BKM && !KG) {
             if (cs_on && t < nkt) cs += r.a;
@@ -574,20 +551,6 @@ __device__ __forceinline__ void gemm_mainloop_x3(const twog_rows_t A, const twog
         *reinterpret_cast<i32x2*>(base + sb_off) = ph;
         *reinterpret_cast<i32x2*>(base + sb_off + PB) = pm;
         *reinterpret_cast<i32x2*>(base + sb_off + 2 * PB) = pl;
-        if constexpr (KU > 1) {
-#pragma unroll
-            for (int u = 1; u < KU; ++u) {
-                char* bu = base + u * X3_STAGE;
-                split3(r.a2[u - 1], ph, pm, pl);
-                *reinterpret_cast<i32x2*>(bu + sa_off) = ph;
-                *reinterpret_cast<i32x2*>(bu + sa_off + PA) = pm;
-                *reinterpret_cast<i32x2*>(bu + sa_off + 2 * PA) = pl;
-                split3(r.b2[u - 1], ph, pm, pl);
-                *reinterpret_cast<i32x2*>(bu + sb_off) = ph;
-                *reinterpret_cast<i32x2*>(bu + sb_off + PB) = pm;
-                *reinterpret_cast<i32x2*>(bu + sb_off + 2 * PB) = pl;
-            }
-        }
     };
     // fragment addressing: lane l = (r = l & 31 row / column of the 32x32 block, h = l >> 5 half of the 16-deep k-step)
     const int r32 = lane & 31, h = lane >> 5;
@@ -613,55 +576,52 @@ __device__ __forceinline__ void gemm_mainloop_x3(const twog_rows_t A, const twog
         return __builtin_bit_cast(bf16x8, v);
     };
     auto compute = [&](int buf) {
-#pragma unroll
-      for (int u_ = 0; u_ < KU; ++u_) {
-        const char* base = lds + (buf * KU + u_) * X3_STAGE;
+        const char* base = lds + buf * X3_STAGE;
         // X3_PRODUCTS chunk products per block, smallest terms first. 6 (shipped): everything >= 2^-16 |a b|; 8 (TWOG_X3_PRODUCTS=8
         // at build time): also m l and l m -- measured identical to three digits (profiles/r04_x3_products_6_vs_8*.txt).
         // WHERE the products are added matters more than how many there are: the bf16 MFMA's accumulate is not a
         // round-to-nearest fp32 add -- every v_mfma_f32_32x32x16_bf16 into a LARGE accumulator loses ~2^-29 of it towards
         // zero (tools/x3_bias_probe.py: on same-sign operands six accumulations per 16 k into the running sum gave a
-        // relative bias of -4.3e-7 at K = 1 536 and -2.1e-6 at K = 61 440, where the fp32 MFMA has 4e-10). TMPACC (build-time
-        // option TWOG_X3_TMPACC=1; NOT the default: with four register stages the kernel sits at its 128-VGPR budget and the
-        // 16-register temporary spills 360-570 bytes per lane into scratch -- profiles/HISTORY.md section 8):
+        // relative bias of -4.3e-7 at K = 1 536 and -2.1e-6 at K = 61 440, where the fp32 MFMA has 4e-10). TTMP (the
+        // split-accumulator kernels; at two workgroups per CU the kernel sits at its 128-VGPR budget and the 16-register
+        // temporary would spill 360-570 bytes per lane into scratch -- profiles/HISTORY.md section 8):
         // the products of one k-step are chained through a FRESH accumulator (C = 0: its roundings are relative to one
         // k-step's partial sum) and that partial sum is added to the running sum by 16 fp32 VALU adds per block (round to
         // nearest even, unbiased); the B fragments of a block are read right before its chain, so the temporary takes the
-        // registers the second block's fragments held. Default (0): all products into the running sum (round 3's form).
+        // registers the second block's fragments held. Default: all products into the running sum (round 3's form).
         constexpr int PI[8] = {2, 1, 2, 0, 1, 1, 0, 0}, PJ[8] = {1, 2, 0, 2, 1, 0, 1, 0};
         constexpr int FIRST = 8 - X3_PRODUCTS;
         static_assert(X3_PRODUCTS == 8 || X3_PRODUCTS == 6, "l m and m l are the two optional products");
         bf16x8 af[3];
 #pragma unroll
         for (int p = 0; p < 3; ++p) af[p] = AKM ? frag_t(base + p * PA, tchA) : frag_r(base + p * PA, fa_r);
-        if constexpr (TMP) {
+        if constexpr (TTMP) {
 #pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            bf16x8 bf[3];
+            for (int b = 0; b < 2; ++b) {
+                bf16x8 bf[3];
 #pragma unroll
-            for (int p = 0; p < 3; ++p)
-                bf[p] = BKM ? frag_t(base + 3 * PA + p * PB, tchB + 4 * b) : frag_r(base + p * PB, fb_r + b * 32 * X3_RROW);
-            f32x16 t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PI[FIRST]], bf[PJ[FIRST]], f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                for (int p = 0; p < 3; ++p)
+                    bf[p] = BKM ? frag_t(base + 3 * PA + p * PB, tchB + 4 * b) : frag_r(base + p * PB, fb_r + b * 32 * X3_RROW);
+                f32x16 t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PI[FIRST]], bf[PJ[FIRST]], f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
 #pragma unroll
-            for (int q = FIRST + 1; q < 8; ++q) t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PI[q]], bf[PJ[q]], t, 0, 0, 0);
+                for (int q = FIRST + 1; q < 8; ++q) t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PI[q]], bf[PJ[q]], t, 0, 0, 0);
 #pragma unroll
-            for (int i = 0; i < 16; ++i) acc[0][b][i] += t[i];
-            __builtin_amdgcn_sched_barrier(0);   // one temporary: the compiler must not run the two blocks' chains side by side
-        }
+                for (int i = 0; i < 16; ++i) acc[0][b][i] += t[i];
+                __builtin_amdgcn_sched_barrier(0);   // one temporary: the compiler must not run the two blocks' chains side by side
+            }
         } else {
-        bf16x8 bf[2][3];
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int p = 0; p < 3; ++p)
-                bf[b][p] = BKM ? frag_t(base + 3 * PA + p * PB, tchB + 4 * b) : frag_r(base + p * PB, fb_r + b * 32 * X3_RROW);
-#pragma unroll
-        for (int t = FIRST; t < 8; ++t)
+            bf16x8 bf[2][3];
 #pragma unroll
             for (int b = 0; b < 2; ++b)
-                acc[0][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PI[t]], bf[b][PJ[t]], acc[0][b], 0, 0, 0);
+#pragma unroll
+                for (int p = 0; p < 3; ++p)
+                    bf[b][p] = BKM ? frag_t(base + 3 * PA + p * PB, tchB + 4 * b) : frag_r(base + p * PB, fb_r + b * 32 * X3_RROW);
+#pragma unroll
+            for (int t = FIRST; t < 8; ++t)
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+                    acc[0][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PI[t]], bf[b][PJ[t]], acc[0][b], 0, 0, 0);
         }
-      }
     };
     // Four register stages and two LDS stages, one barrier per k-tile: the loads of k-tile t + 4 are issued before the MFMAs
     // of tile t (a k-tile of 16 lasts under two microseconds at this matrix rate: two stages do not cover a miss to HBM);
@@ -669,79 +629,8 @@ __device__ __forceinline__ void gemm_mainloop_x3(const twog_rows_t A, const twog
     // of the split issues between the MFMAs). Loads past the last k-tile are clamped to it instead of branched around (see
     // gemm_mainloop); the redundant tiles are stored but never read.
     if (nkt <= 0) return;
-    const int k_last = k_begin + (nkt - 1) * XK * KU;
-    auto kof = [&](int t) { return min(k_begin + t * XK * KU, k_last); };
-    if constexpr (PIPE) {
-        static_assert(!PIPE || (KU == 1 && KS == 1 && !TMP), "PIPE: one k-tile per interval, one k-group, products into the running sum");
-        constexpr int PI[8] = {2, 1, 2, 0, 1, 1, 0, 0}, PJ[8] = {1, 2, 0, 2, 1, 0, 1, 0};
-        constexpr int FIRST = 8 - X3_PRODUCTS;
-        auto frags = [&](int buf, bf16x8 (&af)[3], bf16x8 (&bf)[2][3]) {
-            const char* base = lds + buf * X3_STAGE;
-#pragma unroll
-            for (int p = 0; p < 3; ++p) af[p] = AKM ? frag_t(base + p * PA, tchA) : frag_r(base + p * PA, fa_r);
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int p = 0; p < 3; ++p)
-                    bf[b][p] = BKM ? frag_t(base + 3 * PA + p * PB, tchB + 4 * b) : frag_r(base + p * PB, fb_r + b * 32 * X3_RROW);
-        };
-        auto mfmas = [&](const bf16x8 (&af)[3], const bf16x8 (&bf)[2][3]) {
-#pragma unroll
-            for (int t = FIRST; t < 8; ++t)
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-                    acc[0][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PI[t]], bf[b][PJ[t]], acc[0][b], 0, 0, 0);
-        };
-        Stage r0, r1, r2, r3;
-        gload(r0, kof(0));
-        gload(r1, kof(1));
-        gload(r2, kof(2));
-        gload(r3, kof(3));
-        split_store(r0, 0, 0);
-        __syncthreads();
-        bf16x8 fa0[3], fb0[2][3], fa1[3], fb1[2][3];
-        frags(0, fa0, fb0);
-        split_store(r1, 1, 1);
-        gload(r0, kof(4));
-        gload(r1, kof(5));
-        __syncthreads();
-        // iteration t: fragment set "cur" holds tile t, LDS stage s1 tile t + 1; tile t + 2 goes from its registers into stage s2
-        int s1 = 1, s2 = 2;
-        auto rot = [&]() { s1 = s2; s2 = s2 == 2 ? 0 : s2 + 1; };
-        int kt = 0;
-        for (; kt + 3 < nkt; kt += 4) {
-            frags(s1, fa1, fb1); mfmas(fa0, fb0); split_store(r2, s2, kt + 2); gload(r2, kof(kt + 6)); __syncthreads(); rot();
-            frags(s1, fa0, fb0); mfmas(fa1, fb1); split_store(r3, s2, kt + 3); gload(r3, kof(kt + 7)); __syncthreads(); rot();
-            frags(s1, fa1, fb1); mfmas(fa0, fb0); split_store(r0, s2, kt + 4); gload(r0, kof(kt + 8)); __syncthreads(); rot();
-            frags(s1, fa0, fb0); mfmas(fa1, fb1); split_store(r1, s2, kt + 5); gload(r1, kof(kt + 9)); __syncthreads(); rot();
-        }
-        // up to three k-tiles left: set 0 holds tile kt, stage s1 tile kt + 1, r2 tile kt + 2
-        if (kt < nkt) {
-            if (kt + 1 < nkt) frags(s1, fa1, fb1);
-            mfmas(fa0, fb0);
-            if (kt + 2 < nkt) { split_store(r2, s2, kt + 2); __syncthreads(); }
-        }
-        if (kt + 1 < nkt) {
-            if (kt + 2 < nkt) frags(s2, fa0, fb0);
-            mfmas(fa1, fb1);
-        }
-        if (kt + 2 < nkt) mfmas(fa0, fb0);
-        return;
-    }
-#if TWOG_X3_TMPACC
-    // (TMPACC: two register stages -- the temporary accumulator takes the registers of the other two)
-    Stage r0, r1;
-    gload(r0, kof(0));
-    gload(r1, kof(1));
-    split_store(r0, 0, 0);
-    __syncthreads();
-    int kt = 0;
-    for (; kt + 1 < nkt; kt += 2) {
-        gload(r0, kof(kt + 2)); compute(0); split_store(r1, 1, kt + 1); __syncthreads();
-        gload(r1, kof(kt + 3)); compute(1); split_store(r0, 0, kt + 2); __syncthreads();
-    }
-    if (kt < nkt) compute(0);
-#else
+    const int k_last = k_begin + (nkt - 1) * XK;
+    auto kof = [&](int t) { return min(k_begin + t * XK, k_last); };
     Stage r0, r1, r2, r3;
     gload(r0, kof(0));
     gload(r1, kof(1));
@@ -760,7 +649,6 @@ __device__ __forceinline__ void gemm_mainloop_x3(const twog_rows_t A, const twog
     if (kt < nkt) compute(0);
     if (kt + 1 < nkt) { split_store(r1, 1, kt + 1); __syncthreads(); compute(1); }
     if (kt + 2 < nkt) { split_store(r2, 0, kt + 2); __syncthreads(); compute(0); }
-#endif
 }
 
 // X3 for the 64-row tile class (the recurrent chains at a real batch: 160 ... 960 tiles of K = 512 ... 1 536, MFMA-bound
@@ -772,17 +660,7 @@ __device__ __forceinline__ void gemm_mainloop_x3(const twog_rows_t A, const twog
 // rows whose 16-byte chunks are XOR-swizzled by the row (conflict-free ds_read_b128 for the hardware's lane groups and
 // conflict-free ds_write_b64); the k-major operand [k][64 rows] in 128-byte rows, chunks swizzled by the k row, read
 // through ds_read_b64_tr_b16.
-#ifndef TWOG_X3S_RS
-#define TWOG_X3S_RS 4
-#endif
-// cache policy of the chain kernels' operand loads (the aux field of buffer_load: 0 default, 2 = nt: streamed, evicted first).
-// A of a chain launch is read once per launch (previous states / gradients), B is the weight every step comes back to.
-#ifndef TWOG_X3S_A_AUX
-#define TWOG_X3S_A_AUX 0
-#endif
-#ifndef TWOG_X3S_B_AUX
-#define TWOG_X3S_B_AUX 0
-#endif
+constexpr int X3S_RS = 4;   // register stages of the 64x64 class's plain kernels (see the ring in gemm_mainloop_x3s)
 // Diagnostic build only (-DTWOG_STAMPS, tools/stamps_probe.sh): cycle stamps at the phase boundaries of the X3 chain loop,
 // summed per wave of workgroup 0 and written to a buffer of their own at the end (cdna_hip_programming.md, In-kernel stamps).
 #ifdef TWOG_STAMPS
@@ -856,9 +734,9 @@ __device__ __forceinline__ void gemm_mainloop_x3s(const twog_rows_t A, const two
             const int sa = (int)((uint32_t)(k0 + u * XK) * 4u);
             const int sb = (int)(BKM ? (uint32_t)(k0 + u * XK) * (uint32_t)B.ld_outer * 4u : (uint32_t)(k0 + u * XK) * 4u);
 #pragma unroll
-            for (int i = 0; i < NPA; ++i) r.a[u][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, (int)oa[i], sa, TWOG_X3S_A_AUX));
+            for (int i = 0; i < NPA; ++i) r.a[u][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, (int)oa[i], sa, 0));
 #pragma unroll
-            for (int i = 0; i < NPB; ++i) r.b[u][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, (int)ob[i], sb, TWOG_X3S_B_AUX));
+            for (int i = 0; i < NPB; ++i) r.b[u][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, (int)ob[i], sb, 0));
         }
     };
     auto split_store = [&](const Stage& r, int buf) {
@@ -878,13 +756,7 @@ __device__ __forceinline__ void gemm_mainloop_x3s(const twog_rows_t A, const two
 #pragma unroll
             for (int i = 0; i < NPB; ++i) {
                 if (NPB * NT == FB || b_on[i]) {
-#ifdef TWOG_PROBE_NO_BSPLIT   // timing probe only (wrong results): what the split of the B operand costs a chain launch
-                    ph = i32x2{__builtin_bit_cast(int, r.b[u][i][0]), __builtin_bit_cast(int, r.b[u][i][1])};
-                    pm = i32x2{__builtin_bit_cast(int, r.b[u][i][2]), __builtin_bit_cast(int, r.b[u][i][3])};
-                    pl = ph;
-#else
                     split3(r.b[u][i], ph, pm, pl);
-#endif
                     *reinterpret_cast<i32x2*>(base + sb_off[i]) = ph;
                     *reinterpret_cast<i32x2*>(base + sb_off[i] + PB) = pm;
                     *reinterpret_cast<i32x2*>(base + sb_off[i] + 2 * PB) = pl;
@@ -1004,7 +876,7 @@ __device__ __forceinline__ void gemm_mainloop_x3s(const twog_rows_t A, const two
 // counters are zero again at the launch boundary (graph replays need no memset node). The hand-off form is the
 // guide's split-K recipe (cdna_hip_programming.md section 5 item 2 / MI355X_MICROARCH.md "Valid forms": sc1 payload,
 // every storing wave drained, workgroup barrier, one relaxed agent atomic; the last arriver's loads all sc1).
-template <int BM, int BN, int NT, bool AKM, bool BKM, int D, bool KG, bool GATE, int KS = 1, bool XS = false, bool X3 = false, int KU = 1, bool TTMP = false, bool PIPE = false>
+template <int BM, int BN, int NT, bool AKM, bool BKM, int D, bool KG, bool GATE, int KS = 1, bool XS = false, bool X3 = false, int KU = 1, bool TTMP = false>
 __device__ __forceinline__ void gemm_tile(const Group& g, const GateArgs* ga) {
     constexpr int NTG = NT / KS;
     constexpr int WM = BM / (NTG / 128), WN = BN / 2;  // per-wave tile; the waves of a k-group in a (NTG/128) x 2 grid
@@ -1015,7 +887,7 @@ __device__ __forceinline__ void gemm_tile(const Group& g, const GateArgs* ga) {
     constexpr int B_ELEMS = BKM ? BK * LDB : BN * LDB;
     // (X3 on the 64-row class: two stages of three bf16 planes per operand, 2 x 6 x 64 rows x 2 XK bytes, XK = 16 KS)
     constexpr int SMEM_FLOATS = (X3 && BM == 128 && BN == 64) ? 2 * KU * 3 * (128 + 64) * 32 / 4   // 128x64 chain tile: 2 stages x KU images
-                                : (X3 && BM == 128) ? (PIPE ? 3 : KS * 2 * KU) * X3_STAGE / 4
+                                : (X3 && BM == 128) ? 2 * X3_STAGE / 4
                                 : (X3 && BM == 64 && 12 * 64 * 8 * KS * KU > 2 * (A_ELEMS + B_ELEMS)) ? 12 * 64 * 8 * KS * KU : 2 * (A_ELEMS + B_ELEMS);
     __shared__ __attribute__((aligned(16))) float smem[SMEM_FLOATS];
 
@@ -1079,7 +951,7 @@ __device__ __forceinline__ void gemm_tile(const Group& g, const GateArgs* ga) {
     const int lane = threadIdx.x & 63, wave = (threadIdx.x >> 6) % (NTG / 64), kgrp = (threadIdx.x >> 6) / (NTG / 64);
     const int li = lane & 31, kh = lane >> 5;
     const int wm = (wave >> 1) * WM, wn = (wave & 1) * WN;
-    static_assert(KS == 1 || (KS == 2 && (TM * TN == 1 || (X3 && BM == 128 && BN == 128))), "the in-workgroup k-split: the 64x64 class and the X3 128x128 tile");
+    static_assert(KS == 1 || (KS == 2 && TM * TN == 1), "the in-workgroup k-split: the 64x64 class");
 
     f32x16 acc[TM][TN];
 #pragma unroll
@@ -1094,9 +966,10 @@ __device__ __forceinline__ void gemm_tile(const Group& g, const GateArgs* ga) {
     // 64x64 class, the previous C values of accumulate launches. XS kernels fetch them only in the workgroup that
     // combines the slices (next to its slab loads), not in every slice.
     constexpr bool PREFETCH_C = (TM * TN == 1);
-    // LA: the deterministic split-K of the non-chain launches (tall dW reductions) combined INSIDE the launch by the last
-    // arriver of each tile, as the XS kernels do (round 5; built, bit-identical to the two-launch form,
-    // measured slower and left OFF: see prepare_group). Tickets: g.xcnt (host: the first 16 KB of the split-K workspace).
+    // LA: the XL chain launches (xl_setup, 4-wave X3 64x64 tiles) split the reduction over workgroups and combine the slices
+    // INSIDE the launch, by the last arriver of each tile, as the XS kernels do. Tickets: g.xcnt (the chain workspace).
+    // Non-chain split-K launches leave g.xcnt null and use slabs + splitk_reduce_kernel (round 5 combined them in the
+    // launch too: bit-identical, measured slower, removed -- profiles/r05_splitk_in_launch_combine_ab.txt).
     const bool la = !XS && g.splitk > 1 && g.xcnt != nullptr;
     const bool epi_here = XS || g.splitk == 1 || la;
     float bv[TN];
@@ -1169,14 +1042,10 @@ __device__ __forceinline__ void gemm_tile(const Group& g, const GateArgs* ga) {
             static_assert(!X3 || BM != 128 || BN != 64 || (NT == 512 && KS == 1 && !AKM && !KG && !XS && !GATE), "X3: 128x64 chain tiles");
             gemm_mainloop_x3s<BM, BN, NT, BKM, 1, 1, false, 2, true, KU>(A, B, M, N, m0, n0, k_begin, k_end, smem, acc);
         } else if constexpr (BM == 128) {
-            static_assert(!X3 || BM != 128 || (BN == 128 && NT == 512 * KS && !GATE && !XS), "X3: the 8-wave (16-wave: KS = 2) 128x128 class");
+            static_assert(!X3 || BM != 128 || (BN == 128 && NT == 512 && KS == 1 && KU == 1 && !GATE && !XS), "X3: the 8-wave 128x128 class");
             f32x4 cs = {0.f, 0.f, 0.f, 0.f};
             const bool cs_on = AKM && BKM && !KG && G.cs != nullptr && tn_idx == 0;   // uniform over the workgroup
-            if constexpr (KS == 2) {   // (host: whole PAIRS of k-tiles, so both k-groups run the same number of barriers)
-                const int half = (k_end - k_begin) / 2;
-                gemm_mainloop_x3<AKM, BKM, KG, TTMP, KU, 2>(A, B, M, N, m0, n0, k_begin + kgrp * half, k_begin + (kgrp + 1) * half, smem, acc, cs, cs_on);
-            } else
-            gemm_mainloop_x3<AKM, BKM, KG, TTMP, KU, 1, PIPE>(A, B, M, N, m0, n0, k_begin, k_end, smem, acc, cs, cs_on);
+            gemm_mainloop_x3<AKM, BKM, KG, TTMP>(A, B, M, N, m0, n0, k_begin, k_end, smem, acc, cs, cs_on);
             if constexpr (AKM && BKM && !KG) {
                 if (cs_on) {
                     // thread (k row tid / 32, column quad tid % 32) holds its k rows' sums: the 16 k rows are added in row order
@@ -1197,7 +1066,7 @@ __device__ __forceinline__ void gemm_tile(const Group& g, const GateArgs* ga) {
             }
         } else {
             static_assert(!X3 || BM == 128 || (BM == 64 && BN == 64 && !AKM && !KG && !XS), "X3: 64x64 tiles, row-major A");
-            gemm_mainloop_x3s<BM, BN, NT, BKM, KS, 1, false, (GATE || KU > 1 ? 2 : TWOG_X3S_RS), true, KU>(A, B, M, N, m0, n0, k_begin, k_end, smem, acc);
+            gemm_mainloop_x3s<BM, BN, NT, BKM, KS, 1, false, (GATE || KU > 1 ? 2 : X3S_RS), true, KU>(A, B, M, N, m0, n0, k_begin, k_end, smem, acc);
         }
     } else if (fast)
         gemm_mainloop<BM, BN, NT, AKM, BKM, true, TM, TN, D, KG, KS>(A, B, M, N, a_vec, b_vec, m0, n0, k_begin, k_end, smem, acc);
@@ -1440,63 +1309,35 @@ template <bool AKM, bool BKM, bool KG>
 __global__ __launch_bounds__(512, 4) void gemm_x3_kernel(const Group g) {   // 4 waves per SIMD = two workgroups per CU: <= 128 VGPRs
     gemm_tile<128, 128, 512, AKM, BKM, 2, KG, false, 1, false, true>(g, nullptr);
 }
-// forward (row-major) form with two k-tiles per barrier interval: one workgroup per CU (launches of at most one tile per CU)
-__global__ __launch_bounds__(512, 2) void gemm_x3_nn_ku2_kernel(const Group g) {
-    gemm_tile<128, 128, 512, false, false, 2, false, false, 1, false, true, 2>(g, nullptr);
-}
 // dW = dY^T X with every k-step's products through a fresh accumulator (TTMP): one workgroup per CU
-// fragment reads one k-tile ahead of the MFMAs (PIPE): one workgroup per CU
-template <bool AKM, bool BKM, bool KG>
-__global__ __launch_bounds__(512, 1) void gemm_x3_pipe_kernel(const Group g) {
-    gemm_tile<128, 128, 512, AKM, BKM, 2, KG, false, 1, false, true, 1, false, true>(g, nullptr);
-}
-// 16 waves = two k-groups on one tile (KS = 2): launches of at most one tile per CU (the segment level's per-step projection)
-__global__ __launch_bounds__(1024, 1) void gemm_x3_nn_k2_kernel(const Group g) {
-    gemm_tile<128, 128, 1024, false, false, 2, false, false, 2, false, true>(g, nullptr);
-}
 template <bool KG>
 __global__ __launch_bounds__(512, 2) void gemm_x3_tt_split_acc_kernel(const Group g) {
     gemm_tile<128, 128, 512, true, true, 2, KG, false, 1, false, true, 1, true>(g, nullptr);
 }
 
-// Issue priority of the waves of a recurrent chain's launches (s_setprio, 0-3): beside the side stream's dW GEMMs a chain
-// workgroup shares its CU with two GEMM workgroups, and the SIMD's arbiter serves equal-priority waves in turn.
-#ifndef TWOG_CHAIN_PRIO
-#define TWOG_CHAIN_PRIO 0
-#endif
-#if TWOG_CHAIN_PRIO > 0
-#define TWOG_CHAIN_SETPRIO() __builtin_amdgcn_s_setprio(TWOG_CHAIN_PRIO)
-#else
-#define TWOG_CHAIN_SETPRIO() ((void)0)
-#endif
 // X3 on the 64x64 class (gemm_mainloop_x3s): 4 waves, or 8 waves = two k-groups; plain and gate-fused epilogues
 template <bool BKM, int KS>
 __global__ __launch_bounds__(256 * KS, 2) void gemm_x3s_kernel(const Group g) {
-    TWOG_CHAIN_SETPRIO();
     gemm_tile<64, 64, 256 * KS, false, BKM, 2, false, false, KS, false, true>(g, nullptr);
 }
 template <int KS>
 __global__ __launch_bounds__(256 * KS, 2) void gemm_gate_bwd_x3s_kernel(const Group g, const GateArgs ga) {
-    TWOG_CHAIN_SETPRIO();
     gemm_tile<64, 64, 256 * KS, false, true, 2, false, true, KS, false, true>(g, &ga);
 }
 
 // 128 x 64 tiles for chain launches with enough rows (pick_rows128): one 8-wave workgroup per CU, two k-tiles per barrier
 template <bool BKM>
 __global__ __launch_bounds__(512, 1) void gemm_x3su128_kernel(const Group g) {
-    TWOG_CHAIN_SETPRIO();
     gemm_tile<128, 64, 512, false, BKM, 2, false, false, 1, false, true, 2>(g, nullptr);
 }
 
 // KU k-tiles per barrier interval (launches that run one workgroup per CU: at most 256 tiles)
 template <bool BKM, int KS, int KU>
 __global__ __launch_bounds__(256 * KS, KS == 2 ? 1 : 2) void gemm_x3su_kernel(const Group g) {
-    TWOG_CHAIN_SETPRIO();
     gemm_tile<64, 64, 256 * KS, false, BKM, 2, false, false, KS, false, true, KU>(g, nullptr);
 }
 template <int KS, int KU>
 __global__ __launch_bounds__(256 * KS, KS == 2 ? 1 : 2) void gemm_gate_bwd_x3su_kernel(const Group g, const GateArgs ga) {
-    TWOG_CHAIN_SETPRIO();
     gemm_tile<64, 64, 256 * KS, false, true, 2, false, true, KS, false, true, KU>(g, &ga);
 }
 
@@ -1540,7 +1381,6 @@ struct GruFwdGroup {
 
 template <int D, int KS, bool X3 = false>
 __global__ __launch_bounds__(256 * KS, 1) void gemm_gru_fwd_kernel(const GruFwdGroup g) {
-    TWOG_CHAIN_SETPRIO();
     constexpr int BM = 64, BN = 192, NT = 256 * KS, TM = 1, TN = 3;
     // X3 (bf16 x 3 on the bf16 matrix cores, see gemm_mainloop_x3s): two stages of three bf16 planes of both operand tiles
     __shared__ __attribute__((aligned(16))) float smem[X3 ? 2 * 3 * (BM + BN) * (16 * KS) * 2 / 4 : 2 * (BM + BN) * (BK + 4)];
@@ -1750,8 +1590,6 @@ static bool x3_128_ok(const Group& g) {
     return ok;
 }
 
-thread_local int g_dw_one_per_cu = getenv("TWOG_DW_ONE_PER_CU") ? atoi(getenv("TWOG_DW_ONE_PER_CU")) : 0;
-
 template <int BM, int BN, int NT, int D>
 int launch(Group& g, int akm, int bkm, hipStream_t st) {
     g_last_class_x3 = 0;
@@ -1763,55 +1601,18 @@ int launch(Group& g, int akm, int bkm, hipStream_t st) {
         // X3 (fp32-exact operands on the bf16 matrix cores, gemm_mainloop_x3): aligned operands, whole k-tiles, plain rows
         if (x3_128_ok(g)) {
             static const int split_acc = getenv("TWOG_X3_DW_SPLIT_ACC") ? atoi(getenv("TWOG_X3_DW_SPLIT_ACC")) : 0;
-            // at most one tile per CU, whole pairs of k-tiles, no split-K: two k-tiles per barrier interval. Built and measured
-            // in round 6 (VERDICT r05 item 7's "raise the 128x128 class"), SLOWER: the segment level's 240-tile projection launch
-            // 47.4 -> 49.8 us, the 64-clip step 65.59 -> 65.84 ms (same box, alternating twice): profiles/r06_gemm128_ku2_ab.txt.
-            // Off by default (TWOG_X3_KU128=1 selects it).
-            static const int ku128 = getenv("TWOG_X3_KU128") ? atoi(getenv("TWOG_X3_KU128")) : 0;
-            bool ku2 = ku128 != 0 && !akm && !bkm && g.splitk == 1 && g.total_tiles <= 256;
-            for (int i = 0; i < g.n; ++i) ku2 = ku2 && (g.p[i].K % (2 * X3_BK)) == 0;
-            // at most one tile per CU, whole pairs of k-tiles: 16 waves, the reduction halved between two k-groups. Built and measured
-            // in round 6 (four waves per SIMD on a lone tile, as two co-resident workgroups of a big launch have): NO gain -- the
-            // 240-tile projection launch 47.0 -> 46.3 us, the step unchanged. The sixteen waves meet at ONE barrier per k-tile, so their
-            // LDS phases (768 cycles of plane stores + fragment reads per k-tile on the CU) and their MFMA phases (768 cycles per
-            // SIMD) still alternate instead of overlapping, which is what two independent workgroups get for free.
-            // Off by default (TWOG_X3_K2=1 selects it). profiles/r06_gemm128_two_k_groups.txt
-            static const int k2_on = getenv("TWOG_X3_K2") ? atoi(getenv("TWOG_X3_K2")) : 0;
-            bool k2 = k2_on != 0 && !ku2 && !akm && !bkm && g.splitk == 1 && g.total_tiles <= 256;
-            for (int i = 0; i < g.n; ++i) k2 = k2 && (g.p[i].K % (2 * X3_BK)) == 0 && g.p[i].K >= 8 * X3_BK;
-            // fragment reads one k-tile ahead (PIPE, one workgroup per CU): TWOG_X3_PIPE bit 0 = the forward-form launches of at
-            // most one tile per CU, bit 1 = every forward-form launch, bit 2 = the dX / dW forms too. Built and measured in round 6,
-            // bit-identical and SLOWER: the 240-tile projection launch +3 us, the big launches with one pipelined workgroup per CU
-            // lose to two unpipelined ones (roofline.frac 0.430 -> 0.398 forward forms, 0.347 all forms). Off by default.
-            // profiles/r06_gemm128_fragment_reads_ahead.txt
-            static const int pipe_on = getenv("TWOG_X3_PIPE") ? atoi(getenv("TWOG_X3_PIPE")) : 0;
-            const bool one_per_cu = g.splitk == 1 && g.total_tiles <= 256;
-            const bool pipe_nn = !akm && !bkm && (((pipe_on & 1) && one_per_cu) || (pipe_on & 2));
-            if (pipe_nn) hipLaunchKernelGGL((gemm_x3_pipe_kernel<false, false, false>), grid, block, 0, st, g);
-            else if ((pipe_on & 4) && !akm && bkm && !kg) hipLaunchKernelGGL((gemm_x3_pipe_kernel<false, true, false>), grid, block, 0, st, g);
-            else if ((pipe_on & 4) && akm && bkm && !kg && !split_acc) hipLaunchKernelGGL((gemm_x3_pipe_kernel<true, true, false>), grid, block, 0, st, g);
-            else if (k2) hipLaunchKernelGGL(gemm_x3_nn_k2_kernel, grid, dim3(1024), 0, st, g);
-            else if (ku2) hipLaunchKernelGGL(gemm_x3_nn_ku2_kernel, grid, block, 0, st, g);
-            else if (!akm && !bkm) hipLaunchKernelGGL((gemm_x3_kernel<false, false, false>), grid, block, 0, st, g);
+            if (!akm && !bkm) hipLaunchKernelGGL((gemm_x3_kernel<false, false, false>), grid, block, 0, st, g);
             else if (!akm && bkm && !kg) hipLaunchKernelGGL((gemm_x3_kernel<false, true, false>), grid, block, 0, st, g);
             else if (!akm && bkm) hipLaunchKernelGGL((gemm_x3_kernel<false, true, true>), grid, block, 0, st, g);
             else if (akm && bkm && split_acc && !kg) hipLaunchKernelGGL((gemm_x3_tt_split_acc_kernel<false>), grid, block, 0, st, g);
             else if (akm && bkm && split_acc) hipLaunchKernelGGL((gemm_x3_tt_split_acc_kernel<true>), grid, block, 0, st, g);
-            else if (akm && bkm && g_dw_one_per_cu) {
-                // (experiment, round 6: the dW launches of a side stream with ONE workgroup per CU -- 40 KB of unused dynamic LDS
-                // on top of the 48 KB of stages -- so that half of every CU's registers stay free for a 4-wave chain workgroup;
-                // twog_gemm_dw_one_per_cu(1) / TWOG_DW_ONE_PER_CU=1; profiles/r06_dw_one_workgroup_per_cu.txt)
-                static std::atomic<uint32_t> a0{0}, a1{0};
-                if (!kg) { twog_allow_dynamic_lds(gemm_x3_kernel<true, true, false>, 40 * 1024, a0); hipLaunchKernelGGL((gemm_x3_kernel<true, true, false>), grid, block, 40 * 1024, st, g); }
-                else { twog_allow_dynamic_lds(gemm_x3_kernel<true, true, true>, 40 * 1024, a1); hipLaunchKernelGGL((gemm_x3_kernel<true, true, true>), grid, block, 40 * 1024, st, g); }
-            }
             else if (akm && bkm && !kg) hipLaunchKernelGGL((gemm_x3_kernel<true, true, false>), grid, block, 0, st, g);
             else if (akm && bkm) hipLaunchKernelGGL((gemm_x3_kernel<true, true, true>), grid, block, 0, st, g);
             else if (!kg) hipLaunchKernelGGL((gemm_x3_kernel<true, false, false>), grid, block, 0, st, g);
             else hipLaunchKernelGGL((gemm_x3_kernel<true, false, true>), grid, block, 0, st, g);
             TWOG_CHECK_LAUNCH();
             g_last_class_x3 = 1;
-            if (g.splitk > 1 && !g.xcnt) {
+            if (g.splitk > 1) {
                 hipLaunchKernelGGL((splitk_reduce_kernel<BM, BN>), dim3(g.total_tiles, (BM * BN) / 1024), dim3(256), 0, st, g);
                 TWOG_CHECK_LAUNCH();
             }
@@ -1829,7 +1630,7 @@ int launch(Group& g, int akm, int bkm, hipStream_t st) {
     else if (!kg) hipLaunchKernelGGL((gemm_kernel<BM, BN, NT, true, false, D, false>), grid, block, 0, st, g);
     else hipLaunchKernelGGL((gemm_kernel<BM, BN, NT, true, false, D, true>), grid, block, 0, st, g);
     TWOG_CHECK_LAUNCH();
-    if (g.splitk > 1 && !g.xcnt) {
+    if (g.splitk > 1) {
         hipLaunchKernelGGL((splitk_reduce_kernel<BM, BN>), dim3(g.total_tiles, (BM * BN) / 1024), dim3(256), 0, st, g);
         TWOG_CHECK_LAUNCH();
     }
@@ -1844,7 +1645,7 @@ extern "C" int twog_gemm_last_class(void) { return g_last_class; }
 
 // Builds the launch descriptor of one chunk (<= MAXP problems): tile class, class-sorted problem list (order[i] = index of
 // the caller's problem that became sorted problem i), XCD map, split-K. Shared by the plain and the gate-fused launch.
-constexpr size_t SPLITK_TICKET_BYTES = 16384;   // 4096 tickets at the start of the split-K workspace (see prepare_group)
+constexpr size_t SPLITK_TICKET_BYTES = 16384;   // reserved at the start of the split-K workspace (see prepare_group)
 
 static void prepare_group(const twog_gemm_t* pr, int n, int a_kmajor, int b_kmajor, void* workspace,
                           size_t workspace_bytes, Group& g, int* order, bool& big, int& bm) {
@@ -1966,22 +1767,9 @@ static void prepare_group(const twog_gemm_t* pr, int n, int a_kmajor, int b_kmaj
             if (want8 && best8 + 0.08 < best) want8 = 0;   // (48 tiles x 8 splits of 1 920 at K = 15 360: 0.150 against 0.138 ms)
         }
         if (want8) want = want8;
-        // (experiment, round 6: SHORT workgroups for the tall dW reductions -- TWOG_GEMM_SLAB_K=k asks for splits of about k
-        // reduction rows, a multiple of 8, as many as the workspace holds -- so that a launch chain on another stream finds
-        // free compute units sooner; profiles/r06_dw_short_slabs_beside_the_chain.txt. Off by default.)
-        static const int slab_k = getenv("TWOG_GEMM_SLAB_K") ? atoi(getenv("TWOG_GEMM_SLAB_K")) : 0;
-        if (slab_k > 0 && big && a_kmajor && b_kmajor && force_split <= 0 && t <= 512 && kmax >= 4 * slab_k) {
-            int s8 = ((kmax / slab_k + 7) / 8) * 8;
-            while (s8 > want && (size_t)s8 * t * BMN * BMN * sizeof(float) + SPLITK_TICKET_BYTES + (size_t)(s8 + 1) * t * 128 * sizeof(float) > workspace_bytes) s8 -= 8;
-            if (s8 > want) want = s8;
-        }
-        // the first 16 KB of the workspace are the arrival tickets of the in-launch combine (LA, gemm_tile): zero when the
-        // workspace is first handed over, returned to zero by every launch. OFF by default -- measured on one box, same
-        // session: bs64 step 69.32 ms with it against 68.57 ms with slabs + splitk_reduce_kernel, 8-clip step 16.32 against
-        // 16.28 (profiles/r05_splitk_in_launch_combine_ab.txt): the one workgroup per tile that arrives last re-reads S slabs
-        // of 64 KB alone, where the reduce launch spreads the same bytes over 16 workgroups per tile at 5 TB/s; what the
-        // launch boundary costs is less than that. TWOG_GEMM_LA=1 selects it (tests run both).
-        static const int la_on = getenv("TWOG_GEMM_LA") ? atoi(getenv("TWOG_GEMM_LA")) : 0;
+        // the first 16 KB of the workspace are reserved (they held the arrival tickets of round 5's in-launch combine of the
+        // slices, measured slower than slabs + splitk_reduce_kernel and removed: profiles/r05_splitk_in_launch_combine_ab.txt);
+        // the slabs start behind them, and they count in `need`, so the split choice is unchanged
         bool any_cs = false;
         for (int i = 0; i < n; ++i) any_cs = any_cs || pr[i].a_colsum != nullptr;
         const size_t cs_bytes = any_cs ? (size_t)(want + 1) * t * 128 * sizeof(float) : 0;   // (+1: the split count is rounded below)
@@ -1992,8 +1780,6 @@ static void prepare_group(const twog_gemm_t* pr, int n, int a_kmajor, int b_kmaj
             g.splitk = (kmax + g.k_per_split - 1) / g.k_per_split;
             g.slabs = reinterpret_cast<float*>(static_cast<char*>(workspace) + SPLITK_TICKET_BYTES);
             g.xcd_split = (want8 && g.splitk % 8 == 0) ? 1 : 0;
-            const bool fits32 = (uint64_t)g.splitk * t * BMN * BMN * sizeof(float) < (uint64_t(1) << 32);
-            if (la_on && !any_cs && bm == BMN && t <= (int)(SPLITK_TICKET_BYTES / sizeof(unsigned)) && fits32) g.xcnt = static_cast<unsigned*>(workspace);
             if (any_cs) g.cs_part = g.slabs + (size_t)g.splitk * t * BMN * BMN;
         }
     }

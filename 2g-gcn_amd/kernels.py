@@ -199,8 +199,8 @@ class HipKernels:
         if buf is None or buf.numel() * 4 < nbytes:
             buf = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
             if key == 'splitk':
-                # the first 16 KB of the split-K workspace are the arrival tickets of the in-launch combine (include/twog_gcn.h,
-                # twog_gemm_f32): zero when first handed over, returned to zero by every launch
+                # the first 16 KB of the split-K workspace are reserved and handed over zeroed, as twog_gemm_f32 asks
+                # (include/twog_gcn.h); the slabs start behind them
                 self.fill_zero(buf[:4096])
             self._ws_put(k, buf)
         else:

@@ -212,27 +212,6 @@ torch.save(out, sys.argv[2])
 """
 
 
-def test_gemm_split_k_in_launch_combine_equals_the_reduce_launch_bit_for_bit(K, tmp_path):
-    """TWOG_GEMM_LA=1 (the k-slices of a tile combined inside the launch by the slice that arrives last; off by default:
-    measured slower, profiles/r05_splitk_in_launch_combine_ab.txt) against the default slabs + ordered-reduce launch: both add
-    the slices in slice order, so every output word must be equal -- tall dW reductions (8-wave X3 class, XCD-dealt splits),
-    a dX shape, a small-output shape of the 64x64 class; every case twice (the tickets return to zero)."""
-    res = {}
-    for la in ('0', '1'):
-        f = tmp_path / f'la{la}.pt'
-        env = dict(os.environ, TWOG_GEMM_LA=la)
-        r = subprocess.run([sys.executable, '-c', _LA_CHILD, ROOT, str(f)], env=env, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        res[la] = torch.load(f)
-    split_seen = False
-    for k in res['0']:
-        (a, ca), (b, cb) = res['0'][k], res['1'][k]
-        assert ca == cb, (k, hex(ca), hex(cb))
-        split_seen = split_seen or bool(ca & K.GEMM_SPLITK)
-        assert torch.isfinite(b).all() and torch.equal(a, b), f'{k}: in-launch combine differs from the reduce launch'
-    assert split_seen, 'no case took the split-K path'
-
-
 _KU_CHILD = """
 import sys, torch
 sys.path.insert(0, sys.argv[1])
@@ -243,76 +222,41 @@ out = {}
 for (M, N, Kd, seed) in ((1280, 1536, 1024, 1), (512, 1536, 512, 2), (2000, 1000, 96, 3), (128, 128, 32, 4), (640, 384, 112, 5), (256, 256, 16, 6), (384, 512, 208, 7)):
     g = torch.Generator().manual_seed(500 + seed)
     A, B, bias = torch.randn(M, Kd, generator=g).cuda(), torch.randn(N, Kd, generator=g).cuda(), torch.randn(N, generator=g).cuda()
-    C = torch.empty(M, N, device='cuda')
-    K.gemm([dict(A=A, B=B, C=C, bias=bias, act=1)], split_k_workspace=False)
     ref = torch.relu(A.double() @ B.double().t() + bias.double())
-    out[(M, N, Kd)] = (C.cpu(), K.gemm_last_class(), float((C.double() - ref).abs().max() / ref.abs().max()))
+    for rep in range(2):
+        C = torch.empty(M, N, device='cuda')
+        K.gemm([dict(A=A, B=B, C=C, bias=bias, act=1)], split_k_workspace=False)
+        out[(M, N, Kd, rep)] = (C.cpu(), K.gemm_last_class(), float((C.double() - ref).abs().max() / ref.abs().max()))
 torch.save(out, sys.argv[2])
 """
 
 
-def test_gemm_x3_128_class_two_k_tiles_per_barrier_option_is_bit_identical(K, tmp_path):
-    """TWOG_X3_KU128=1 (round 6, off by default: measured slower, profiles/r06_gemm128_ku2_ab.txt): forward-form launches of the
-    bf16x3 128x128 class with at most one tile per CU run gemm_x3_nn_ku2_kernel -- two k-tiles per barrier interval, the same MFMA
-    sequence into the same accumulators. Every output word must equal the default kernel's, with bias + ReLU epilogue, a ragged
-    problem, a K that is not a multiple of 32 (falls back to the default kernel) and a single k-pair."""
+def test_gemm_128_class_default_launches_are_exact_and_reproducible(K, tmp_path):
+    """Default settings, in child processes (the tile policy is read once per process). The forward-form shapes of _KU_CHILD
+    forced onto the 128x128 tile (TWOG_GEMM_TILE=128: bias + ReLU epilogue, a ragged problem, reductions from one k-tile to
+    64, K not a multiple of 32) run the bf16x3 class within 2e-6 of fp64. The tall dW reductions, the dX shape and the
+    small-output shape of _LA_CHILD take the split-K path (slabs + ordered reduce launch) and are finite. Every case is
+    launched twice, and the two launches give the same words."""
     res = {}
-    for ku in ('0', '1'):
-        f = tmp_path / f'ku{ku}.pt'
-        r = subprocess.run([sys.executable, '-c', _KU_CHILD, ROOT, str(f)], env=dict(os.environ, TWOG_X3_KU128=ku, TWOG_X3_K2='0', TWOG_X3_PIPE='0', TWOG_GEMM_TILE='128'),
-                           capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        res[ku] = torch.load(f)
-    for k in res['0']:
-        (a, ca, ea), (b, cb, eb) = res['0'][k], res['1'][k]
-        assert ca & K.GEMM_TILE128 and ca & K.GEMM_X3, (k, hex(ca))
-        assert ea < 2e-6 and eb < 2e-6, (k, ea, eb)
-        assert torch.equal(a, b), f'{k}: two k-tiles per barrier interval changed the result'
-
-
-def test_gemm_x3_128_class_sixteen_wave_tile_for_launches_of_one_tile_per_cu(K, tmp_path):
-    """Round 6, TWOG_X3_K2=1 (off by default: measured no faster, profiles/r06_gemm128_two_k_groups.txt): forward-form launches
-    of the bf16x3 128x128 class with at most one tile per CU (the segment level's per-step projection: 240 tiles) run
-    gemm_x3_nn_k2_kernel -- 16 waves, the reduction halved between two k-groups of eight, the two partial tiles added in fixed
-    order. Same products, one more fp32 addition per element: against
-    fp64 both stay inside the class's 2e-6, they differ from each other by rounding only, and two runs agree bit for bit. A K
-    that is not a whole pair of k-tiles, or shorter than eight k-tiles, keeps the 8-wave kernel (identical words)."""
-    res = {}
-    for tag, k2 in (('off', '0'), ('on', '1'), ('again', '1')):
-        f = tmp_path / f'k2{tag}.pt'
-        r = subprocess.run([sys.executable, '-c', _KU_CHILD, ROOT, str(f)], env=dict(os.environ, TWOG_X3_K2=k2, TWOG_X3_PIPE='0', TWOG_GEMM_TILE='128'),
-                           capture_output=True, text=True, timeout=600)
+    for tag, child, env in (('la', _LA_CHILD, dict(os.environ)), ('ku', _KU_CHILD, dict(os.environ, TWOG_GEMM_TILE='128'))):
+        f = tmp_path / f'{tag}.pt'
+        r = subprocess.run([sys.executable, '-c', child, ROOT, str(f)], env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         res[tag] = torch.load(f)
-    for k in res['off']:
-        (a, ca, ea), (b, cb, eb), (c, _, _) = res['off'][k], res['on'][k], res['again'][k]
-        assert ca & K.GEMM_TILE128 and ca & K.GEMM_X3 and cb == ca, (k, hex(ca), hex(cb))
-        assert ea < 2e-6 and eb < 2e-6, (k, ea, eb)
-        assert torch.equal(b, c), f'{k}: two runs of the 16-wave tile differ'
-        if k[2] % 32 or k[2] < 128 or k[0] * k[1] > 256 * 128 * 128:
-            assert torch.equal(a, b), k
-        else:
-            assert not torch.equal(a, b), f'{k}: the 16-wave kernel did not run'
-            assert ((a - b).abs().max() / a.abs().max()).item() < 3e-6, k
-
-
-def test_gemm_x3_128_class_fragment_reads_one_k_tile_ahead_is_bit_identical(K, tmp_path):
-    """Round 6: gemm_x3_pipe_kernel reads the fragments of k-tile t + 1 before it multiplies k-tile t (two fragment sets, three
-    LDS stages, one workgroup per CU) -- the same MFMA sequence into the same accumulators as gemm_x3_kernel. Every output word
-    must equal the unpipelined kernel's (TWOG_X3_PIPE=0), with bias + ReLU epilogue, a ragged problem, reductions of 6, 2 and 64
-    k-tiles (main loop + every remainder length)."""
-    res = {}
-    for pipe in ('0', '3'):
-        f = tmp_path / f'pipe{pipe}.pt'
-        r = subprocess.run([sys.executable, '-c', _KU_CHILD, ROOT, str(f)], env=dict(os.environ, TWOG_X3_PIPE=pipe, TWOG_X3_K2='0', TWOG_GEMM_TILE='128'),
-                           capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        res[pipe] = torch.load(f)
-    for k in res['0']:
-        (a, ca, ea), (b, cb, eb) = res['0'][k], res['3'][k]
-        assert ca & K.GEMM_TILE128 and ca & K.GEMM_X3, (k, hex(ca))
-        assert ea < 2e-6 and eb < 2e-6, (k, ea, eb)
-        assert torch.equal(a, b), f'{k}: reading the fragments one k-tile ahead changed the result'
+    split_seen = False
+    for k in ('tt', 'tt2', 'nt', 'small'):
+        (a, ca), (b, cb) = res['la'][f'{k}0'], res['la'][f'{k}1']
+        assert ca == cb, (k, hex(ca), hex(cb))
+        split_seen = split_seen or bool(ca & K.GEMM_SPLITK)
+        assert torch.isfinite(a).all() and torch.equal(a, b), f'{k}: two launches differ'
+    assert split_seen, 'no case took the split-K path'
+    for (M, N, Kd, rep), (a, ca, ea) in res['ku'].items():
+        if rep:
+            continue
+        b, cb, eb = res['ku'][(M, N, Kd, 1)]
+        assert ca & K.GEMM_TILE128 and ca & K.GEMM_X3 and cb == ca, ((M, N, Kd), hex(ca), hex(cb))
+        assert ea < 2e-6 and eb < 2e-6, ((M, N, Kd), ea, eb)
+        assert torch.equal(a, b), f'{(M, N, Kd)}: two launches differ'
 
 
 def test_gemm_column_sums_of_a_from_the_same_pass(K):
@@ -1885,7 +1829,8 @@ def test_gemm_x3_same_sign_and_wide_exponent_operands():
     to nearest (bias 4e-10 on the same data). The 64x64 class keeps the five small products in a second accumulator (one
     accumulation into the main one per 16 k: -4e-8 at K = 1 536); the 128x128 class has no registers for that at two
     workgroups per CU and adds all six into the running sum (-4.3e-7 at K = 1 536, -2.1e-6 at K = 61 440); the fix that
-    chains each k-step through a fresh accumulator (TWOG_X3_TMPACC=1) exists at build time and spills (profiles/HISTORY.md section 8).
+    chains each k-step through a fresh accumulator spills at two workgroups per CU (profiles/HISTORY.md section 8) and is
+    the one-workgroup-per-CU option TWOG_X3_DW_SPLIT_ACC=1.
     On SIGNED operands -- every GEMM of this model multiplies by signed weights or signed gradients -- the bias is 3e-9.
     Required: the class bit (X3 ran); the same-sign bias within the caps above (the documented state, so that a change for
     the worse fails); signed cases: |mean| <= 1e-7 of sum |a b|; max error <= 3e-6 of sum |a b| everywhere."""

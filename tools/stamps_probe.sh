@@ -4,7 +4,7 @@
 # LDS counter): the phase SHARES are what to read, not the total.
 set -e
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out
-( cd 2g-gcn_amd/csrc && /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DTWOG_STAMPS -c gemm_f32.hip -o /tmp/gemm_stamps.o \
-  && /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 /tmp/gemm_stamps.o $(ls *.o | grep -v gemm_f32.o) -o ../../gpurun_out/lib_stamps.so )
-TWOG_LIB_PATH=$PWD/gpurun_out/lib_stamps.so TWOG_GEMM_BPLANES=0 python3 tools/stamps_probe.py
+mkdir -p build
+( cd 2g-gcn_amd/csrc && /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DTWOG_STAMPS -c gemm_f32.hip -o ../../build/gemm_stamps.o \
+  && /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 ../../build/gemm_stamps.o $(ls *.o | grep -Ev '^gemm_f32\.o$|\.(jitter|diag|diagj)\.o$') -o ../../build/lib_stamps.so )
+TWOG_LIB_PATH=$PWD/build/lib_stamps.so python3 tools/stamps_probe.py
