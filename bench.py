@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark of the 2G-GCN hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR] [--full]
   (N > 1: one rank per GPU over RCCL -- either launched by torch.distributed.run (WORLD_SIZE set), or, when started
   bare, bench.py starts the N ranks itself as child processes before touching the GPU and exits with their code)
 
@@ -10,9 +10,13 @@ Workload (BASELINE.json configs[2]): synthetic clips T=120, N=34 geometry nodes 
 loss list (NLL on the two segment-level heads, vhoi/losses.py:53-61) + backward + gradient all-reduce (N > 1) + fused
 Adam; inputs are resident in HBM before the timed region. Prints ONE JSON line on rank 0.
 
-Also measured live: the dominant kernel's roofline (fp32-MFMA GEMM, HIP events around every GEMM launch made from the
-host composition during the timed steps) and, on rank 0 at N=1, the CPU baseline (the oracle = port of the reference's
-PyTorch-CPU path) on a bounded sample of the same workload.
+Also in every line: the dominant kernel's roofline (fp32-MFMA GEMM, HIP events around every GEMM launch made from the
+host composition during the timed steps) and the per-loop times of the recurrences, from the same events.
+
+--full adds what takes runs of its own after the timed steps: the geometric-level GCN roofline, forward-only clips/s,
+at N > 1 the collective diagnostics and the other scaling mode, for a host-composed step the GEMM figures (from extra
+instrumented steps), and, on rank 0 at N=1, the CPU baseline (the oracle = port of the reference's PyTorch-CPU path) on
+a bounded sample of the same workload (about two minutes; --no-cpu-baseline leaves it out).
 """
 import argparse
 import json
@@ -405,9 +409,12 @@ def main():
     ap.add_argument('--batch', type=int, default=None, help='clips per GPU per step (default: the workload\'s)')
     ap.add_argument('--workload', choices=sorted(WORKLOADS), default='c3',
                     help='c3 = the headline configuration; c2 / c5 = the other single-GPU shapes (informational)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure what takes runs of its own: GCN roofline, forward-only '
+                         'clips/s, N > 1 collective diagnostics and the other scaling mode, the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave the CPU baseline out')
     ap.add_argument('--cpu-baseline-only', action='store_true', help=argparse.SUPPRESS)
-    ap.add_argument('--forward-only', action='store_true', help=argparse.SUPPRESS)  # always reported now
+    ap.add_argument('--forward-only', action='store_true', help=argparse.SUPPRESS)  # no-op: forward-only clips/s comes with --full
     ap.add_argument('--scaling', choices=['weak', 'strong'], default='weak',
                     help='weak: the workload\'s batch per GPU (global = batch * N); strong: the workload\'s batch is the '
                          'GLOBAL batch, batch / N clips per GPU (SURVEY 8e: fixed global bs64 = 8 x 8 at N = 8)')
@@ -581,9 +588,9 @@ def main():
     torch.cuda.synchronize()
     # A host-composed configuration (constructor defaults: thousands of small GEMM launches per step from Python) is
     # host-bound, and two event records per launch would be a large part of what is measured (general segment loop: 374 ms
-    # per step with them, 211 without). Such a step is timed WITHOUT the per-launch events; the roofline figures then come
-    # from `prof_steps` extra instrumented steps after the timed region. The BASELINE workloads (~100 host-issued GEMM
-    # launches per step; the chains run inside the library) keep the events inside the timed region.
+    # per step with them, 211 without). Such a step is timed WITHOUT the per-launch events; with --full the roofline figures
+    # then come from `prof_steps` extra instrumented steps after the timed region. The BASELINE workloads (~100 host-issued
+    # GEMM launches per step; the chains run inside the library) keep the events inside the timed region.
     instrument_timed = dry.used <= 4000
     prof_steps = args.steps if instrument_timed else min(args.steps, 3)
     pool = [torch.cuda.Event(enable_timing=True) for _ in range(dry.used * prof_steps + 64)]
@@ -625,13 +632,16 @@ def main():
         dump_outputs(args.dump_outputs, [(f'output_{j}', o) for j, o in enumerate(kept['out']) if torch.is_tensor(o)]
                      + [('loss', loss), ('parameters', dp.flat.flat), ('gradients', dp.flat.grad)])
     del kept
-    if not instrument_timed:
+    if not instrument_timed and args.full:
         with GemmProfiler(K, pool) as prof:
             for i in range(prof_steps):
                 step()
             torch.cuda.synchronize()
         log(f'host-composed step ({dry.used // 2} instrumented launches): timed without per-launch events; GEMM figures '
             f'from {prof_steps} extra steps')
+    elif not instrument_timed:
+        log(f'host-composed step ({dry.used // 2} instrumented launches): timed without per-launch events; GEMM figures '
+            f'with --full')
     if world > 1:
         tmax = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -640,15 +650,15 @@ def main():
     log('collector passes inside the timed region (generation: ms): '
         + (' '.join(f'{g}:{ms:.1f}' for g, ms in gc_log if ms >= 0.5 or g == 2) or 'none above 0.5 ms')
         + f' ({len(gc_log)} passes)')
-    agg = prof.summary()
-    if os.environ.get('TWOG_BENCH_GEMM_DETAIL') and rank == 0:
+    agg = prof.summary() if prof is not None else None   # None: a host-composed step without --full
+    if prof is not None and os.environ.get('TWOG_BENCH_GEMM_DETAIL') and rank == 0:
         prof.detail(prof_steps)
     log(f'timed region done: {dt / args.steps * 1e3:.1f} ms/step; per step (device): '
         + ' '.join(f'{step_ev[i].elapsed_time(step_ev[i + 1]):.0f}' for i in range(args.steps)))
 
-    # ---- N > 1: what the step's collectives cost, and whether the group really spans N devices
+    # ---- --full, N > 1: what the step's collectives cost, and whether the group really spans N devices
     dist_diag = None
-    if world > 1:
+    if world > 1 and args.full:
         ones = torch.ones(1, device=device)
         dist.all_reduce(ones)
         buf = torch.empty_like(dp.flat.grad)
@@ -688,11 +698,11 @@ def main():
                          step_ms_without_collectives=float(tt[1]),
                          note='max over ranks; the gradient all-reduce of the timed step is bucketed and overlaps the backward pass')
 
-    # ---- N > 1: the OTHER scaling mode in the same line (SURVEY 8e asks for both). `value` is the mode --scaling names
-    # (default weak: the workload's 64 clips on every GPU); the secondary run keeps everything else and changes only the
-    # clips per GPU: strong = BASELINE configs[3]'s fixed GLOBAL batch of 64 (64 / N per GPU), weak = 64 per GPU.
+    # ---- --full, N > 1: the OTHER scaling mode in the same line (SURVEY 8e asks for both). `value` is the mode --scaling
+    # names (default weak: the workload's 64 clips on every GPU); the secondary run keeps everything else and changes only
+    # the clips per GPU: strong = BASELINE configs[3]'s fixed GLOBAL batch of 64 (64 / N per GPU), weak = 64 per GPU.
     other_scaling = None
-    if world > 1:
+    if world > 1 and args.full:
         other = 'strong' if args.scaling == 'weak' else 'weak'
         base = BS if args.workload_batch is None else args.workload_batch
         nb2 = base // world if other == 'strong' else base
@@ -721,23 +731,25 @@ def main():
             log(f'{other} scaling: {nb2} clips per GPU, {dt2 / args.steps * 1e3:.1f} ms/step')
             del step2, _keep
 
-    # secondary roofline: the geometric-level GCN forward alone (the kernel group the north star's HBM-roofline target
-    # names), HIP events around its launches; algorithmic bytes T*(16N + 512N) per clip
-    from twog_gcn_amd import ops as _ops
-    with torch.no_grad():
-        Pd = {n: p_ for n, p_ in model.named_parameters()}
-        bn = model.geometry_embedding_gcn.joint_embed.cnn[0].bn  # cloned: the measurement must not touch the statistics
-        bn_bufs = dict(running_mean=bn.running_mean.clone(), running_var=bn.running_var.clone(),
-                       num_batches_tracked=bn.num_batches_tracked.clone())
-        for _ in range(2):
-            _ops.geo_gcn_forward(K, Pd, x_human, bs, T, N_NODES, True, bn_bufs, {})
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            _ops.geo_gcn_forward(K, Pd, x_human, bs, T, N_NODES, True, bn_bufs, {})
-        e1.record()
-        torch.cuda.synchronize()
-        gcn_ms = e0.elapsed_time(e1) / 10
+    # ---- --full: secondary roofline: the geometric-level GCN forward alone (the kernel group the north star's HBM-roofline
+    # target names), HIP events around its launches; algorithmic bytes T*(16N + 512N) per clip
+    gcn_ms = None
+    if args.full:
+        from twog_gcn_amd import ops as _ops
+        with torch.no_grad():
+            Pd = {n: p_ for n, p_ in model.named_parameters()}
+            bn = model.geometry_embedding_gcn.joint_embed.cnn[0].bn  # cloned: the measurement must not touch the statistics
+            bn_bufs = dict(running_mean=bn.running_mean.clone(), running_var=bn.running_var.clone(),
+                           num_batches_tracked=bn.num_batches_tracked.clone())
+            for _ in range(2):
+                _ops.geo_gcn_forward(K, Pd, x_human, bs, T, N_NODES, True, bn_bufs, {})
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                _ops.geo_gcn_forward(K, Pd, x_human, bs, T, N_NODES, True, bn_bufs, {})
+            e1.record()
+            torch.cuda.synchronize()
+            gcn_ms = e0.elapsed_time(e1) / 10
     gcn_bytes = bs * T * (16 * N_NODES + 512 * N_NODES)
     # frame-level message attention (the other HBM-bound kernel pair of SURVEY 8d): algorithmic bytes per clip, fp32, each
     # tensor once. Forward, SURVEY's figure: read the entity features [x, h] (4 T E 2h), write every receiver's message
@@ -750,12 +762,12 @@ def main():
     att_fwd_bytes = bs * (4 * T * E_ * 2 * hh_ + att_out)
     att_fwd_bytes_all = bs * (att_feat + att_out + att_msg)
     att_bwd_bytes = bs * (att_out + att_feat + att_msg + att_msg + 2 * att_feat)
-    att_fwd_ms, att_bwd_ms = prof.attn_ms('fwd'), prof.attn_ms('bwd')
-    chain_ms = prof.chain_ms()
-
+    if prof is not None:
+        att_fwd_ms, att_bwd_ms = prof.attn_ms('fwd'), prof.attn_ms('bwd')
+        chain_ms = prof.chain_ms()
 
     fwd_only = None
-    if True:  # forward-only clips/s is part of every line (north star: ">= 50x the reference CPU forward")
+    if args.full:  # forward-only clips/s (north star: ">= 50x the reference CPU forward")
         with torch.no_grad():
             model(x_human, x_objects, mask, human_segmentation=seg)
             torch.cuda.synchronize()
@@ -767,20 +779,6 @@ def main():
             fwd_only = bs * world * max(2, args.steps // 2) / (time.perf_counter() - t1)
 
     if rank == 0:
-        total_gemm_s = sum(v[1] for v in agg.values())
-        dom = max(agg.items(), key=lambda kv: kv[1][1])
-        kind, (flops, secs, calls, bytes_alg) = dom
-        achieved = flops / secs / 1e12 if secs > 0 else 0.0
-        # HBM-side bytes per launch of the dominant kernel come from the committed rocprofv3 PMC passes of this same
-        # command (tools/bench_pmc.sh -> profiles/): counters cannot be read from inside the process.
-        traffic, traffic_src = None, None
-        import glob
-        tfiles = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'profiles',
-                                               'r*_gemm128_hbm_traffic.json')))
-        if kind.startswith('128x128') and tfiles:   # the latest round's committed counter passes
-            tj = json.load(open(tfiles[-1]))
-            traffic = tj['hbm_bytes_per_launch']
-            traffic_src = 'profiles/' + os.path.basename(tfiles[-1]) + ': ' + tj['source']
         result = {
             'metric': 'clips/sec fwd+bwd, T=120 N=34 C=512' if args.workload == 'c3' else f'clips/sec fwd+bwd, {wl["name"]} (informational)', 'value': bs * world * args.steps / dt, 'unit': 'clips/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3,
@@ -808,87 +806,106 @@ def main():
                        'devices': devices, 'collective_backend': backend if world > 1 else None,
                        'step': 'forward + multi-task loss (fused HIP criterion) + backward + gradient all-reduce + fused Adam',
                        'loss_last': float(loss.detach())},
-            'roofline': ({
-                # X3 kernels: fp32 operands split EXACTLY into three bf16 chunks, six chunk products per multiply-add on
-                # v_mfma_f32_32x32x16_bf16, fp32 accumulate (same error against fp64 as the fp32-MFMA kernels, tested).
-                # `achieved` = matrix FLOP/s actually executed (6 x the algorithmic 2 M N K), `peak` = dense bf16 MFMA.
-                'bound': 'mfma', 'kernel': 'gemm_x3_kernel<*> 128x128 tiles (v_mfma_f32_32x32x16_bf16 on 3 exact bf16 chunks per fp32 operand, 6 products, fp32 accumulate)',
-                'achieved': achieved * X3_PRODUCTS, 'peak': PEAK_BF16_MFMA_TFLOPS, 'unit': 'TFLOP/s',
-                'frac': achieved * X3_PRODUCTS / PEAK_BF16_MFMA_TFLOPS,
-                'fp32_equivalent_tflops': achieved, 'fp32_mfma_peak_tflops': PEAK_FP32_MFMA_TFLOPS,
-                'fp32_equivalent_over_fp32_mfma_peak': achieved / PEAK_FP32_MFMA_TFLOPS,
-                'note': 'TWOG_GEMM_X3=0 selects the native fp32-MFMA kernels (v_mfma_f32_32x32x2_f32: 0.80 of their 157.3 TFLOP/s peak, slower in wall time)',
-            } if kind == '128x128 bf16x3' else {
-                'bound': 'mfma', 'kernel': f'gemm_kernel<{kind.replace("x", ",")},*> (fp32 v_mfma_f32_32x32x2_f32)',
-                'achieved': achieved, 'peak': PEAK_FP32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
-                'frac': achieved / PEAK_FP32_MFMA_TFLOPS,
-            }),
-            'roofline_common': {'traffic': traffic,
-                         'traffic_unit': 'bytes per launch (L2<->fabric, Infinity-Cache hits included)',
-                         'traffic_source': traffic_src,
-                         'algorithmic_bytes_per_launch': bytes_alg / max(calls, 1),
-                         'launches_per_step': calls / prof_steps, 'avg_launch_ms': secs / max(calls, 1) * 1e3,
-                         'algorithmic_gflop_per_step': flops / prof_steps / 1e9,
-                         'share_of_step_time': secs / prof_steps / (dt / args.steps)},
-            'roofline_gcn': {'bound': 'hbm', 'kernel': 'geo_gcn forward (bn_stats, bn_finalize + similarity fold, gcn_fused_fwd, projection GEMM)',
-                             'achieved': gcn_bytes / (gcn_ms * 1e-3) / 1e9, 'peak': 8000.0, 'unit': 'GB/s',
-                             'frac': gcn_bytes / (gcn_ms * 1e-3) / 8e12, 'ms_per_batch': gcn_ms,
-                             'algorithmic_bytes_per_batch': gcn_bytes,
-                             'note': 'arithmetic-bound, not HBM-bound: fp32 MFMA floor of this block (2.41 MFLOP/frame at 157.3 '
-                                     'TFLOP/s) = 0.118 ms per bs64 batch; on the bf16 pipe with the exact three-way operand split '
-                                     '(6 products per multiply-add, 2 516.6 TFLOP/s) the floor would be 0.044 ms -- still above '
-                                     'the 0.043 ms that 40 % of the HBM peak would take for its 137.9 MB, and far above its HBM '
-                                     'floor (0.017 ms): at fp32-equivalent arithmetic the north star\'s >= 40 % of the HBM '
-                                     'roofline is out of reach for this block whatever the kernel. The bf16 x 3 port of '
-                                     'gcn_fused_fwd_kernel (0.13 ms of a 63 ms step at stake) was not built.'},
-            'roofline_attn_fwd': None if not att_fwd_ms else {
-                'bound': 'hbm', 'kernel': 'attn_fwd_kernel (frame level: 4 relations + geometry, one launch)',
-                'achieved': att_fwd_bytes / (att_fwd_ms * 1e-3) / 1e9, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
-                'frac': att_fwd_bytes / (att_fwd_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 'ms_per_launch': att_fwd_ms,
-                'algorithmic_bytes_per_launch': att_fwd_bytes,
-                'bytes_incl_sender_messages': att_fwd_bytes_all,
-                'achieved_incl_sender_messages': att_fwd_bytes_all / (att_fwd_ms * 1e-3) / 1e9},
-            'roofline_attn_bwd': None if not att_bwd_ms else {
-                'bound': 'hbm', 'kernel': 'attn_bwd_kernel (frame level)',
-                'achieved': att_bwd_bytes / (att_bwd_ms * 1e-3) / 1e9, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
-                'frac': att_bwd_bytes / (att_bwd_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 'ms_per_launch': att_bwd_ms,
-                'algorithmic_bytes_per_launch': att_bwd_bytes},
-            'gemm_classes': {k: {'tflops': (v[0] / v[1] / 1e12 if v[1] else 0.0), 'ms_per_step': v[1] / prof_steps * 1e3,
-                                 'launches_per_step': v[2] / prof_steps} for k, v in agg.items()},
-            'host_gemm_share_of_step': total_gemm_s / prof_steps / (dt / args.steps),
         }
-        result['roofline'].update(result.pop('roofline_common'))   # traffic, launches, shares: common to both kernel families
-        # ---- the recurrent chains (they run inside the library: timed per loop call, launch counts from the loops' code)
-        cm = chain_model(bs, CFG['hidden_size'])
         from twog_gcn_amd.kernels import get_kernels as _gk
         _K = _gk()
-        for _n, _flag in (('bigru_fwd', 'last_bigru_persistent'), ('bigru_bwd', 'last_bigru_bwd_persistent')):
-            if getattr(_K, _flag, False):   # small batches: ONE persistent launch for all time steps (csrc/gru_persist.hip)
-                cm[_n].update(gemm_launches=1, kernel='bigru_persist_' + _n[6:] + '_kernel (one launch for all steps: W_hh slices resident in LDS as '
-                              'bf16x3 fragments, v_mfma_f32_16x16x32_bf16, steps ordered by agent-scope counters)')
-        for _n, _flag in (('segrnn_fwd', 'last_segrnn_persistent'), ('segrnn_bwd', 'last_segrnn_bwd_persistent')):
-            if getattr(_K, _flag, False):   # small batches: the segment level as ONE persistent launch (csrc/seg_persist.hip)
-                cm[_n].update(gemm_launches=1, kernel='seg_persist_' + _n[7:] + '_kernel (one launch for all steps: four roles per slice of 16 '
-                              'units, weights resident in registers for the whole sequence, two in-launch hand-offs per step; sender MLPs, '
-                              'W_hh and the attention Gram matrix on 3 x bf16 (v_mfma_f32_16x16x32_bf16), the W_ih[:, messages] '
-                              'products / backward products on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32))')
-        x3_on = os.environ.get('TWOG_GEMM_X3', '1') != '0' and CFG['hidden_size'] >= 256 and bs * (H + O + 1) >= 6 * 64
-        src, pmc = latest_pmc_rows(('gemm_gate_bwd_x3s', 'gemm_x3s', 'gemm_gru_fwd', 'gemm_x3d', 'gemm_gate_bwd_x3d'))
-        chain_total_ms = sum(v for v in chain_ms.values() if v)
-        result['roofline_chain'] = {
-            'bound': 'latency (240 dependent time steps) + mfma',
-            'loops': {n: {'ms_per_call': chain_ms.get(n), 'gemm_launches_per_call': cm[n]['gemm_launches'],
-                          'us_per_time_step': (chain_ms[n] * 1e3 / T if chain_ms.get(n) else None),
-                          'algorithmic_gflop': cm[n]['flops'] / 1e9,
-                          'fp32_equivalent_tflops': (cm[n]['flops'] / (chain_ms[n] * 1e-3) / 1e12 if chain_ms.get(n) else None),
-                          'kernels': cm[n]['kernel']} for n in cm},
-            'ms_per_step': chain_total_ms, 'share_of_step_time': chain_total_ms / (dt / args.steps * 1e3),
-            'mfma_busy_pct_from_counters': pmc, 'counters_source': src,
-            'note': 'per-loop HIP events on the launch stream; each loop call issues its launches inside lib2ggcn_hip.so'}
-        host_x3 = sum(v[0] for k, v in agg.items() if 'bf16x3' in k)
-        host_all = sum(v[0] for v in agg.values())
-        lib = sum(c['flops'] for c in cm.values()) * prof_steps
-        result['x3_share_of_gemm_flops'] = ((host_x3 + (lib if x3_on else 0.0)) / (host_all + lib)) if host_all + lib > 0 else None
+        if agg is not None:   # per-kernel figures from the events of the timed steps (or, --full, of extra steps)
+            total_gemm_s = sum(v[1] for v in agg.values())
+            dom = max(agg.items(), key=lambda kv: kv[1][1])
+            kind, (flops, secs, calls, bytes_alg) = dom
+            achieved = flops / secs / 1e12 if secs > 0 else 0.0
+            # HBM-side bytes per launch of the dominant kernel come from the committed rocprofv3 PMC passes of this same
+            # command (tools/bench_pmc.sh -> profiles/): counters cannot be read from inside the process.
+            traffic, traffic_src = None, None
+            import glob
+            tfiles = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'profiles',
+                                                   'r*_gemm128_hbm_traffic.json')))
+            if kind.startswith('128x128') and tfiles:   # the latest round's committed counter passes
+                tj = json.load(open(tfiles[-1]))
+                traffic = tj['hbm_bytes_per_launch']
+                traffic_src = 'profiles/' + os.path.basename(tfiles[-1]) + ': ' + tj['source']
+            result.update({
+                'roofline': ({
+                    # X3 kernels: fp32 operands split EXACTLY into three bf16 chunks, six chunk products per multiply-add on
+                    # v_mfma_f32_32x32x16_bf16, fp32 accumulate (same error against fp64 as the fp32-MFMA kernels, tested).
+                    # `achieved` = matrix FLOP/s actually executed (6 x the algorithmic 2 M N K), `peak` = dense bf16 MFMA.
+                    'bound': 'mfma', 'kernel': 'gemm_x3_kernel<*> 128x128 tiles (v_mfma_f32_32x32x16_bf16 on 3 exact bf16 chunks per fp32 operand, 6 products, fp32 accumulate)',
+                    'achieved': achieved * X3_PRODUCTS, 'peak': PEAK_BF16_MFMA_TFLOPS, 'unit': 'TFLOP/s',
+                    'frac': achieved * X3_PRODUCTS / PEAK_BF16_MFMA_TFLOPS,
+                    'fp32_equivalent_tflops': achieved, 'fp32_mfma_peak_tflops': PEAK_FP32_MFMA_TFLOPS,
+                    'fp32_equivalent_over_fp32_mfma_peak': achieved / PEAK_FP32_MFMA_TFLOPS,
+                    'note': 'TWOG_GEMM_X3=0 selects the native fp32-MFMA kernels (v_mfma_f32_32x32x2_f32: 0.80 of their 157.3 TFLOP/s peak, slower in wall time)',
+                } if kind == '128x128 bf16x3' else {
+                    'bound': 'mfma', 'kernel': f'gemm_kernel<{kind.replace("x", ",")},*> (fp32 v_mfma_f32_32x32x2_f32)',
+                    'achieved': achieved, 'peak': PEAK_FP32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
+                    'frac': achieved / PEAK_FP32_MFMA_TFLOPS,
+                }),
+                'roofline_common': {'traffic': traffic,
+                             'traffic_unit': 'bytes per launch (L2<->fabric, Infinity-Cache hits included)',
+                             'traffic_source': traffic_src,
+                             'algorithmic_bytes_per_launch': bytes_alg / max(calls, 1),
+                             'launches_per_step': calls / prof_steps, 'avg_launch_ms': secs / max(calls, 1) * 1e3,
+                             'algorithmic_gflop_per_step': flops / prof_steps / 1e9,
+                             'share_of_step_time': secs / prof_steps / (dt / args.steps)},
+                'roofline_attn_fwd': None if not att_fwd_ms else {
+                    'bound': 'hbm', 'kernel': 'attn_fwd_kernel (frame level: 4 relations + geometry, one launch)',
+                    'achieved': att_fwd_bytes / (att_fwd_ms * 1e-3) / 1e9, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
+                    'frac': att_fwd_bytes / (att_fwd_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 'ms_per_launch': att_fwd_ms,
+                    'algorithmic_bytes_per_launch': att_fwd_bytes,
+                    'bytes_incl_sender_messages': att_fwd_bytes_all,
+                    'achieved_incl_sender_messages': att_fwd_bytes_all / (att_fwd_ms * 1e-3) / 1e9},
+                'roofline_attn_bwd': None if not att_bwd_ms else {
+                    'bound': 'hbm', 'kernel': 'attn_bwd_kernel (frame level)',
+                    'achieved': att_bwd_bytes / (att_bwd_ms * 1e-3) / 1e9, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
+                    'frac': att_bwd_bytes / (att_bwd_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 'ms_per_launch': att_bwd_ms,
+                    'algorithmic_bytes_per_launch': att_bwd_bytes},
+                'gemm_classes': {k: {'tflops': (v[0] / v[1] / 1e12 if v[1] else 0.0), 'ms_per_step': v[1] / prof_steps * 1e3,
+                                     'launches_per_step': v[2] / prof_steps} for k, v in agg.items()},
+                'host_gemm_share_of_step': total_gemm_s / prof_steps / (dt / args.steps),
+            })
+            result['roofline'].update(result.pop('roofline_common'))   # traffic, launches, shares: common to both kernel families
+            # ---- the recurrent chains (they run inside the library: timed per loop call, launch counts from the loops' code)
+            cm = chain_model(bs, CFG['hidden_size'])
+            for _n, _flag in (('bigru_fwd', 'last_bigru_persistent'), ('bigru_bwd', 'last_bigru_bwd_persistent')):
+                if getattr(_K, _flag, False):   # small batches: ONE persistent launch for all time steps (csrc/gru_persist.hip)
+                    cm[_n].update(gemm_launches=1, kernel='bigru_persist_' + _n[6:] + '_kernel (one launch for all steps: W_hh slices resident in LDS as '
+                                  'bf16x3 fragments, v_mfma_f32_16x16x32_bf16, steps ordered by agent-scope counters)')
+            for _n, _flag in (('segrnn_fwd', 'last_segrnn_persistent'), ('segrnn_bwd', 'last_segrnn_bwd_persistent')):
+                if getattr(_K, _flag, False):   # small batches: the segment level as ONE persistent launch (csrc/seg_persist.hip)
+                    cm[_n].update(gemm_launches=1, kernel='seg_persist_' + _n[7:] + '_kernel (one launch for all steps: four roles per slice of 16 '
+                                  'units, weights resident in registers for the whole sequence, two in-launch hand-offs per step; sender MLPs, '
+                                  'W_hh and the attention Gram matrix on 3 x bf16 (v_mfma_f32_16x16x32_bf16), the W_ih[:, messages] '
+                                  'products / backward products on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32))')
+            x3_on = os.environ.get('TWOG_GEMM_X3', '1') != '0' and CFG['hidden_size'] >= 256 and bs * (H + O + 1) >= 6 * 64
+            src, pmc = latest_pmc_rows(('gemm_gate_bwd_x3s', 'gemm_x3s', 'gemm_gru_fwd', 'gemm_x3d', 'gemm_gate_bwd_x3d'))
+            chain_total_ms = sum(v for v in chain_ms.values() if v)
+            result['roofline_chain'] = {
+                'bound': 'latency (240 dependent time steps) + mfma',
+                'loops': {n: {'ms_per_call': chain_ms.get(n), 'gemm_launches_per_call': cm[n]['gemm_launches'],
+                              'us_per_time_step': (chain_ms[n] * 1e3 / T if chain_ms.get(n) else None),
+                              'algorithmic_gflop': cm[n]['flops'] / 1e9,
+                              'fp32_equivalent_tflops': (cm[n]['flops'] / (chain_ms[n] * 1e-3) / 1e12 if chain_ms.get(n) else None),
+                              'kernels': cm[n]['kernel']} for n in cm},
+                'ms_per_step': chain_total_ms, 'share_of_step_time': chain_total_ms / (dt / args.steps * 1e3),
+                'mfma_busy_pct_from_counters': pmc, 'counters_source': src,
+                'note': 'per-loop HIP events on the launch stream; each loop call issues its launches inside lib2ggcn_hip.so'}
+            host_x3 = sum(v[0] for k, v in agg.items() if 'bf16x3' in k)
+            host_all = sum(v[0] for v in agg.values())
+            lib = sum(c['flops'] for c in cm.values()) * prof_steps
+            result['x3_share_of_gemm_flops'] = ((host_x3 + (lib if x3_on else 0.0)) / (host_all + lib)) if host_all + lib > 0 else None
+        if gcn_ms is not None:
+            result['roofline_gcn'] = {
+                'bound': 'hbm', 'kernel': 'geo_gcn forward (bn_stats, bn_finalize + similarity fold, gcn_fused_fwd, projection GEMM)',
+                'achieved': gcn_bytes / (gcn_ms * 1e-3) / 1e9, 'peak': 8000.0, 'unit': 'GB/s',
+                'frac': gcn_bytes / (gcn_ms * 1e-3) / 8e12, 'ms_per_batch': gcn_ms,
+                'algorithmic_bytes_per_batch': gcn_bytes,
+                'note': 'arithmetic-bound, not HBM-bound: fp32 MFMA floor of this block (2.41 MFLOP/frame at 157.3 '
+                        'TFLOP/s) = 0.118 ms per bs64 batch; on the bf16 pipe with the exact three-way operand split '
+                        '(6 products per multiply-add, 2 516.6 TFLOP/s) the floor would be 0.044 ms -- still above '
+                        'the 0.043 ms that 40 % of the HBM peak would take for its 137.9 MB, and far above its HBM '
+                        'floor (0.017 ms): at fp32-equivalent arithmetic the north star\'s >= 40 % of the HBM '
+                        'roofline is out of reach for this block whatever the kernel. The bf16 x 3 port of '
+                        'gcn_fused_fwd_kernel (0.13 ms of a 63 ms step at stake) was not built.'}
         # which form of each recurrence served this shape (persistent = one launch for all time steps, csrc/gru_persist.hip /
         # seg_persist.hip; otherwise one launch per dependency level, csrc/gru.hip / segrnn.hip)
         result['recurrence_paths'] = {
@@ -902,10 +919,11 @@ def main():
         if world > 1:
             # both scaling modes in one line: `value` / `scaling` above are the mode --scaling names, this is the other
             result['value_is'] = (f'{args.scaling} scaling: {bs} clips per GPU, global batch {bs * world}')
-            result['other_scaling'] = other_scaling
-            key = 'strong_scaling' if args.scaling == 'weak' else 'weak_scaling'
-            result[key] = other_scaling
-        if world == 1 and not args.no_cpu_baseline:
+            if args.full:
+                result['other_scaling'] = other_scaling
+                key = 'strong_scaling' if args.scaling == 'weak' else 'weak_scaling'
+                result[key] = other_scaling
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log('cpu baseline ...')
             result['cpu_baseline'] = cpu_baseline_in_child(args.workload)
             log('cpu baseline done')

@@ -25,7 +25,7 @@ def _bench(*flags, timeout=900):
 
 
 def test_bench_gpus_2_launches_two_ranks_weak():
-    d = _bench('--gpus', '2', '--steps', '2', '--warmup', '1', '--workload', 'c5', '--no-cpu-baseline')
+    d = _bench('--gpus', '2', '--steps', '2', '--warmup', '1', '--workload', 'c5', '--full', '--no-cpu-baseline')
     assert d['n_gpus'] == 2 and d['scaling'] == 'weak'
     assert len(d['config']['devices']) == 2 and d['config']['devices'][0].startswith('rank0:')
     assert d['config']['per_gpu_batch'] == 16 and d['config']['global_batch'] == 32
@@ -39,12 +39,26 @@ def test_bench_gpus_2_launches_two_ranks_weak():
 
 
 def test_bench_strong_scaling_splits_the_global_batch():
-    d = _bench('--gpus', '2', '--steps', '2', '--warmup', '1', '--workload', 'c5', '--scaling', 'strong',
+    d = _bench('--gpus', '2', '--steps', '2', '--warmup', '1', '--workload', 'c5', '--scaling', 'strong', '--full',
                '--no-cpu-baseline')
     assert d['n_gpus'] == 2 and d['scaling'] == 'strong'
     assert d['config']['per_gpu_batch'] == 8 and d['config']['global_batch'] == 16
     wk = d['weak_scaling']
     assert wk['scaling'] == 'weak' and wk['per_gpu_batch'] == 16 and wk['global_batch'] == 32 and wk['value'] > 0
+
+
+def test_bench_plain_run_leaves_the_full_figures_out():
+    """A plain run reports the headline and the figures of its own timed steps; what takes runs of its own (GCN
+    roofline, forward-only rate, CPU baseline) comes with --full."""
+    plain = _bench('--gpus', '1', '--steps', '2', '--warmup', '1', '--workload', 'c5')
+    assert plain['value'] > 0 and plain['unit'] == 'clips/s' and plain['higher_is_better'] is True
+    assert abs(plain['value'] - 16 * 2 / (plain['ms_per_step'] * 2e-3)) < 1e-6 * plain['value']
+    assert plain['roofline']['achieved'] > 0 and plain['roofline_chain']['ms_per_step'] > 0
+    for key in ('roofline_gcn', 'forward_only_clips_per_s', 'cpu_baseline'):
+        assert key not in plain, key
+    full = _bench('--gpus', '1', '--steps', '2', '--warmup', '1', '--workload', 'c5', '--full', '--no-cpu-baseline')
+    assert full['roofline_gcn']['ms_per_batch'] > 0 and full['forward_only_clips_per_s'] > 0
+    assert 'cpu_baseline' not in full
 
 
 def test_bench_world_size_mismatch_is_refused():
