@@ -229,6 +229,7 @@ SIGNATURES = {
     'twog_attn_fwd': [C.POINTER(Attn), _I, _P],
     'twog_attn_limits': [C.POINTER(C.c_int), C.POINTER(C.c_int)],
     'twog_attn_bwd': [C.POINTER(AttnBwd), _I, _P],
+    'twog_attn_last_path': [],
     'twog_segrnn_fwd': [C.POINTER(SegRnn), _P, C.c_size_t, _P],
     'twog_segrnn_bwd': [C.POINTER(SegRnn), C.POINTER(SegRnnBwd), _P, C.c_size_t, _P],
     'twog_segrnn_persistent_supported': [C.POINTER(SegRnn)],

@@ -826,6 +826,8 @@ inline size_t lds_bwd(const twog_attn_t& a, bool staged) {
 }
 constexpr size_t LDS_LIMIT = 160 * 1024;
 
+thread_local int g_last_path = 0;  // twog_attn_last_path(): code path of this thread's most recent attention launch
+
 // the rows of one instance must be equally strided: plain rows (inner <= 1) or exactly one outer group per instance
 inline bool rows_ok(const twog_rows_t& m, int n) { return !m.ptr || m.inner <= 1 || m.inner == n; }
 inline bool desc_ok(const twog_attn_t& a) {
@@ -850,6 +852,8 @@ extern "C" int twog_attn_limits(int* max_h, int* max_o) {
     *max_o = MAX_O;
     return 0;
 }
+
+extern "C" int twog_attn_last_path(void) { return g_last_path; }
 
 extern "C" int twog_attn_fwd(const twog_attn_t* a, int n, void* stream) {
     if (n > MAXG) return -1;
@@ -888,10 +892,12 @@ extern "C" int twog_attn_fwd(const twog_attn_t* a, int n, void* stream) {
         // CU overlap their phases better than three large ones (measured at the BASELINE shape: 0.262 ms with 512
         // threads, 0.231 with 256, 0.250 with 128; the row-parallel kernel: 0.283)
         static const int cols_threads = getenv("TWOG_ATTN_COLS_THREADS") ? atoi(getenv("TWOG_ATTN_COLS_THREADS")) : 256;
+        g_last_path = TWOG_ATTN_PATH_GRAM_COLUMNS | cols_threads << TWOG_ATTN_PATH_THREADS_SHIFT;
         hipLaunchKernelGGL(attn_fwd_cols_kernel, dim3(maxinst, n, 1), dim3(cols_threads), lds, (hipStream_t)stream, g);
         TWOG_CHECK_LAUNCH();
         return 0;
     }
+    g_last_path = (staged ? TWOG_ATTN_PATH_STAGED : 0) | (staged ? 1024 : 512) << TWOG_ATTN_PATH_THREADS_SHIFT;
     hipLaunchKernelGGL(attn_fwd_kernel, dim3(maxinst, n, staged ? 2 : 1), dim3(staged ? 1024 : 512), lds, (hipStream_t)stream, g);
     TWOG_CHECK_LAUNCH();
     return 0;
@@ -925,10 +931,16 @@ extern "C" int twog_attn_bwd(const twog_attn_bwd_t* a, int n, void* stream) {
     bool columns = !staged && cols_on;
     for (int i = 0; i < n; ++i) columns = columns && a[i].f.H <= 2 && a[i].f.O <= 8 && (a[i].f.hidden & 1) == 0;
     if (columns) {
+        g_last_path = TWOG_ATTN_PATH_BACKWARD | TWOG_ATTN_PATH_DW_COLUMNS | 256 << TWOG_ATTN_PATH_THREADS_SHIFT;
         hipLaunchKernelGGL(attn_bwd_cols_kernel, dim3(maxinst, n, 1), dim3(256), lds, (hipStream_t)stream, g);
         TWOG_CHECK_LAUNCH();
         return 0;
     }
+    // the kernel takes its wave-group form per descriptor (wg_dw); reported here: every descriptor of the launch takes it
+    bool wave_groups = staged && wg_on;
+    for (int i = 0; i < n; ++i) wave_groups = wave_groups && a[i].f.H <= 2 && a[i].f.O <= 8 && (a[i].f.hidden & 1) == 0;
+    g_last_path = TWOG_ATTN_PATH_BACKWARD | (staged ? TWOG_ATTN_PATH_STAGED : 0) |
+                  (wave_groups ? TWOG_ATTN_PATH_DW_WAVE_GROUPS : 0) | (staged ? 1024 : 256) << TWOG_ATTN_PATH_THREADS_SHIFT;
     hipLaunchKernelGGL(attn_bwd_kernel, dim3(maxinst, n, staged ? 2 : 1), dim3(staged ? 1024 : 256), lds, (hipStream_t)stream, g);
     TWOG_CHECK_LAUNCH();
     return 0;

@@ -799,6 +799,15 @@ class HipKernels:
             arr[i].relu_mask_dmsg = int(d.get('relu_mask_dmsg', 0))
         self._check(self.lib.twog_attn_bwd(arr, n, self._stream()), 'twog_attn_bwd')
 
+    ATTN_STAGED, ATTN_GRAM_COLUMNS, ATTN_DW_COLUMNS, ATTN_DW_WAVE_GROUPS, ATTN_BACKWARD = 1, 2, 4, 8, 16  # TWOG_ATTN_PATH_*
+    ATTN_THREADS_SHIFT = 16
+
+    def attn_last_path(self):
+        """Bit field (ATTN_*; workgroup size in the bits from ATTN_THREADS_SHIFT up) of the code path the most recent
+        attention launch of this thread selected -- attn_fwd / attn_bwd, or the last step of a launch-per-step segment
+        recurrence."""
+        return int(self.lib.twog_attn_last_path())
+
     # ---------------------------------------------------------------- segment-level recurrence
     @staticmethod
     def _seg_dims(p):

@@ -321,6 +321,17 @@ typedef struct {
 } twog_attn_bwd_t;
 int twog_attn_bwd(const twog_attn_bwd_t* a, int n, void* stream);
 
+/* Code path the most recent twog_attn_fwd / twog_attn_bwd launch of this thread selected (host-side decisions, taken
+ * over all descriptors of the launch); tests assert it, so that a case written for one path cannot silently move to
+ * another when a boundary changes. A call that launches nothing (no instances, an error) leaves the word as it was. */
+#define TWOG_ATTN_PATH_STAGED          1  /* latency regime: message / gradient rows staged in LDS, two workgroups per instance */
+#define TWOG_ATTN_PATH_GRAM_COLUMNS    2  /* forward: Gram matrix column-parallel from global memory (<= 10 entities)   */
+#define TWOG_ATTN_PATH_DW_COLUMNS      4  /* backward, streaming: dL/dw column-parallel, one relation after the other  */
+#define TWOG_ATTN_PATH_DW_WAVE_GROUPS  8  /* backward, staged: every descriptor takes the wave-group dL/dw (H <= 2, O <= 8) */
+#define TWOG_ATTN_PATH_BACKWARD        16 /* written by twog_attn_bwd (else by twog_attn_fwd)                           */
+#define TWOG_ATTN_PATH_THREADS_SHIFT   16 /* workgroup size = word >> 16                                                */
+int twog_attn_last_path(void);
+
 /* ===============================================================================================================
  * Segment-level gated bidirectional recurrence with message passing (vhoi/models.py:785-880, :1535-1564,
  * :1051, :1145, :1239, :1334). Buffers are (clip, time, entity)-ordered; [2] = direction (0 forward, 1 backward).

@@ -357,7 +357,7 @@ class FakeKernels:
         mask = d.get('obj_mask')
         dev = fh.device
         if mask is None:
-            m = torch.ones(n, O, device=dev)
+            m = torch.ones(n, O, device=dev, dtype=fh.dtype)
         else:
             m = mask.repeat_interleave(d['inst_per_clip'], dim=0)[:n]
 
@@ -460,6 +460,10 @@ class FakeKernels:
                 else:
                     dst.copy_(val.reshape(dst.shape))
 
+    def attn_last_path(self):
+        """The double has one code path: no bit of HipKernels.ATTN_* is ever set."""
+        return 0
+
     # ------------------------------------------------------------------ segment-level recurrence
     @staticmethod
     def _seg_dims(p):
@@ -492,7 +496,7 @@ class FakeKernels:
         dev = p['gi_h'].device
         nsh, nso, nmh, nmo = self._seg_dims(p)
         natt = H * H + 2 * H * O + O * O
-        z = lambda *s: torch.zeros(*s, device=dev)
+        z = lambda *s: torch.zeros(*s, device=dev, dtype=p['gi_h'].dtype)   # (an fp64 p runs the specification in fp64)
         bufs = dict(hs_h=z(bs, T, H, 2 * h), hs_o=z(bs, T, O, 2 * h), save_h=z(2, bs, T, H, 4 * h),
                     save_o=z(2, bs, T, O, 4 * h), msrc_h=z(2, bs, T, H, nsh * h), msrc_o=z(2, bs, T, O, nso * h),
                     mg_h=z(2, bs, T, H, nmh * h), mg_o=z(2, bs, T, O, nmo * h), att=z(2, T, bs, natt))
@@ -528,7 +532,7 @@ class FakeKernels:
         bs, T, H, O, h = p['bs'], p['T'], p['H'], p['O'], p['hidden']
         dev = bufs['hs_h'].device
         nsh, nso, nmh, nmo = self._seg_dims(p)
-        z = lambda *s: torch.zeros(*s, device=dev)
+        z = lambda *s: torch.zeros(*s, device=dev, dtype=bufs['hs_h'].dtype)
         out = dict(d_gi_h=z(bs, T, H, 6 * h), d_gi_o=z(bs, T, O, 6 * h), d_gh_h=z(bs, T, H, 6 * h),
                    d_gh_o=z(bs, T, O, 6 * h), d_u_h=z(bs, T, H), d_u_o=z(bs, T, O),
                    d_pre_h=z(2, bs, T, H, nsh * h), d_pre_o=z(2, bs, T, O, nso * h))
@@ -685,7 +689,7 @@ class FakeKernels:
     def ssp_fwd(self, gi, ph, ps, att, mask, n_inst, inst_per_clip, H, O, att_off):
         cols = gi.shape[-1]
         m = (mask.repeat_interleave(inst_per_clip, 0) if mask is not None else torch.ones(n_inst, O)).view(n_inst, O, 1)
-        add = torch.zeros(n_inst, O, cols)
+        add = torch.zeros(n_inst, O, cols, dtype=gi.dtype)
         if ph is not None:
             w = att[:, att_off:att_off + O * H].view(n_inst, O, H)
             add = add + torch.einsum('nkh,nhc->nkc', w, ph.view(n_inst, H, cols))
@@ -696,7 +700,7 @@ class FakeKernels:
     def ssp_gather(self, dgi, att, att_ld_clip, att_ld_frame, att_off, n_inst, inst_per_clip, H, O):
         cols = dgi.shape[1]
         flat = att.reshape(-1)
-        qh = torch.zeros(n_inst, H, cols)
+        qh = torch.zeros(n_inst, H, cols, dtype=dgi.dtype)
         g = dgi.reshape(n_inst, O, cols)
         for inst in range(n_inst):
             c, f = divmod(inst, inst_per_clip)
@@ -708,7 +712,7 @@ class FakeKernels:
     def ssp_bwd(self, dgi, ph, att, mask, n_inst, inst_per_clip, H, O, att_off, want_qs, dw=None):
         cols = dgi.shape[-1]
         m = (mask.repeat_interleave(inst_per_clip, 0) if mask is not None else torch.ones(n_inst, O)).view(n_inst, O, 1)
-        g = dgi.view(n_inst, O, cols) * (m != 0).float()
+        g = dgi.view(n_inst, O, cols) * (m != 0).to(dgi.dtype)
         qh = qs = None
         if ph is not None:
             w = att[:, att_off:att_off + O * H].view(n_inst, O, H)

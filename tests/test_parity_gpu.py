@@ -596,6 +596,46 @@ def test_more_entities_than_the_tuned_attention_kernel_holds(H, O, N):
     _oracle_vs_hip(bs=2, T=5, H=H, O=O, N=N, h=32, backward=True, seed=19, max_nudged_share=0.10)
 
 
+def _watch_the_message_kernels(monkeypatch):
+    """Counts the calls that reach the general single-relation kernels and collects the code path of every host-issued
+    attention backward launch (HipKernels.attn_last_path)."""
+    from twog_gcn_amd.kernels import HipKernels
+    seen = dict(general=0, attn_bwd_paths=[])
+    for name in ('relation_fwd', 'relation_fwd_many', 'relation_bwd', 'relation_bwd_many'):
+        def counting(self, *a, _f=getattr(HipKernels, name), **kw):
+            seen['general'] += 1
+            return _f(self, *a, **kw)
+        monkeypatch.setattr(HipKernels, name, counting)
+
+    def attn_bwd(self, descs, _f=HipKernels.attn_bwd):
+        _f(self, descs)
+        seen['attn_bwd_paths'].append(self.attn_last_path())
+    monkeypatch.setattr(HipKernels, 'attn_bwd', attn_bwd)
+    return seen
+
+
+@pytest.mark.parametrize('H,O,N,h', [(3, 10, 40, 32), (4, 12, 50, 32), (4, 2, 34, 64)])
+def test_as_many_entities_as_the_tuned_attention_kernel_holds(H, O, N, h, monkeypatch):
+    """The complement of the test above: 3 and 4 humans, up to 12 objects -- the clips the host routes to the TUNED kernels
+    (attn.hip, ssp.hip, segrnn.hip; at h = 64 the persistent segment launch) -- forward + backward against the oracle, at
+    the tolerances and the nudged-unit share of the test above; no call may reach the general single-relation kernels."""
+    seen = _watch_the_message_kernels(monkeypatch)
+    _oracle_vs_hip(bs=2, T=5, H=H, O=O, N=N, h=h, backward=True, seed=19, max_nudged_share=0.10)
+    assert seen['general'] == 0, 'a clip within the tuned range ran on the general single-relation kernels'
+    assert seen['attn_bwd_paths'], 'the tuned attention backward kernel did not run'
+
+
+def test_4_humans_and_12_objects_at_full_width_take_the_unstaged_attention_backward(monkeypatch):
+    """(4, 12) at h = 512: the rows the frame-level attention backward would stage (82 rows of 516 floats) exceed the 160 KB
+    of LDS, so the launch falls back to the unstaged 256-thread form at 3 instances -- reached through the model here."""
+    from twog_gcn_amd.kernels import HipKernels as HK
+    seen = _watch_the_message_kernels(monkeypatch)
+    _oracle_vs_hip(bs=1, T=3, H=4, O=12, N=50, h=512, backward=True, seed=19, max_nudged_share=0.10)
+    assert seen['general'] == 0
+    want = HK.ATTN_BACKWARD | 256 << HK.ATTN_THREADS_SHIFT
+    assert want in seen['attn_bwd_paths'], [hex(p) for p in seen['attn_bwd_paths']]
+
+
 def test_limits_fail_loudly():
     """More entities than ANY kernel of the path supports must raise, not silently fall back."""
     N, h, O = 26, 16, 17
