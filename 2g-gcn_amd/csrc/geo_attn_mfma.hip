@@ -341,12 +341,14 @@ inline size_t lds_bwd_bytes(int N, bool with_m) {
 
 extern "C" int twog_gcn_attn2_fwd(const float* x, const float* md, int n_frames, int n_nodes, float* adj, float* z,
                                   void* stream) {
-    if (n_nodes > MAXN || n_nodes < 1) return -1;
+    int plan[4];
+    const int rc = twog_internal_plan_attn2(TWOG_GCN_PLAN_ATTN2_FWD, n_frames, n_nodes, plan);
+    if (rc < 0) return rc;
     if (n_frames <= 0) return 0;
-    const size_t lds = lds_fwd_bytes(n_nodes);
+    const int grid = plan[0];
+    const size_t lds = (size_t)plan[2];
     static std::atomic<uint32_t> lds_attr_done{0};
     twog_allow_dynamic_lds(gcn_attn2_fwd_kernel, 160 * 1024, lds_attr_done);
-    const int grid = n_frames < 512 ? n_frames : 512;
     hipLaunchKernelGGL(gcn_attn2_fwd_kernel, dim3(grid), dim3(512), lds, (hipStream_t)stream, x, md, n_frames, n_nodes,
                        adj, z);
     TWOG_CHECK_LAUNCH();
@@ -355,14 +357,34 @@ extern "C" int twog_gcn_attn2_fwd(const float* x, const float* md, int n_frames,
 
 extern "C" int twog_gcn_attn2_bwd_blocks(int n_frames) { return n_frames < 256 ? (n_frames > 0 ? n_frames : 1) : 256; }
 
-extern "C" int twog_gcn_attn2_bwd(const float* x, const float* md, const float* adj, const float* dz, int n_frames,
-                                  int n_nodes, float* dx_att, float* partials, int n_blocks, void* stream) {
+// the launch geometry of twog_gcn_attn2_fwd / twog_gcn_attn2_bwd: out = {grid, 1 frame per trip, LDS bytes, with_m (backward)}
+int twog_internal_plan_attn2(int kernel, int n_frames, int n_nodes, int out[4]) {
     if (n_nodes > MAXN || n_nodes < 1) return -1;
-    if (n_frames <= 0) return 0;
-    if (n_blocks != twog_gcn_attn2_bwd_blocks(n_frames)) return -2;
+    out[1] = 1;
+    if (kernel == TWOG_GCN_PLAN_ATTN2_FWD) {
+        out[0] = n_frames < 512 ? (n_frames > 0 ? n_frames : 0) : 512;
+        out[2] = (int)lds_fwd_bytes(n_nodes);
+        out[3] = 0;
+        return 0;
+    }
     const bool with_m = lds_bwd_bytes(n_nodes, true) <= 160 * 1024;
     const size_t lds = lds_bwd_bytes(n_nodes, with_m);
-    if (lds > 160 * 1024) return -3;
+    out[0] = twog_gcn_attn2_bwd_blocks(n_frames);
+    out[2] = (int)lds;
+    out[3] = with_m ? 1 : 0;
+    return lds > 160 * 1024 ? -3 : 0;
+}
+
+extern "C" int twog_gcn_attn2_bwd(const float* x, const float* md, const float* adj, const float* dz, int n_frames,
+                                  int n_nodes, float* dx_att, float* partials, int n_blocks, void* stream) {
+    int plan[4];
+    const int rc = twog_internal_plan_attn2(TWOG_GCN_PLAN_ATTN2_BWD, n_frames, n_nodes, plan);
+    if (rc == -1) return rc;
+    if (n_frames <= 0) return 0;
+    if (n_blocks != plan[0]) return -2;
+    if (rc < 0) return rc;
+    const bool with_m = plan[3] != 0;
+    const size_t lds = (size_t)plan[2];
     // 16 waves: the phases are lists of 9 ... 16 independent 16x16 tiles, each a chain of 12-16 dependent MFMAs -- with 8 waves
     // every list takes two rounds with half the waves idle in the second (TWOG_GCN_ATTN2_WAVES=8: the 8-wave form)
     static const int waves = getenv("TWOG_GCN_ATTN2_WAVES") ? atoi(getenv("TWOG_GCN_ATTN2_WAVES")) : 16;

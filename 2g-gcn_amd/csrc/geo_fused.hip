@@ -7,9 +7,10 @@
 //
 // What it replaces: embed1_fwd (wrote e1: frames*N x 64), the X GEMM (read e1, wrote X) and gcn_attn2_fwd (read X) --
 // three launches that each streamed the (frames*N) x 64 activations through HBM, the last one with five workgroup
-// barriers per frame. Here a workgroup takes FG consecutive frames (R = FG*N rows, FG = 7 at N = 34):
-//   A  X = relu(e1 W2^T + b2) for the group's rows, tiled over the whole GROUP (7 frames x 34 nodes = 238 rows = 15 tiles;
-//      frame by frame it would be 7 x 3). e1 is never stored: each lane computes the 16 values of its A fragment
+// barriers per frame. Here a workgroup takes FG consecutive frames (R = FG*N rows; FG = 8 up to N = 34, 6 at N = 50, 4 at N = 64:
+// twog_gcn_launch_plan reports it):
+//   A  X = relu(e1 W2^T + b2) for the group's rows, tiled over the whole GROUP (8 frames x 34 nodes = 272 rows = 17 tiles;
+//      frame by frame it would be 8 x 3). e1 is never stored: each lane computes the 16 values of its A fragment
 //      (row = lane%16, k = lane/16 + 4 kk) from the four normalised inputs of its row. X -> LDS (+ global: the backward
 //      pass reads it). Products on v_mfma_f32_16x16x4_f32 (exact fp32).
 //   B  one wave takes 16 rows of ONE frame from start to end: P = X M + d (to its private LDS scratch, to change from the
@@ -249,12 +250,16 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_fused_fwd_kernel(const flo
             }
             // Z = S X for the item's rows: k runs over the frame's nodes (rows of X_f), k = g + 4 kk; fragments first
             {
-                // (k runs to NP: the padding columns of S are exact zeros and the rows of sX behind the frame are finite --
-                // the next frame's rows or the zeroed tail -- so the extra steps add nothing; a compile-time trip count
-                // keeps the 16 + 4 x KSTEPS operand loads and the MFMAs free of branches)
+                // (k runs to NP: a compile-time trip count keeps the 16 + 4 x KSTEPS operand loads and the MFMAs free of
+                // branches. The padding columns of S are exact zeros, but the rows of sX behind the frame are the NEXT frame's
+                // X, which may belong to another clip and be non-finite: 0 x inf = NaN would land in this frame's Z. So the X
+                // operand is selected to zero for k >= N; only the last four k-steps can reach it, N > NP - 16.)
                 float sa[KSTEPS];
 #pragma unroll
                 for (int kk = 0; kk < KSTEPS; ++kk) sa[kk] = priv[i16 * LDN + g + 4 * kk];
+                bool kpad[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) kpad[j] = g + 4 * (KSTEPS - 4 + j) >= N;
                 f32x4g zc[4];
 #pragma unroll
                 for (int ct = 0; ct < 4; ++ct) {
@@ -262,6 +267,8 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_fused_fwd_kernel(const flo
                     float xb[KSTEPS];
 #pragma unroll
                     for (int kk = 0; kk < KSTEPS; ++kk) xb[kk] = pb[kk * 4 * LDK];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) xb[KSTEPS - 4 + j] = kpad[j] ? 0.f : xb[KSTEPS - 4 + j];
                     zc[ct] = f32x4g{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int kk = 0; kk < KSTEPS; ++kk) zc[ct] = mfma16(sa[kk], xb[kk], zc[ct]);
@@ -288,11 +295,9 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_fused_fwd_kernel(const flo
 // x_geo: geometry of human 0 (x_human + 2048), frame f at x_geo + f * frame_stride; ab [2][4N] from twog_bn_finalize;
 // w1 [64][4], b1 [64] (joint_embed.cnn.1), w2 [64][64], b2 [64] (joint_embed.cnn.3), md [65][64] = [Mt | d] (the folded
 // similarity, see geo_attn_mfma.hip). Outputs: x_out [(f,n)][64] (may be NULL: inference), adj [f][N][N], z [(f,n)][64].
-extern "C" int twog_gcn_fused_fwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, const float* ab,
-                                  const float* w1, const float* b1, const float* w2, const float* b2, const float* md,
-                                  float* x_out, float* adj, float* z, void* stream) {
+// the launch geometry of twog_gcn_fused_fwd: out = {grid, frames per group, LDS bytes, NT}
+int twog_internal_plan_fused_fwd(int n_frames, int n_nodes, int out[4]) {
     if (n_nodes > MAXN || n_nodes < 1) return -1;
-    if (n_frames <= 0) return 0;
     // frames per group: as many as fit the CU's LDS (rows of X for the group + one scratch tile per wave), at most 8
     static const int force_fg = getenv("TWOG_GCN_FG") ? atoi(getenv("TWOG_GCN_FG")) : 0;
     Layout best = layout_of(n_nodes, 1);
@@ -303,16 +308,31 @@ extern "C" int twog_gcn_fused_fwd(const float* x_geo, int64_t frame_stride, int 
     if (force_fg > 0 && layout_of(n_nodes, force_fg).floats * sizeof(float) <= 160 * 1024) best = layout_of(n_nodes, force_fg);
     const size_t lds = best.floats * sizeof(float);
     if (lds > 160 * 1024) return -3;
-    const int n_groups = (n_frames + best.FG - 1) / best.FG;
-    const int grid = n_groups < 256 ? n_groups : 256;
+    const int n_groups = n_frames > 0 ? (n_frames + best.FG - 1) / best.FG : 0;
+    out[0] = n_groups < 256 ? n_groups : 256;
+    out[1] = best.FG;
+    out[2] = (int)lds;
+    out[3] = best.NT;
+    return 0;
+}
+
+extern "C" int twog_gcn_fused_fwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, const float* ab,
+                                  const float* w1, const float* b1, const float* w2, const float* b2, const float* md,
+                                  float* x_out, float* adj, float* z, void* stream) {
+    int plan[4];
+    const int rc = twog_internal_plan_fused_fwd(n_frames, n_nodes, plan);
+    if (rc < 0) return rc;
+    if (n_frames <= 0) return 0;
+    const int grid = plan[0], FG = plan[1];
+    const size_t lds = (size_t)plan[2];
     static std::atomic<uint32_t> done1{0}, done2{0}, done3{0}, done4{0};
 #define TWOG_GCN_LAUNCH(NT_, FLAG_)                                                                                      \
     do {                                                                                                                 \
         twog_allow_dynamic_lds(gcn_fused_fwd_kernel<NT_>, 160 * 1024, FLAG_);                                            \
         hipLaunchKernelGGL(gcn_fused_fwd_kernel<NT_>, dim3(grid), dim3(64 * NWAVES), lds, (hipStream_t)stream, x_geo,    \
-                           frame_stride, n_frames, n_nodes, ab, w1, b1, w2, b2, md, x_out, adj, z, best.FG);            \
+                           frame_stride, n_frames, n_nodes, ab, w1, b1, w2, b2, md, x_out, adj, z, FG);                 \
     } while (0)
-    switch (best.NT) {
+    switch (plan[3]) {
         case 1: TWOG_GCN_LAUNCH(1, done1); break;
         case 2: TWOG_GCN_LAUNCH(2, done2); break;
         case 3: TWOG_GCN_LAUNCH(3, done3); break;

@@ -379,6 +379,30 @@ __global__ __launch_bounds__(256) void gcn_attn_bwd_kernel(const float* qk, cons
 
 extern "C" int twog_gcn_max_nodes(void) { return MAX_NODES; }
 
+namespace {
+inline int embed1_fwd_grid(int64_t rows) { const int64_t g = (rows + 3) / 4; return (int)(g > 4096 ? 4096 : g); }
+inline int attn_grid(int n_frames) { return n_frames < 2048 ? n_frames : 2048; }
+inline size_t attn_fwd_lds(int N) { return sizeof(float) * (size_t)(2 * N * LDQ + N * LDX + N * (N + 1)); }
+inline size_t attn_bwd_lds(int N) { return sizeof(float) * (size_t)(2 * N * LDQ + 2 * N * LDX + 2 * N * (N + 1)); }
+}  // namespace
+
+extern "C" int twog_gcn_launch_plan(int kernel, int n_frames, int n_nodes, int out[4]) {
+    if (!out) return -2;
+    if (n_nodes > MAX_NODES || n_nodes < 1) return -1;
+    if (n_frames < 0) n_frames = 0;
+    out[0] = out[2] = out[3] = 0;
+    out[1] = 1;
+    switch (kernel) {
+        case TWOG_GCN_PLAN_FUSED_FWD: return twog_internal_plan_fused_fwd(n_frames, n_nodes, out);
+        case TWOG_GCN_PLAN_ATTN2_FWD:
+        case TWOG_GCN_PLAN_ATTN2_BWD: return twog_internal_plan_attn2(kernel, n_frames, n_nodes, out);
+        case TWOG_GCN_PLAN_EMBED1_FWD: out[0] = embed1_fwd_grid((int64_t)n_frames * n_nodes); return 0;
+        case TWOG_GCN_PLAN_ATTN_FWD: out[0] = attn_grid(n_frames); out[2] = (int)attn_fwd_lds(n_nodes); return 0;
+        case TWOG_GCN_PLAN_ATTN_BWD: out[0] = attn_grid(n_frames); out[2] = (int)attn_bwd_lds(n_nodes); return 0;
+        default: return -2;
+    }
+}
+
 extern "C" int twog_bn_stats(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, double* partials,
                              int n_blocks, void* stream) {
     if (n_nodes > MAX_NODES || n_nodes < 1) return -1;
@@ -404,9 +428,7 @@ extern "C" int twog_bn_finalize(const double* partials, int n_blocks, int n_fram
 extern "C" int twog_gcn_embed1_fwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes,
                                    const float* ab, const float* w1, const float* b1, float* e1, void* stream) {
     if (n_nodes > MAX_NODES || n_nodes < 1) return -1;
-    const int64_t rows = (int64_t)n_frames * n_nodes;
-    int grid = (int)((rows + 3) / 4);
-    if (grid > 4096) grid = 4096;
+    const int grid = embed1_fwd_grid((int64_t)n_frames * n_nodes);
     hipLaunchKernelGGL(embed1_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x_geo, frame_stride, n_frames,
                        n_nodes, ab, w1, b1, e1);
     TWOG_CHECK_LAUNCH();
@@ -431,8 +453,8 @@ extern "C" int twog_gcn_embed1_bwd(const float* x_geo, int64_t frame_stride, int
 extern "C" int twog_gcn_attn_fwd(const float* qk, const float* x, int n_frames, int n_nodes, float* s_out, float* z,
                                  void* stream) {
     if (n_nodes > MAX_NODES || n_nodes < 1) return -1;
-    const size_t lds = sizeof(float) * (size_t)(2 * n_nodes * LDQ + n_nodes * LDX + n_nodes * (n_nodes + 1));
-    int grid = n_frames < 2048 ? n_frames : 2048;
+    const size_t lds = attn_fwd_lds(n_nodes);
+    const int grid = attn_grid(n_frames);
     hipLaunchKernelGGL(gcn_attn_fwd_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, qk, x, n_frames, n_nodes,
                        s_out, z);
     TWOG_CHECK_LAUNCH();
@@ -442,8 +464,8 @@ extern "C" int twog_gcn_attn_fwd(const float* qk, const float* x, int n_frames, 
 extern "C" int twog_gcn_attn_bwd(const float* qk, const float* x, const float* s, const float* dz, int n_frames,
                                  int n_nodes, float* dx_att, float* dqk, void* stream) {
     if (n_nodes > MAX_NODES || n_nodes < 1) return -1;
-    const size_t lds = sizeof(float) * (size_t)(2 * n_nodes * LDQ + 2 * n_nodes * LDX + 2 * n_nodes * (n_nodes + 1));
-    int grid = n_frames < 2048 ? n_frames : 2048;
+    const size_t lds = attn_bwd_lds(n_nodes);
+    const int grid = attn_grid(n_frames);
     hipLaunchKernelGGL(gcn_attn_bwd_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, qk, x, s, dz, n_frames,
                        n_nodes, dx_att, dqk);
     TWOG_CHECK_LAUNCH();

@@ -36,6 +36,12 @@ int twog_internal_gemm_gru_fwd(const twog_gemm_t* gh, const twog_gemm_t* gim, co
 
 int twog_internal_gru_fwd_mode(void);   // TWOG_GRU_FWD_FUSION (part of the chains' hipGraph keys: it changes what is captured)
 
+// library-internal: the launch geometry of the geometric-level GCN kernels, out = {grid, frames per group, dynamic LDS bytes,
+// variant}. The launchers launch with exactly these numbers and twog_gcn_launch_plan (geo_gcn.hip) reports them; < 0 = the
+// launcher's own error code. geo_fused.hip / geo_attn_mfma.hip (kernel = TWOG_GCN_PLAN_ATTN2_FWD or _BWD) / geo_gcn.hip.
+int twog_internal_plan_fused_fwd(int n_frames, int n_nodes, int out[4]);
+int twog_internal_plan_attn2(int kernel, int n_frames, int n_nodes, int out[4]);
+
 // address of row r in a twog_rows_t (see include/twog_gcn.h)
 __device__ __forceinline__ int64_t twog_row_off(const twog_rows_t& m, int r) {
     if (m.inner <= 1) return (int64_t)r * m.ld_outer;

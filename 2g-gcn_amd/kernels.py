@@ -338,6 +338,26 @@ class HipKernels:
         bs, T, H, Fh = x_human.shape
         return x_human.data_ptr() + 2048 * 4, H * Fh, bs * T
 
+    # twog_gcn_launch_plan: TWOG_GCN_PLAN_* of include/twog_gcn.h
+    PLAN_FUSED_FWD, PLAN_ATTN2_FWD, PLAN_ATTN2_BWD, PLAN_EMBED1_FWD, PLAN_ATTN_FWD, PLAN_ATTN_BWD = range(6)
+
+    def gcn_launch_plan(self, kernel, n_frames, n_nodes):
+        """(grid, frames per group, dynamic LDS bytes, variant) the launcher of `kernel` (PLAN_*) uses at this size; host
+        arithmetic of the library, no GPU call. variant: NT of the fused forward kernel, with_m of gcn_attn2_bwd."""
+        out = (C.c_int * 4)()
+        self._check(self.lib.twog_gcn_launch_plan(kernel, n_frames, n_nodes, out), 'twog_gcn_launch_plan')
+        return tuple(out)
+
+    @staticmethod
+    def bn_stats_blocks(n_frames):
+        """Workgroups of twog_bn_stats: >= 8 frames per block, at most 240 blocks (the finalize kernel sums them 4-wide)."""
+        return max(1, min(240, n_frames // 8))
+
+    @staticmethod
+    def embed1_bwd_blocks(n_rows):
+        """Workgroups (= partial rows) of twog_gcn_embed1_bwd: 4 waves per block, >= 8 rows per wave."""
+        return max(1, min(2048, (n_rows + 31) // 32))
+
     def bn_fold(self, x_human, n_nodes, gamma, beta, running_mean, running_var, num_batches_tracked, training,
                 stats_reduce=None, fold=None):
         """stats_reduce (optional, sync-BN of distributed.DataParallel): callable (sums fp64 [2*4N], n_frames) ->
@@ -349,7 +369,7 @@ class HipKernels:
         dev = x_human.device
         ab = torch.empty(2, nch, dtype=torch.float32, device=dev)
         mi = torch.empty(2, nch, dtype=torch.float32, device=dev)
-        nblk = max(1, min(240, nf // 8))   # >= 8 frames per block, at most 240 blocks (the finalize kernel sums them 4-wide)
+        nblk = self.bn_stats_blocks(nf)
         partials = torch.empty(nblk * 2 * nch, dtype=torch.float64, device=dev)
         if training:
             self._check(self.lib.twog_bn_stats(ptr, fstride, nf, n_nodes, partials.data_ptr(), nblk, self._stream()),
@@ -387,7 +407,7 @@ class HipKernels:
     def gcn_embed1_bwd(self, x_human, n_nodes, ab, mean_invstd, w1, de1):
         ptr, fstride, nf = self._geo(x_human)
         dev = x_human.device
-        nblk = max(1, min(2048, (nf * n_nodes + 31) // 32))  # 4 waves per block, >= 8 rows per wave
+        nblk = self.embed1_bwd_blocks(nf * n_nodes)
         partials = torch.empty(nblk * (320 + 8 * n_nodes), dtype=torch.float32, device=dev)
         dw1 = torch.empty(64, 4, dtype=torch.float32, device=dev)
         db1 = torch.empty(64, dtype=torch.float32, device=dev)

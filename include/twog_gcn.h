@@ -105,6 +105,19 @@ int twog_gemm_f32_chain(const twog_gemm_t* problems, int n_problems, int a_kmajo
  * feature c at [n*4 + c]; BatchNorm channel = c*N + n (models_gcn.py:47).
  * =============================================================================================================== */
 int twog_gcn_max_nodes(void);
+/* The launch geometry the kernels below use for (n_frames, n_nodes): out = {grid (workgroups), frames a workgroup takes per
+ * trip of its loop, dynamic LDS bytes, variant}. Host arithmetic only -- no GPU call; the launchers take their grid, group size
+ * and LDS size from the same code, so the answer is what is launched. A workgroup makes ceil(ceil(n_frames / out[1]) / grid)
+ * trips (embed1: rows = n_frames * n_nodes, 4 rows per workgroup and trip). variant: FUSED_FWD -> NT = ceil(n_nodes / 16), the
+ * kernel instance; ATTN2_BWD -> 1 when the M copy fits the LDS (n_nodes <= 48), else 0; otherwise 0. Returns 0, -1 for
+ * n_nodes outside 1 .. twog_gcn_max_nodes(), -2 for an unknown kernel, -3 when the kernel's LDS does not fit. */
+#define TWOG_GCN_PLAN_FUSED_FWD 0   /* twog_gcn_fused_fwd */
+#define TWOG_GCN_PLAN_ATTN2_FWD 1   /* twog_gcn_attn2_fwd */
+#define TWOG_GCN_PLAN_ATTN2_BWD 2   /* twog_gcn_attn2_bwd (grid = twog_gcn_attn2_bwd_blocks) */
+#define TWOG_GCN_PLAN_EMBED1_FWD 3  /* twog_gcn_embed1_fwd */
+#define TWOG_GCN_PLAN_ATTN_FWD 4    /* twog_gcn_attn_fwd */
+#define TWOG_GCN_PLAN_ATTN_BWD 5    /* twog_gcn_attn_bwd */
+int twog_gcn_launch_plan(int kernel, int n_frames, int n_nodes, int out[4]);
 /* norm_data train-mode batch statistics (models_gcn.py:43-49): per-block fp64 partial sums
  * partials[n_blocks][2][4N] (sum, sum of squares; channel order). */
 int twog_bn_stats(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, double* partials, int n_blocks,

@@ -161,11 +161,12 @@ class FakeKernels:
                 sums, nf = stats_reduce(sums, nf)
             mean = sums[:4 * N] / nf
             var = sums[4 * N:] / nf - mean * mean
-            running_mean.mul_(0.9).add_(0.1 * mean.float())
-            running_var.mul_(0.9).add_(0.1 * (var * nf / max(nf - 1, 1)).float())
+            dt = gamma.dtype   # fp32 as the kernel; fp64 operands run the whole specification in fp64
+            running_mean.mul_(0.9).add_(0.1 * mean.to(dt))
+            running_var.mul_(0.9).add_(0.1 * (var * nf / max(nf - 1, 1)).to(dt))
             if num_batches_tracked is not None:
                 num_batches_tracked.add_(1)
-            mean, var = mean.float(), var.float()
+            mean, var = mean.to(dt), var.to(dt)
         else:
             mean, var = running_mean.clone(), running_var.clone()
         invstd = 1.0 / torch.sqrt(var + 1e-5)
