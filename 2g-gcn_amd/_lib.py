@@ -280,6 +280,9 @@ SIGNATURES = {
     'twog_mtl_weight_bwd': [C.POINTER(Mtl), _P, _P, _P, _P, _P, _I, _P],
     'twog_predict_labels': [_P, _I, _I, _I, _I, _I, _I, _P, _P],
     'twog_f1_at_k': [_P, _P, _I, _I, _I, C.c_double, _L, _I, _P, _P, _P, _P],
+    'twog_eval_update': [_P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P],
+    'twog_confusion_counts': [_P, _P, _L, _I, _P, _P, _P],
+    'twog_eval_limits': [C.POINTER(C.c_int), C.POINTER(C.c_int)],
 }
 
 _lib = None

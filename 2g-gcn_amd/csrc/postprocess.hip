@@ -8,6 +8,17 @@
 
 namespace {
 
+// first argmax_c p[c * stride]. Strict comparison: ties keep the first index, like np.argmax
+__device__ __forceinline__ int first_argmax(const float* p, int C, int64_t stride) {
+    float best = p[0];
+    int arg = 0;
+    for (int c = 1; c < C; ++c) {
+        const float v = p[(int64_t)c * stride];
+        if (v > best) { best = v; arg = c; }
+    }
+    return arg;
+}
+
 // labels[b][t'][e] = first argmax_c logp[b][c][min(t' / ds, T - 1)][e]
 __global__ __launch_bounds__(256) void predict_labels_kernel(const float* logp, int bs, int C, int T, int E, int ds,
                                                              int T_out, long long* labels) {
@@ -17,16 +28,79 @@ __global__ __launch_bounds__(256) void predict_labels_kernel(const float* logp, 
         const int64_t bt = i / E;
         const int tp = (int)(bt % T_out), b = (int)(bt / T_out);
         const int t = min(tp / ds, T - 1);
-        const float* p = logp + ((int64_t)b * C * T + t) * E + e;
-        float best = p[0];
-        int arg = 0;
-        for (int c = 1; c < C; ++c) {
-            const float v = p[(int64_t)c * T * E];
-            if (v > best) { best = v; arg = c; }  // strict: ties keep the first index, like np.argmax
-        }
-        labels[i] = arg;
+        labels[i] = first_argmax(logp + ((int64_t)b * C * T + t) * E + e, C, (int64_t)T * E);
     }
 }
+
+// ---- confusion counts (predict.py:205-226 feeds sklearn with host copies of every label; here the C x C counts are
+// built where the labels are). Every workgroup keeps a private histogram of 32-bit counters in LDS: hist[C * C] cells
+// (row = true class, column = predicted class) followed by the two flag counters. A workgroup sees at most
+// n / gridDim.x + 256 positions, far below 2^32 for any tensor that fits the device. The flush adds the non-zero
+// cells to the int64 totals with integer atomics, so the totals do not depend on the arrival order.
+constexpr int EVAL_MAX_CLASSES = 64;   // 64 * 64 * 4 B = 16 KB of LDS
+constexpr int EVAL_GRID_CAP = 1024;    // workgroups of 256: every one flushes up to C * C cells
+
+__device__ __forceinline__ void count_position(unsigned* hist, int C, long long tgt, long long pred) {
+    if (tgt == -1) return;                                   // ignored (predict.py:210-211)
+    if (tgt < -1 || tgt >= C || pred < 0 || pred >= C) { atomicAdd(&hist[C * C], 1u); return; }
+    atomicAdd(&hist[(int)tgt * C + (int)pred], 1u);
+}
+
+__device__ __forceinline__ void clear_hist(unsigned* hist, int C) {
+    for (int k = threadIdx.x; k < C * C + 2; k += 256) hist[k] = 0u;
+    __syncthreads();
+}
+
+__device__ __forceinline__ void flush_hist(const unsigned* hist, int C, long long* counts, long long* flags) {
+    __syncthreads();
+    for (int k = threadIdx.x; k < C * C + 2; k += 256) {
+        const unsigned v = hist[k];
+        if (v == 0u) continue;
+        long long* dst = k < C * C ? counts + k : flags + (k - C * C);
+        atomicAdd(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)v);
+    }
+}
+
+// One pass over one model output: position (b, s, e) evaluates target step t' = step_index[b][s] (or s), whose label is
+// the argmax at source step min(t' / ds, T - 1). t' < 0 is padding (label 0, target -1: what the reference's -100 /
+// -1.0 rubbish rows give after argmax); t' >= T_tgt is counted in flags[1] and never read.
+__global__ __launch_bounds__(256) void eval_update_kernel(const float* logp, int bs, int C, int T, int E, int ds,
+                                                          const long long* target, int T_tgt, const int* step_index,
+                                                          int S, long long* counts, long long* flags,
+                                                          long long* labels_out, long long* targets_out) {
+    extern __shared__ unsigned hist[];
+    clear_hist(hist, C);
+    const int64_t n = (int64_t)bs * S * E;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int e = (int)(i % E);
+        const int64_t bsx = i / E;
+        const int s = (int)(bsx % S), b = (int)(bsx / S);
+        const int tp = step_index ? step_index[(int64_t)b * S + s] : s;
+        long long label = 0, tgt = -1;
+        if (tp >= T_tgt) {
+            atomicAdd(&hist[C * C + 1], 1u);
+        } else if (tp >= 0) {
+            const int t = min(tp / ds, T - 1);
+            label = first_argmax(logp + ((int64_t)b * C * T + t) * E + e, C, (int64_t)T * E);
+            tgt = target[((int64_t)b * T_tgt + tp) * E + e];
+            count_position(hist, C, tgt, label);
+        }
+        if (labels_out) labels_out[i] = label;
+        if (targets_out) targets_out[i] = tgt;
+    }
+    flush_hist(hist, C, counts, flags);
+}
+
+__global__ __launch_bounds__(256) void confusion_counts_kernel(const long long* y_true, const long long* y_pred,
+                                                               int64_t n, int C, long long* counts, long long* flags) {
+    extern __shared__ unsigned hist[];
+    clear_hist(hist, C);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        count_position(hist, C, y_true[i], y_pred[i]);
+    flush_hist(hist, C, counts, flags);
+}
+
+inline int eval_grid(int64_t n) { return (int)((n + 255) / 256 < EVAL_GRID_CAP ? (n + 255) / 256 : EVAL_GRID_CAP); }
 
 // One thread per sequence. Steps whose target equals the ignore value are dropped from BOTH sequences before the
 // run-length encoding (metrics.py:75-77). `used` is a per-sequence scratch row of n_steps bytes.
@@ -117,6 +191,42 @@ extern "C" int twog_f1_at_k(const int64_t* y_true, const int64_t* y_pred, int n_
     hipLaunchKernelGGL(f1_at_k_kernel, dim3((n_seq + 63) / 64), dim3(64), 0, (hipStream_t)stream,
                        reinterpret_cast<const long long*>(y_true), reinterpret_cast<const long long*>(y_pred), n_seq,
                        n_steps, num_classes, overlap, (long long)ignore_value, use_ignore, scratch, f1, valid);
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int twog_eval_limits(int* max_classes, int* positions_per_trip) {
+    if (max_classes) *max_classes = EVAL_MAX_CLASSES;
+    if (positions_per_trip) *positions_per_trip = EVAL_GRID_CAP * 256;
+    return 0;
+}
+
+extern "C" int twog_eval_update(const float* logp, int bs, int n_classes, int T, int E, int downsampling,
+                                const int64_t* target, int T_tgt, const int32_t* step_index, int S, int64_t* counts,
+                                int64_t* flags, int64_t* labels_out, int64_t* targets_out, void* stream) {
+    if (bs < 0 || n_classes < 1 || T < 1 || E < 1 || downsampling < 1 || T_tgt < 0 || (step_index && S < 0)) return -1;
+    if (n_classes > EVAL_MAX_CLASSES) return -2;
+    const int steps = step_index ? S : T_tgt;
+    const int64_t n = (int64_t)bs * steps * E;
+    if (n == 0) return 0;
+    const size_t lds = ((size_t)n_classes * n_classes + 2) * sizeof(unsigned);
+    hipLaunchKernelGGL(eval_update_kernel, dim3(eval_grid(n)), dim3(256), lds, (hipStream_t)stream, logp, bs, n_classes,
+                       T, E, downsampling, reinterpret_cast<const long long*>(target), T_tgt, step_index, steps,
+                       reinterpret_cast<long long*>(counts), reinterpret_cast<long long*>(flags),
+                       reinterpret_cast<long long*>(labels_out), reinterpret_cast<long long*>(targets_out));
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int twog_confusion_counts(const int64_t* y_true, const int64_t* y_pred, int64_t n, int n_classes,
+                                     int64_t* counts, int64_t* flags, void* stream) {
+    if (n < 0 || n_classes < 1) return -1;
+    if (n_classes > EVAL_MAX_CLASSES) return -2;
+    if (n == 0) return 0;
+    const size_t lds = ((size_t)n_classes * n_classes + 2) * sizeof(unsigned);
+    hipLaunchKernelGGL(confusion_counts_kernel, dim3(eval_grid(n)), dim3(256), lds, (hipStream_t)stream,
+                       reinterpret_cast<const long long*>(y_true), reinterpret_cast<const long long*>(y_pred), n,
+                       n_classes, reinterpret_cast<long long*>(counts), reinterpret_cast<long long*>(flags));
     TWOG_CHECK_LAUNCH();
     return 0;
 }

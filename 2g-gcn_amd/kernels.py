@@ -1383,6 +1383,50 @@ class HipKernels:
                                           valid.data_ptr(), self._stream()), 'twog_f1_at_k')
         return f1, valid
 
+    def eval_limits(self):
+        """(largest class count of eval_update / confusion_counts, positions one trip of their capped grid covers)."""
+        max_classes, per_trip = C.c_int(0), C.c_int(0)
+        self._check(self.lib.twog_eval_limits(C.byref(max_classes), C.byref(per_trip)), 'twog_eval_limits')
+        return max_classes.value, per_trip.value
+
+    def eval_update(self, logp, downsampling, target, step_index, counts, flags, want_labels=False):
+        """One pass over one (bs, C, T, E) output: ADDS the (true, predicted) pairs of the evaluated positions to counts
+        int64 (C, C) and the two error counters to flags int64 (2,), in place. target int64 (bs, T_tgt, E), -1 ignored;
+        step_index int32 (bs, S) or None. With want_labels returns (labels, targets) int64 (bs, S or T_tgt, E)."""
+        assert logp.dim() == 4 and logp.dtype == torch.float32
+        assert target.dim() == 3 and target.dtype == torch.int64 and target.shape[0] == logp.shape[0] \
+            and target.shape[2] == logp.shape[3], (tuple(target.shape), tuple(logp.shape))
+        logp, target = logp.contiguous(), target.contiguous()
+        bs, Cn, T, E = logp.shape
+        T_tgt = target.shape[1]
+        assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == Cn * Cn
+        assert flags.dtype == torch.int64 and flags.is_contiguous() and flags.numel() == 2
+        S = T_tgt
+        if step_index is not None:
+            assert step_index.dim() == 2 and step_index.dtype == torch.int32 and step_index.shape[0] == bs
+            step_index = step_index.contiguous()
+            S = step_index.shape[1]
+        labels = targets = None
+        if want_labels:
+            labels = torch.empty(bs, S, E, dtype=torch.int64, device=logp.device)
+            targets = torch.empty(bs, S, E, dtype=torch.int64, device=logp.device)
+        self._check(self.lib.twog_eval_update(logp.data_ptr(), bs, Cn, T, E, int(downsampling), target.data_ptr(), T_tgt,
+                                              _ptr(step_index), S, counts.data_ptr(), flags.data_ptr(), _ptr(labels),
+                                              _ptr(targets), self._stream()), 'twog_eval_update')
+        return (labels, targets) if want_labels else None
+
+    def confusion_counts(self, y_true, y_pred, num_classes, counts, flags):
+        """ADDS the (true, predicted) pairs of two int64 label tensors of equal size to counts int64 (C, C), in place;
+        true == -1 is ignored, any other label outside [0, C) is counted in flags[0]."""
+        y_true, y_pred = y_true.to(torch.int64).contiguous(), y_pred.to(torch.int64).contiguous()
+        assert y_true.numel() == y_pred.numel()
+        assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == num_classes * num_classes
+        assert flags.dtype == torch.int64 and flags.is_contiguous() and flags.numel() == 2
+        self._check(self.lib.twog_confusion_counts(y_true.data_ptr(), y_pred.data_ptr(), y_true.numel(), int(num_classes),
+                                                   counts.data_ptr(), flags.data_ptr(), self._stream()),
+                    'twog_confusion_counts')
+        return counts
+
 
 _backend = None
 

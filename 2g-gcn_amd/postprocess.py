@@ -5,9 +5,17 @@ downsampling factor (:64-70), `process_output`'s argmax (:186-202) and `pyrutils
 `evaluate_f1_at_k` (predict.py:229-246). The reference copies every (bs, C, T, E) log-probability tensor to the host and
 does these in numpy; here the labels and the per-sequence F1@k are computed by HIP kernels and only the final scalar
 (or the int64 labels, C x smaller than the log-probabilities) crosses PCIe.
+
+The frame-wise half of the evaluation is here too: `evaluate_predictions` (predict.py:205-226: micro / macro precision,
+recall and F1, the per-class report), the Bimanual 15-fps fix-up `downsample_bad_bimanual_videos` (:136-156) and
+`summarize_frames_into_segments` (:159-183). The device builds C x C confusion counts (twog_eval_update,
+twog_confusion_counts); every metric is a few hundred fp64 divisions on those integers, done on the host in numpy with
+scikit-learn's semantics, so scikit-learn itself is not needed. `EvaluationAccumulator` keeps the counts and the F1@k
+sums on the device over a whole test set and merges over ranks by a sum.
 """
 import numpy as np
 import torch
+import torch.distributed as dist
 
 from .kernels import get_kernels
 
@@ -70,3 +78,270 @@ def evaluate_f1_at_k(targets: dict, outputs: dict, num_subactivities, num_afford
         results[index] = f1_at_k(target.reshape(-1, steps), output.reshape(-1, steps), num_classes, overlap=overlap,
                                  ignore_value=-1.0)
     return results
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# metrics from confusion counts (host, fp64 numpy): counts[t, p] = positions of true class t predicted as class p
+def _ratio(num, den):
+    """num / den with scikit-learn's zero_division: a zero denominator gives 0."""
+    num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+    return np.divide(num, den, out=np.zeros(np.broadcast(num, den).shape), where=den != 0)
+
+
+def _class_sums(counts, labels=None):
+    """(tp, predicted, true) per class; for `labels` beyond the matrix the three are 0."""
+    counts = np.asarray(counts, dtype=np.int64)
+    tp, pred, true = np.diag(counts), counts.sum(0), counts.sum(1)
+    if labels is None:
+        return tp, pred, true
+    out = np.zeros((3, len(labels)), dtype=np.int64)
+    inside = [i for i, c in enumerate(labels) if c < counts.shape[0]]
+    for row, src in zip(out, (tp, pred, true)):
+        row[inside] = src[[labels[i] for i in inside]]
+    return out[0], out[1], out[2]
+
+
+def _prf(tp, pred, true):
+    return _ratio(tp, pred), _ratio(tp, true), _ratio(2 * tp, pred + true)  # F1 = 2 tp / (2 tp + fp + fn)
+
+
+def precision_recall_f1(counts, average: str) -> dict:
+    """scikit-learn's ``precision_recall_fscore_support(y_true, y_pred, average=average)`` (predict.py:224, labels=None)
+    from a count matrix. 'micro' is over all counted positions; 'macro' is the plain mean over the classes PRESENT in
+    the targets or the predictions, not over range(C). With nothing counted micro is 0.0 and macro is NaN: that is what
+    scikit-learn 1.7.2 returns (the mean of no classes), other versions may differ; golden G15 pins it."""
+    tp, pred, true = _class_sums(counts)
+    if average == 'micro':
+        p, r, f = _prf(tp.sum(), pred.sum(), true.sum())
+    elif average == 'macro':
+        present = (pred + true) > 0
+        p, r, f = (v[present].mean() if present.any() else float('nan') for v in _prf(tp, pred, true))
+    else:
+        raise ValueError(f'average must be micro or macro, not {average!r}')
+    return {'precision': float(p), 'recall': float(r), 'f1': float(f)}
+
+
+def classification_report(counts, target_names, digits: int = 4, output_dict: bool = False):
+    """scikit-learn's ``classification_report(y_true, y_pred, labels=range(len(target_names)), target_names=...)``
+    (predict.py:220-222) from a count matrix, which may hold more classes than there are names. One row per name, then
+    'accuracy' when the names cover every class present in the targets or predictions ('micro avg' otherwise), 'macro avg'
+    (plain mean over the named classes) and 'weighted avg' (weights = support; plain mean when every support is 0)."""
+    names = [str(n) for n in target_names]
+    labels = list(range(len(names)))
+    tp, pred, true = _class_sums(counts, labels)
+    p, r, f = _prf(tp, pred, true)
+    rows = {n: {'precision': float(p[i]), 'recall': float(r[i]), 'f1-score': float(f[i]), 'support': int(true[i])}
+            for i, n in enumerate(names)}
+    all_tp, all_pred, all_true = _class_sums(counts)
+    covered = not ((all_pred + all_true)[len(labels):] > 0).any()
+    support = int(true.sum())
+    mp, mr, mf = _prf(tp.sum(), pred.sum(), true.sum())
+    if covered:
+        rows['accuracy'] = float(mf)
+    else:
+        rows['micro avg'] = {'precision': float(mp), 'recall': float(mr), 'f1-score': float(mf), 'support': support}
+    mean = lambda v, w=None: float(np.average(v, weights=w)) if len(v) else float('nan')
+    rows['macro avg'] = {'precision': mean(p), 'recall': mean(r), 'f1-score': mean(f), 'support': support}
+    w = true if support > 0 else None
+    rows['weighted avg'] = {'precision': mean(p, w), 'recall': mean(r, w), 'f1-score': mean(f, w), 'support': support}
+    if output_dict:
+        return rows
+    width = max([len(n) for n in names] + [len('weighted avg')])
+    head = ' ' * width + ''.join(f'{h:>{digits + 6}}' for h in ('precision', 'recall', 'f1-score', 'support'))
+    lines = [head, '']
+    fmt = lambda name, v: (f'{name:>{width}}' + ''.join(f'{v[k]:>{digits + 6}.{digits}f}' for k in ('precision', 'recall', 'f1-score'))
+                           + f'{v["support"]:>{digits + 6}d}')
+    lines += [fmt(n, rows[n]) for n in names] + ['']
+    if covered:
+        lines.append(f'{"accuracy":>{width}}' + ' ' * (2 * (digits + 6)) + f'{rows["accuracy"]:>{digits + 6}.{digits}f}'
+                     + f'{support:>{digits + 6}d}')
+    else:
+        lines.append(fmt('micro avg', rows['micro avg']))
+    lines += [fmt('macro avg', rows['macro avg']), fmt('weighted avg', rows['weighted avg']), '']
+    return '\n'.join(lines)
+
+
+def _check_flags(name, flags):
+    bad_target, bad_step = int(flags[0]), int(flags[1])
+    if bad_target:
+        raise ValueError(f'output {name!r}: {bad_target} evaluated positions have a label outside [-1, num_classes)')
+    if bad_step:
+        raise ValueError(f'output {name!r}: {bad_step} evaluated positions have a step_index entry beyond the last target step')
+
+
+def evaluate_predictions(targets: dict, outputs: dict, print_report: bool = True, subactivity_names=None,
+                         affordance_names=None) -> dict:
+    """predict.py:205-226: {index: labels (N, T) or (N, T, E)} (device tensors, as `process_output` returns them; -1
+    targets ignored) -> {f'{index}-micro': {'precision', 'recall', 'f1'}, f'{index}-macro': ...}. The confusion counts
+    come from twog_confusion_counts, the numbers from `precision_recall_f1`; with `print_report` the per-class table of
+    `classification_report` is printed under the reference's headings."""
+    K = get_kernels()
+    results = {}
+    for index, target in sorted(targets.items()):
+        output = torch.as_tensor(outputs[index])
+        target = torch.as_tensor(target).to(output.device)
+        names = affordance_names if 'affordance' in str(index) else subactivity_names
+        # the class count is the largest label seen (labels=None in predict.py:224), at least the number of names
+        n_classes = max(int(max(target.max(), output.max())) + 1 if target.numel() else 1, len(names) if names else 1)
+        state = K.zeros(n_classes * n_classes + 2, dtype=torch.int64, device=output.device)
+        counts, flags = state[:-2].view(n_classes, n_classes), state[-2:]
+        K.confusion_counts(target.reshape(-1), output.reshape(-1), n_classes, counts, flags)
+        state = state.cpu().numpy()
+        _check_flags(index, state[-2:])
+        counts = state[:-2].reshape(n_classes, n_classes)
+        if print_report:
+            problem_type = 'Recognition' if 'recognition' in str(index) else 'Prediction'
+            problem_class = 'Affordance' if 'affordance' in str(index) else 'Sub-activity'
+            print(f'{problem_class} {problem_type}')
+            print(classification_report(counts, names if names else range(n_classes), digits=4))
+        for average in ('micro', 'macro'):
+            results[f'{index}-{average}'] = precision_recall_f1(counts, average)
+    return results
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# which target steps are evaluated: step_index (N, S) int32, -1 = padding
+def half_rate_step_index(T_tgt: int, is_15fps, device=None) -> torch.Tensor:
+    """`downsample_bad_bimanual_videos` (predict.py:136-156) as a step index (N, T_tgt): clips flagged in `is_15fps`
+    evaluate steps 1, 3, 5, ... (T_tgt // 2 of them) and pad the rest with -1; the other clips evaluate 0 .. T_tgt - 1."""
+    flagged = np.asarray(is_15fps, dtype=bool).reshape(-1)
+    index = np.tile(np.arange(T_tgt, dtype=np.int32), (flagged.size, 1))
+    half = np.full(T_tgt, -1, dtype=np.int32)
+    half[:T_tgt // 2] = np.arange(1, T_tgt, 2, dtype=np.int32)
+    index[flagged] = half
+    return torch.from_numpy(index).to(device) if device is not None else torch.from_numpy(index)
+
+
+def segment_step_index(segment_starts, device=None) -> torch.Tensor:
+    """`summarize_frames_into_segments` (predict.py:159-183) as a step index (N, longest list): clip v evaluates the
+    first frame of each of its segments, `segment_starts[v]`, and pads with -1."""
+    width = max((len(s) for s in segment_starts), default=0)
+    index = np.full((len(segment_starts), width), -1, dtype=np.int32)
+    for row, starts in zip(index, segment_starts):
+        row[:len(starts)] = np.asarray(starts, dtype=np.int32)
+    return torch.from_numpy(index).to(device) if device is not None else torch.from_numpy(index)
+
+
+def _select_steps(labels: torch.Tensor, index: torch.Tensor, pad: int) -> torch.Tensor:
+    """labels (N, T) or (N, T, E) -> labels[v, index[v, s]] with `pad` where index < 0."""
+    index = index.to(labels.device).long()
+    idx = index.clamp(min=0)
+    keep = index >= 0
+    if labels.ndim == 3:
+        idx, keep = idx.unsqueeze(-1).expand(-1, -1, labels.shape[2]), keep.unsqueeze(-1)
+    return torch.where(keep, torch.gather(labels, 1, idx), torch.full_like(labels[:1, :1], pad))
+
+
+def downsample_bad_bimanual_videos(outputs: dict, targets: dict, is_15fps):
+    """predict.py:136-156 on the LABELS of `process_output` ({index: (N, T) or (N, T, E)}): the clips flagged in
+    `is_15fps` keep every second step from step 1; the freed tail is padded with prediction 0 (the argmax of the
+    reference's -100 rows) and target -1. Returns (outputs, targets) as new dicts."""
+    new_out, new_tgt = {}, {}
+    for index, target in targets.items():
+        step_index = half_rate_step_index(target.shape[1], is_15fps)
+        new_out[index] = _select_steps(outputs[index], step_index, 0)
+        new_tgt[index] = _select_steps(target, step_index, -1)
+    return new_out, new_tgt
+
+
+def summarize_frames_into_segments(labels: dict, segment_starts, is_ground_truth: bool) -> dict:
+    """predict.py:159-183 on the LABELS of `process_output`: clip v keeps the first frame of each of its segments,
+    padded to the longest list with -1 for targets and with 0 for predictions (the argmax of the reference's -1.0
+    rows)."""
+    step_index = segment_step_index(segment_starts)
+    return {index: _select_steps(t, step_index, -1 if is_ground_truth else 0) for index, t in labels.items()}
+
+
+class EvaluationAccumulator:
+    """Running evaluation of a test set on the device: per output name the C x C confusion counts (row = true class,
+    column = predicted class), the two error counters of twog_eval_update and, per overlap, the sums of the per-sequence
+    F1@k and of the valid sequences. `update` issues kernels only -- no device-to-host copy, no synchronisation --
+    `all_reduce` sums the state over the ranks of a sharded test set and `result` makes the one copy to the host.
+
+    names: the evaluated outputs in model order (the last `len(names)` outputs and targets of a batch are used, like
+    predict.py:61-63). num_classes: one int for all of them, or one per name."""
+
+    def __init__(self, names, num_classes, downsampling: int = 1, overlaps=(0.1, 0.25, 0.5)):
+        self.names = list(names)
+        self.num_classes = [int(num_classes)] * len(self.names) if np.ndim(num_classes) == 0 else [int(c) for c in num_classes]
+        if len(self.num_classes) != len(self.names):
+            raise ValueError('num_classes must be one int or one per name')
+        self.downsampling = max(1, int(downsampling))
+        self.overlaps = tuple(float(o) for o in overlaps)
+        self._state = None   # 8-byte words: per name [C * C counts, 2 flags] as int64, then per name [f1 sums, valid sums] as fp64
+
+    def _allocate(self, device):
+        n_int = sum(c * c + 2 for c in self.num_classes)
+        n_ov = len(self.overlaps)
+        self._state = get_kernels().zeros(n_int + 2 * n_ov * len(self.names), dtype=torch.int64, device=device)
+        self._ints = self._state[:n_int]
+        self._floats = self._state[n_int:].view(torch.float64)
+        self._counts, self._flags, self._f1, self._valid = [], [], [], []
+        at = 0
+        for i, c in enumerate(self.num_classes):
+            self._counts.append(self._ints[at:at + c * c].view(c, c))
+            self._flags.append(self._ints[at + c * c:at + c * c + 2])
+            at += c * c + 2
+            self._f1.append(self._floats[2 * n_ov * i:2 * n_ov * i + n_ov])
+            self._valid.append(self._floats[2 * n_ov * i + n_ov:2 * n_ov * (i + 1)])
+
+    def update(self, outputs, targets, step_index=None):
+        """One batch: outputs / targets are the model's lists (the last len(names) are used), output (bs, C, T, E)
+        log-probabilities, target (bs, T_tgt, E) labels on the same device; step_index (bs, S) from
+        `half_rate_step_index` / `segment_step_index`, already on the device (a host tensor would be copied, which
+        synchronises)."""
+        K = get_kernels()
+        n = len(self.names)
+        outputs, targets = list(outputs)[-n:], list(targets)[-n:]
+        if len(outputs) != n or len(targets) != n:
+            raise ValueError(f'{n} outputs and targets expected')
+        for i, (out, tgt) in enumerate(zip(outputs, targets)):
+            if out.ndim != 4:
+                raise RuntimeError(f'Number of dimensions for output is {out.ndim}')  # predict.py:66-67
+            if out.shape[1] != self.num_classes[i]:
+                raise ValueError(f'output {self.names[i]!r} has {out.shape[1]} classes, not {self.num_classes[i]}')
+            if self._state is None:
+                self._allocate(out.device)
+            if step_index is not None:
+                step_index = step_index.to(device=out.device, dtype=torch.int32)
+            labels, kept = K.eval_update(out, self.downsampling, tgt.to(torch.int64), step_index, self._counts[i],
+                                         self._flags[i], want_labels=True)
+            # f1_at_k wants sequence-major (n_seq, n_steps): the transposition of evaluate_f1_at_k
+            steps = labels.shape[1]
+            labels, kept = labels.transpose(1, 2).reshape(-1, steps), kept.transpose(1, 2).reshape(-1, steps)
+            for j, overlap in enumerate(self.overlaps):
+                f1, valid = K.f1_at_k(kept, labels, self.num_classes[i], overlap, -1)
+                self._f1[i][j:j + 1].add_(f1.sum(dtype=torch.float64))
+                self._valid[i][j:j + 1].add_(valid.sum(dtype=torch.float64))
+
+    def all_reduce(self, group=None):
+        """Sum the state over the ranks of `group` (every rank evaluated its own shard of the clips). A process without
+        an initialised process group is the only rank: nothing to do."""
+        if self._state is None:
+            raise RuntimeError('all_reduce before the first update: the state has no device yet')
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(self._ints, op=dist.ReduceOp.SUM, group=group)
+            dist.all_reduce(self._floats, op=dist.ReduceOp.SUM, group=group)
+
+    def result(self) -> dict:
+        """{name: {'micro': {...}, 'macro': {...}, 'report': {...}, 'f1@k': {overlap: value}, 'confusion': ndarray}}.
+        Raises ValueError if a target was outside [-1, C) or a step_index entry pointed beyond the targets. F1@k is
+        NaN when no sequence had a counted step (the reference divides by zero there)."""
+        if self._state is None:
+            raise RuntimeError('result before the first update')
+        host = self._state.cpu().numpy()   # the one device-to-host copy
+        n_int = self._ints.numel()
+        ints, floats = host[:n_int], host[n_int:].view(np.float64)
+        n_ov = len(self.overlaps)
+        res, at = {}, 0
+        for i, (name, c) in enumerate(zip(self.names, self.num_classes)):
+            counts = ints[at:at + c * c].reshape(c, c).copy()
+            _check_flags(name, ints[at + c * c:at + c * c + 2])
+            at += c * c + 2
+            f1, valid = floats[2 * n_ov * i:2 * n_ov * i + n_ov], floats[2 * n_ov * i + n_ov:2 * n_ov * (i + 1)]
+            res[name] = {'micro': precision_recall_f1(counts, 'micro'), 'macro': precision_recall_f1(counts, 'macro'),
+                         'report': classification_report(counts, range(c), output_dict=True),
+                         'f1@k': {ov: (float(f1[j] / valid[j]) if valid[j] > 0 else float('nan'))
+                                  for j, ov in enumerate(self.overlaps)},
+                         'confusion': counts}
+        return res

@@ -787,11 +787,32 @@ int twog_mtl_weight_bwd(const twog_mtl_t* spec, const float* losses, const float
  * twog_f1_at_k: pyrutils/metrics.py:7-81. y_true / y_pred int64 [n_seq][n_steps]; steps with y_true == ignore_value
  *   are dropped from both (use_ignore); f1[s] = F1@overlap of sequence s, valid[s] = 0 for sequences left empty (the
  *   reference skips them); the batch metric is sum(f1) / sum(valid). scratch: n_seq * n_steps bytes.
+ * twog_eval_update: predict.py:205-226 (evaluate_predictions: the label pairs sklearn's precision_recall_fscore_support /
+ *   classification_report count) fused with the label step above, plus the index selection of :136-156
+ *   (downsample_bad_bimanual_videos) and :159-183 (summarize_frames_into_segments). One pass over one output, no labels
+ *   tensor in between. logp [bs][C][T][E]; target int64 [bs][T_tgt][E] (-1 = ignored); step_index int32 [bs][S] or
+ *   NULL. Position (b, s, e), s < S (s < T_tgt without step_index), evaluates t' = step_index[b][s] (t' = s):
+ *   t' < 0 is padding (nothing counted, label 0 / target -1 in the optional outputs); otherwise label = argmax_c
+ *   logp[b][c][min(t' / downsampling, T - 1)][e] against target[b][t'][e]. ADDS to counts int64 [C][C] (row = true,
+ *   column = predicted) and to flags int64 [2]: [0] positions whose target is outside [-1, C), [1] positions whose
+ *   step_index entry is >= T_tgt; neither kind is counted, the second is never read. labels_out / targets_out int64
+ *   [bs][S or T_tgt][E] or NULL. Integer atomics: counts is bit-identical from run to run. Returns -2 for
+ *   C > the max_classes of twog_eval_limits (a C x C histogram of 32-bit counters per workgroup in LDS).
+ * twog_confusion_counts: the same histogram over two int64 label arrays of n elements (predict.py:208-211, :224);
+ *   a prediction outside [0, C) whose target is not -1 is counted in flags[0] too.
+ * twog_eval_limits: max_classes, and the positions one trip of the capped grid covers (more than that and the
+ *   grid-stride loop of the two kernels above runs again).
  * =============================================================================================================== */
 int twog_predict_labels(const float* logp, int bs, int n_classes, int T, int E, int downsampling, int T_out,
                         int64_t* labels, void* stream);
 int twog_f1_at_k(const int64_t* y_true, const int64_t* y_pred, int n_seq, int n_steps, int num_classes, double overlap,
                  int64_t ignore_value, int use_ignore, unsigned char* scratch, float* f1, float* valid, void* stream);
+int twog_eval_update(const float* logp, int bs, int n_classes, int T, int E, int downsampling, const int64_t* target,
+                     int T_tgt, const int32_t* step_index, int S, int64_t* counts, int64_t* flags, int64_t* labels_out,
+                     int64_t* targets_out, void* stream);
+int twog_confusion_counts(const int64_t* y_true, const int64_t* y_pred, int64_t n, int n_classes, int64_t* counts,
+                          int64_t* flags, void* stream);
+int twog_eval_limits(int* max_classes, int* positions_per_trip);
 
 #ifdef __cplusplus
 }
