@@ -210,6 +210,7 @@ SIGNATURES = {
     'twog_gcn_embed1_fwd': [_P, _L, _I, _I, _P, _P, _P, _P, _P],
     'twog_gcn_fused_fwd': [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     'twog_gcn_embed1_bwd': [_P, _L, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
+    'twog_gcn_input_bwd': [_P, _L, _I, _I, _I, _L, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P],
     'twog_gcn_attn_fwd': [_P, _P, _I, _I, _P, _P, _P],
     'twog_gcn_attn_bwd': [_P, _P, _P, _P, _I, _I, _P, _P, _P],
     'twog_gcn_attn2_fwd': [_P, _P, _I, _I, _P, _P, _P],

@@ -247,6 +247,97 @@ __global__ __launch_bounds__(1024) void embed1_bwd_final_kernel(const float* par
     }
 }
 
+// sum over the 16 lanes that share lane / 16 (DPP row rotations inside each 16-lane row, as sum16 of geo_fused.hip: VALU
+// only, every lane ends up with the same bits)
+template <int CTRL>
+__device__ __forceinline__ float row_ror(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float row16_sum(float v) {
+    v += row_ror<0x128>(v);
+    v += row_ror<0x124>(v);
+    v += row_ror<0x122>(v);
+    v += row_ror<0x121>(v);
+    return v;
+}
+
+// Gradient of the geometry input (vhoi/models.py:636-639 split, models_gcn.py:45-59): per (frame, node)
+//   dx^[c] = sum_j de1[j] W1[j][c]                                   (de1 already ReLU-masked)
+//   eval : dx[c] = a[ch] dx^[c]                                      (ch = c*N + n, a = gamma * invstd)
+//   train: dx[c] = a[ch] (dx^[c] - dbeta[ch]/M - x_n[c] dgamma[ch]/M), x_n = (x - mean) invstd, M = n_frames
+// written to human 0's geometry columns; the geometry columns of the humans 1 .. H-1 (which the forward pass never
+// reads) get zeros from the same launch. Streaming: 16 lanes take one node's 256 B of de1 as one float4 each (a wave
+// instruction reads 1 KB contiguous), four nodes per group in flight; the 16 partial dot products meet through DPP;
+// lane 0 of the group reads x and writes dx as float4. Fixed summation order, no atomics: bit-reproducible.
+__global__ __launch_bounds__(256) void input_bwd_kernel(const float* x, int64_t fstride, int n_frames, int N, int H,
+                                                        int64_t hstride, const float* ab, const float* mean_invstd,
+                                                        const float* w1, const float* de1, const float* dgamma,
+                                                        const float* dbeta, int training, float* dx) {
+    // per memory position n*4 + c: a, mean, invstd, dbeta/M, dgamma/M
+    __shared__ __attribute__((aligned(16))) float s_p[5][4 * MAX_NODES];
+    const int nch = 4 * N;
+    for (int pos = threadIdx.x; pos < nch; pos += blockDim.x) {
+        const int ch = (pos & 3) * N + (pos >> 2);
+        s_p[0][pos] = ab[ch];
+        if (training) {
+            s_p[1][pos] = mean_invstd[ch];
+            s_p[2][pos] = mean_invstd[nch + ch];
+            s_p[3][pos] = dbeta[ch] / (float)n_frames;
+            s_p[4][pos] = dgamma[ch] / (float)n_frames;
+        }
+    }
+    const int lane = threadIdx.x & 63, q = lane & 15, grp = lane >> 4, wv = threadIdx.x >> 6;
+    float4 wr[4];  // rows 4q .. 4q+3 of W1 [64][4]
+#pragma unroll
+    for (int k = 0; k < 4; ++k) wr[k] = *reinterpret_cast<const float4*>(w1 + (4 * q + k) * 4);
+    __syncthreads();
+    const int64_t rows = (int64_t)n_frames * N;
+    for (int64_t base = ((int64_t)blockIdx.x * 4 + wv) * 16; base < rows; base += (int64_t)gridDim.x * 64) {
+        float4 d[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t r = base + u * 4 + grp;
+            d[u] = r < rows ? *reinterpret_cast<const float4*>(de1 + r * 64 + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float4 v = d[u];
+            float g0 = v.x * wr[0].x, g1 = v.x * wr[0].y, g2 = v.x * wr[0].z, g3 = v.x * wr[0].w;
+            g0 = fmaf(v.y, wr[1].x, g0); g1 = fmaf(v.y, wr[1].y, g1); g2 = fmaf(v.y, wr[1].z, g2); g3 = fmaf(v.y, wr[1].w, g3);
+            g0 = fmaf(v.z, wr[2].x, g0); g1 = fmaf(v.z, wr[2].y, g1); g2 = fmaf(v.z, wr[2].z, g2); g3 = fmaf(v.z, wr[2].w, g3);
+            g0 = fmaf(v.w, wr[3].x, g0); g1 = fmaf(v.w, wr[3].y, g1); g2 = fmaf(v.w, wr[3].z, g2); g3 = fmaf(v.w, wr[3].w, g3);
+            g0 = row16_sum(g0); g1 = row16_sum(g1); g2 = row16_sum(g2); g3 = row16_sum(g3);
+            const int64_t r = base + u * 4 + grp;
+            if (q == 0 && r < rows) {
+                const int f = (int)(r / N), n = (int)(r - (int64_t)f * N);
+                const float4 a = *reinterpret_cast<const float4*>(&s_p[0][n * 4]);
+                float4 o;
+                if (training) {
+                    const float4 xv = *reinterpret_cast<const float4*>(x + (int64_t)f * fstride + n * 4);
+                    const float4 mu = *reinterpret_cast<const float4*>(&s_p[1][n * 4]);
+                    const float4 is = *reinterpret_cast<const float4*>(&s_p[2][n * 4]);
+                    const float4 kb = *reinterpret_cast<const float4*>(&s_p[3][n * 4]);
+                    const float4 kg = *reinterpret_cast<const float4*>(&s_p[4][n * 4]);
+                    o.x = a.x * (g0 - kb.x - (xv.x - mu.x) * is.x * kg.x);
+                    o.y = a.y * (g1 - kb.y - (xv.y - mu.y) * is.y * kg.y);
+                    o.z = a.z * (g2 - kb.z - (xv.z - mu.z) * is.z * kg.z);
+                    o.w = a.w * (g3 - kb.w - (xv.w - mu.w) * is.w * kg.w);
+                } else {
+                    o = make_float4(a.x * g0, a.y * g1, a.z * g2, a.w * g3);
+                }
+                *reinterpret_cast<float4*>(dx + (int64_t)f * fstride + n * 4) = o;
+            }
+        }
+    }
+    // the other humans' geometry columns: zeros (one float4 per node)
+    const int64_t per_frame = (int64_t)(H - 1) * N, nz = per_frame * n_frames;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nz; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t f = i / per_frame, rem = i - f * per_frame;
+        const int h = 1 + (int)(rem / N), n = (int)(rem - (int64_t)(h - 1) * N);
+        *reinterpret_cast<float4*>(dx + f * fstride + h * hstride + n * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
 constexpr int LDQ = 132;  // 128 + 4: lane j's float4 reads land on banks 4j (mod 64) -> conflict-free b128
 constexpr int LDX = 68;   // 64 + 4
 
@@ -446,6 +537,25 @@ extern "C" int twog_gcn_embed1_bwd(const float* x_geo, int64_t frame_stride, int
     TWOG_CHECK_LAUNCH();
     hipLaunchKernelGGL(embed1_bwd_final_kernel, dim3((320 + 4 * n_nodes + 63) / 64), dim3(1024), 0, st, partials, n_blocks, 4 * n_nodes,
                        mean_invstd, dw1, db1, dgamma, dbeta);
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int twog_gcn_input_bwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, int n_humans,
+                                  int64_t human_stride, const float* ab, const float* mean_invstd, const float* w1,
+                                  const float* de1, const float* dgamma, const float* dbeta, int training,
+                                  float* dx_geo, int n_blocks, void* stream) {
+    if (n_nodes > MAX_NODES || n_nodes < 1) return -1;
+    if (!x_geo || !ab || !w1 || !de1 || !dx_geo || n_humans < 1 || n_blocks < 1 || n_frames < 0) return -2;
+    if (training && !(mean_invstd && dgamma && dbeta)) return -2;
+    // float4 accesses: 16-byte aligned geometry blocks, rows a whole number of float4 apart
+    if (((uintptr_t)x_geo | (uintptr_t)dx_geo | (uintptr_t)de1 | (uintptr_t)w1) & 15) return -2;
+    if ((frame_stride & 3) || (human_stride & 3) || human_stride < 4 * n_nodes ||
+        frame_stride < (int64_t)n_humans * human_stride) return -2;
+    if (n_frames == 0) return 0;
+    hipLaunchKernelGGL(input_bwd_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, x_geo, frame_stride,
+                       n_frames, n_nodes, n_humans, human_stride, ab, mean_invstd, w1, de1, dgamma, dbeta, training,
+                       dx_geo);
     TWOG_CHECK_LAUNCH();
     return 0;
 }

@@ -419,6 +419,26 @@ class HipKernels:
                                                  self._stream()), 'twog_gcn_embed1_bwd')
         return dw1, db1, dgamma, dbeta
 
+    @staticmethod
+    def input_bwd_blocks(n_rows):
+        """Workgroups of twog_gcn_input_bwd: 64 (frame, node) rows per workgroup and trip, at most 2048 workgroups."""
+        return max(1, min(2048, (n_rows + 63) // 64))
+
+    def gcn_input_bwd(self, x_human, n_nodes, ab, mean_invstd, w1, de1, dgamma, dbeta, training, grad_x_human):
+        """Writes the geometry columns of grad_x_human (same shape as x_human, contiguous): d loss / d x_human[b, t, 0, 2048:]
+        from the ReLU-masked de1, zeros for the other humans. Train mode needs the dgamma / dbeta of gcn_embed1_bwd (issued
+        before, on the same stream); eval mode takes None for them."""
+        ptr, fstride, nf = self._geo(x_human)
+        gptr, gstride, _ = self._geo(grad_x_human)
+        assert grad_x_human.shape == x_human.shape and gstride == fstride
+        bs, T, H, Fh = x_human.shape
+        assert Fh == 2048 + 4 * n_nodes and de1.is_contiguous() and w1.is_contiguous()
+        self._check(self.lib.twog_gcn_input_bwd(ptr, fstride, nf, n_nodes, H, Fh, ab.data_ptr(), _ptr(mean_invstd),
+                                                w1.data_ptr(), de1.data_ptr(), _ptr(dgamma), _ptr(dbeta), int(bool(training)),
+                                                gptr, self.input_bwd_blocks(nf * n_nodes), self._stream()),
+                    'twog_gcn_input_bwd')
+        return grad_x_human
+
     def gcn_attn_fwd(self, qk, x, n_frames, n_nodes):
         s = torch.empty(n_frames, n_nodes, n_nodes, dtype=torch.float32, device=qk.device)
         z = torch.empty(n_frames * n_nodes, 64, dtype=torch.float32, device=qk.device)

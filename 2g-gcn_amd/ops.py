@@ -1553,10 +1553,15 @@ def tggcn_forward(K, plan: Plan, P, x_human, x_objects, objects_mask, human_seg,
     return outputs, S
 
 
-def tggcn_backward(K, plan: Plan, P, S, x_human, x_objects, objects_mask, d_outputs, sinks=None):
+def tggcn_backward(K, plan: Plan, P, S, x_human, x_objects, objects_mask, d_outputs, sinks=None, input_grads=None,
+                   training=True):
     """Hand-derived backward pass. d_outputs: list aligned with the forward outputs (None = no gradient).
     Returns dict name -> gradient for every parameter used by the forward that has no entry in `sinks`
-    (see _Grads: gradients with a sink have been added into it)."""
+    (see _Grads: gradients with a sink have been added into it).
+    input_grads: None, or a dict with the keys 'x_human' and / or 'x_objects' -- the gradient with respect to each input
+    named there is computed and stored under its key (same shape as the input). `training`: the mode the forward pass ran
+    in (the BatchNorm of the GCN differentiates differently in the two); only read for 'x_human'. Without a key the pass
+    issues exactly the launches it issues with input_grads=None."""
     p = plan
     P = _Params(P)
     bs, T, H, O, N, h = p.bs, p.T, p.H, p.O, p.N, p.h
@@ -2023,6 +2028,23 @@ def tggcn_backward(K, plan: Plan, P, S, x_human, x_objects, objects_mask, d_outp
     if O > 0:
         dpre_o = K.relu_bwd(dOBJv[:, :h], OBJv[:, :h])
         _lin_w_grads(K, G, 'object_embedding_mlp.0.weight', 'object_embedding_mlp.0.bias', dpre_o, xo_in)
+    need_dxh = input_grads is not None and 'x_human' in input_grads
+    need_dxo = input_grads is not None and 'x_objects' in input_grads
+    if need_dxh or need_dxo:
+        # d x_human[..., :2048] = dpre_h W_human_embedding, d x_objects = dpre_o W_object_embedding: one grouped launch,
+        # C = the visual columns of the gradient (row stride F_h) / the whole object gradient. Every element of the two
+        # torch.empty buffers is written exactly once: the geometry columns by gcn_input_bwd in section A.
+        dx_problems = []
+        if need_dxh:
+            dxh = input_grads['x_human'] = empty(*x_human.shape)
+            dx_problems.append(dict(A=dpre_h, B=P['human_embedding_mlp.0.weight'],
+                                    C=dxh.view(nF * H, x_human.shape[-1])[:, :2048]))
+        if need_dxo:
+            dxo = input_grads['x_objects'] = empty(*x_objects.shape)
+            if O > 0:
+                dx_problems.append(dict(A=dpre_o, B=P['object_embedding_mlp.0.weight'], C=dxo.view(nF * O, x_objects.shape[-1])))
+        if dx_problems:
+            K.gemm(dx_problems, b_kmajor=True)
     dpre_s = K.relu_bwd(dGEOv[:, :h], GEOv[:, :h])
     t1 = S['t1']
     _lin_w_grads(K, G, 'geometry_embedding_mlp.2.weight', 'geometry_embedding_mlp.2.bias', dpre_s, t1)
@@ -2079,6 +2101,11 @@ def tggcn_backward(K, plan: Plan, P, S, x_human, x_objects, objects_mask, d_outp
     G.add(g + 'joint_embed.cnn.1.cnn.bias', db1)
     G.add(g + 'joint_embed.cnn.0.bn.weight', dgamma)
     G.add(g + 'joint_embed.cnn.0.bn.bias', dbeta)
+    if need_dxh:
+        # geometry columns (human 0; zeros for the other humans): W1^T de1 through the BatchNorm backward, which in train
+        # mode needs the dgamma / dbeta sums gcn_embed1_bwd has just produced on this stream
+        K.gcn_input_bwd(x_human, N, S['ab'], S['mi'], w1, de1, dgamma if training else None, dbeta if training else None,
+                        training, dxh)
     G.flush()
     if side is not None:
         side.join()
@@ -2164,6 +2191,7 @@ class TGGCNFunction(torch.autograd.Function):
         outputs, S = tggcn_forward(K, plan, P, x_human, x_objects, objects_mask, human_seg, object_seg, noise,
                                    training, bn_bufs, backward_follows=any(ctx.needs_input_grad))
         ctx.plan, ctx.names, ctx.P = plan, names, P
+        ctx.training, ctx.sync_bn = bool(training), bn_bufs.get('stats_reduce') is not None
         ctx.inputs = (x_human, x_objects, objects_mask)
         # The saved state goes through save_for_backward: the autograd engine owns its lifetime, as for any torch op -- the
         # ~3 GB of buffers are released when backward has run (unless retain_graph), not when the caller lets go of the
@@ -2189,6 +2217,15 @@ class TGGCNFunction(torch.autograd.Function):
         K = get_kernels()
         plan = ctx.plan
         x_human, x_objects, objects_mask = ctx.inputs
+        input_grads = {k: None for k, need in (('x_human', ctx.needs_input_grad[4]), ('x_objects', ctx.needs_input_grad[5]))
+                       if need}
+        if 'x_human' in input_grads and ctx.training and ctx.sync_bn:
+            # the train-mode BatchNorm backward needs dgamma / dbeta summed over the ranks whose statistics were reduced;
+            # a local-statistics answer would be silently wrong
+            raise NotImplementedError('d loss / d x_human in training mode with synchronised BatchNorm statistics '
+                                      '(a bn_stats_reduce hook, DataParallel(sync_bn=True)) is not implemented: the '
+                                      'geometry columns would need dgamma / dbeta reduced over the ranks. Use eval mode, '
+                                      'local statistics, or detach x_human.')
         d_outputs = list(d_outputs)[:len(d_outputs) - ctx.n_extra]
         # a gate tensor that was given as an input (not learned) carries no gradient
         n_gate = 2 if plan.n_aff is None else 4
@@ -2211,8 +2248,10 @@ class TGGCNFunction(torch.autograd.Function):
                     and not getattr(prm, '_post_accumulate_grad_hooks', None)):
                 sinks[n] = g
         S = _unpack_state(ctx.state_skeleton, ctx.saved_tensors)
-        grads = tggcn_backward(K, plan, ctx.P, S, x_human, x_objects, objects_mask, d_outputs, sinks)
+        grads = tggcn_backward(K, plan, ctx.P, S, x_human, x_objects, objects_mask, d_outputs, sinks,
+                               input_grads=input_grads or None, training=ctx.training)
         out = [None] * 11
+        out[4], out[5] = input_grads.get('x_human'), input_grads.get('x_objects')
         for n in ctx.names:
             g = grads.get(n)
             if g is not None:

@@ -140,6 +140,20 @@ int twog_gcn_embed1_fwd(const float* x_geo, int64_t frame_stride, int n_frames, 
 int twog_gcn_embed1_bwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, const float* ab,
                         const float* mean_invstd, const float* w1, const float* de1, float* partials, int n_blocks,
                         float* dw1, float* db1, float* dgamma, float* dbeta, void* stream);
+/* Gradient of the geometry INPUT (the split at vhoi/models.py:636-639, norm_data and the first 1x1 conv at
+ * models_gcn.py:45-59), given the same ReLU-masked de1 as twog_gcn_embed1_bwd: per (frame, node)
+ *   dx^[c] = sum_j de1[j] w1[j][c];   training == 0: dx[c] = a[ch] dx^[c]   (ch = c*N + n, a = ab[0][ch]);
+ *   training != 0: dx[c] = a[ch] (dx^[c] - dbeta[ch]/M - x_n[c] dgamma[ch]/M), x_n = (x - mean) invstd, M = n_frames --
+ * dgamma / dbeta are the sums twog_gcn_embed1_bwd produced over the SAME n_frames (run it first, on the same stream;
+ * NULL ok with training == 0, as is mean_invstd). dx_geo = the gradient of x_human + 2048, laid out like x_geo; human h of
+ * a frame at + h*human_stride. Human 0's 4N geometry columns get dx, those of the humans 1 .. n_humans-1 get zeros (only
+ * human 0's geometry is read). Grid = n_blocks workgroups of 256 threads, each trip of a workgroup
+ * takes 64 (frame, node) rows. Bit-reproducible. Returns -1 for n_nodes outside 1 .. twog_gcn_max_nodes(), -2 for a NULL or
+ * misaligned pointer, strides that are not whole float4s or overlap, n_humans < 1 or n_blocks < 1 -- nothing is launched. */
+int twog_gcn_input_bwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, int n_humans,
+                       int64_t human_stride, const float* ab, const float* mean_invstd, const float* w1,
+                       const float* de1, const float* dgamma, const float* dbeta, int training, float* dx_geo,
+                       int n_blocks, void* stream);
 /* The forward pass up to the aggregation as ONE kernel (csrc/geo_fused.hip): x^ = a*x+b (norm_data folded, :45-50),
  * e1 = relu(W1 x^ + b1) (:57-59, never stored), X = relu(W2 e1 + b2) (:60-63), S = softmax_j(x_i^T M x_j + d . x_j) -- the
  * similarity of compute_similarity (:95-100) with M = Wq^T Wk, d = Wk^T bq folded by the caller into md [65][64] =
