@@ -284,6 +284,9 @@ SIGNATURES = {
     'twog_eval_update': [_P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P],
     'twog_confusion_counts': [_P, _P, _L, _I, _P, _P, _P],
     'twog_eval_limits': [C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    'twog_segment_f1': [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_double), _I, _L, _I, _P, _P, _P, _P, _P, _P],
+    'twog_segment_f1_accumulate': [_P, _P, _I, _I, _P, _P, _P],
+    'twog_segment_f1_limits': [C.POINTER(C.c_int), C.POINTER(C.c_int)],
 }
 
 _lib = None

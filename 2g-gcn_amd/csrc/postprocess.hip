@@ -169,6 +169,212 @@ __global__ __launch_bounds__(64) void f1_at_k_kernel(const long long* y_true, co
     valid[s] = 1.f;
 }
 
+// ---- segmental F1@k with a workgroup per sequence, every overlap from one matching (pyrutils/metrics.py:7-65).
+// The target segment a predicted segment p is matched against is argmax(iou), which does not depend on `used`. For
+// overlap > 0 only a same-label target segment with a positive intersection can reach the threshold, and those are the
+// same-label segments among the contiguous range holding p's first and last step. So with (best_p, idx_p) the first
+// maximum of inter / union over that range:
+//   TP_k = #{t : some p has idx_p == t, best_p >= k, label_p < num_classes}
+//   FP_k = #{p : label_p < num_classes} - TP_k          FN_k = n_target_segments - TP_k
+// which is what the greedy loop counts: of the predicted segments that reach the threshold on one target segment the
+// first is a true positive and the others, like those that reach it nowhere, are false positives.
+// LDS (16-bit entries, values <= SEGF1_MAX_STEPS): orig[q] the step of the q-th kept step, tseg[q] its target segment,
+// tstart[t] / pstart[p] the first kept position of a segment (one entry beyond the last: n_kept); then one bitmap of
+// target segments per overlap. Labels are read in place (int64) through orig[].
+constexpr int SEGF1_MAX_STEPS = 4096;
+constexpr int SEGF1_MAX_OVERLAPS = 8;
+constexpr int SEGF1_THREADS = 256;
+constexpr int SEGF1_WAVES = SEGF1_THREADS / TWOG_WAVE;
+
+struct SegF1Overlaps { double k[SEGF1_MAX_OVERLAPS]; };
+
+inline int segf1_round_steps(int n_steps) { return (n_steps + 63) & ~63; }
+inline size_t segf1_lds_bytes(int n_steps) {   // 4 tables of (rounded + 2) 16-bit entries, K bitmaps of rounded / 32 words
+    const int r = segf1_round_steps(n_steps);
+    return (size_t)4 * (r + 2) * sizeof(unsigned short) + (size_t)SEGF1_MAX_OVERLAPS * (r / 32 + 1) * sizeof(unsigned);
+}
+
+// lanes of this wave below the caller whose bit is set in `mask`
+__device__ __forceinline__ int lanes_below(unsigned long long mask) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// precision, recall and F1 with the reference's three zero-denominator rules (metrics.py:49-60). Every operation is one
+// correctly rounded fp64 division, product or sum of the reference's own expression; no multiply feeds an add, and
+// contraction is off so that it stays that way.
+__device__ __forceinline__ double segment_f1_value(int tp_i, int fp_i, int fn_i) {
+#pragma clang fp contract(off)
+    const double tp = (double)tp_i, fp = (double)fp_i, fn = (double)fn_i;
+    const double precision = tp + fp > 0.0 ? tp / (tp + fp) : 0.0;
+    const double recall = tp + fn > 0.0 ? tp / (tp + fn) : 0.0;
+    return precision + recall > 0.0 ? 2.0 * (precision * recall) / (precision + recall) : 0.0;
+}
+
+// Sequence s reads y[seq_off(s) + step * step_stride]: sequence-major (entities == 0: s * n_steps, stride 1) or
+// entity-minor [bs][n_steps][E] (s = b * E + e: b * n_steps * E + e, stride E).
+__global__ __launch_bounds__(SEGF1_THREADS) void segment_f1_kernel(
+    const long long* y_true, const long long* y_pred, int n_steps, int entities, long long num_classes, SegF1Overlaps ov,
+    int K, long long ignore, int use_ignore, int* tp_out, int* fp_out, int* fn_out, double* f1_out, int* valid_out) {
+    extern __shared__ unsigned segf1_lds[];
+    __shared__ int wave_cnt[2][SEGF1_WAVES];
+    __shared__ int tp_k[SEGF1_MAX_OVERLAPS];
+    const int rounded = (n_steps + 63) & ~63;
+    unsigned short* orig = reinterpret_cast<unsigned short*>(segf1_lds);
+    unsigned short* tseg = orig + (rounded + 2);
+    unsigned short* tstart = tseg + (rounded + 2);
+    unsigned short* pstart = tstart + (rounded + 2);
+    unsigned* bitmap = reinterpret_cast<unsigned*>(pstart + (rounded + 2));   // 8 * (rounded + 2) bytes in: 4-byte aligned
+    const int words = rounded / 32 + 1;                                       // per overlap
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x;
+    int64_t off, stride;
+    if (entities > 0) { off = (int64_t)(s / entities) * n_steps * entities + s % entities; stride = entities; }
+    else { off = (int64_t)s * n_steps; stride = 1; }
+    const long long* yt = y_true + off;
+    const long long* yp = y_pred + off;
+
+    for (int w = tid; w < K * words; w += SEGF1_THREADS) bitmap[w] = 0u;
+
+    // 1. drop the ignored steps: orig[q] = step of the q-th kept one
+    int n_kept = 0;
+    for (int base = 0; base < n_steps; base += SEGF1_THREADS) {
+        const int i = base + tid;
+        const bool kept = i < n_steps && !(use_ignore && yt[(int64_t)i * stride] == ignore);
+        const unsigned long long mask = __ballot(kept);
+        if (lane == 0) wave_cnt[0][wave] = __popcll(mask);
+        __syncthreads();
+        int before = n_kept, total = n_kept;
+        for (int w = 0; w < SEGF1_WAVES; ++w) {
+            const int c = wave_cnt[0][w];
+            if (w < wave) before += c;
+            total += c;
+        }
+        if (kept) orig[before + lanes_below(mask)] = (unsigned short)i;
+        n_kept = total;
+        __syncthreads();
+    }
+    if (n_kept == 0) {   // the reference skips such a sequence (metrics.py:77-78): an all-zero row, valid 0
+        if (tid < K) {
+            const int64_t o = (int64_t)s * K + tid;
+            tp_out[o] = 0; fp_out[o] = 0; fn_out[o] = 0; f1_out[o] = 0.0;
+        }
+        if (tid == 0) valid_out[s] = 0;
+        return;
+    }
+
+    // 2. segment starts of the filtered target and prediction, numbered by a prefix sum
+    int n_tgt = 0, n_pred = 0;
+    for (int base = 0; base < n_kept; base += SEGF1_THREADS) {
+        const int q = base + tid;
+        bool ts = false, ps = false;
+        if (q < n_kept) {
+            const int64_t at = (int64_t)orig[q] * stride;
+            ts = ps = q == 0;
+            if (q > 0) {
+                const int64_t prev = (int64_t)orig[q - 1] * stride;
+                ts = yt[at] != yt[prev];
+                ps = yp[at] != yp[prev];
+            }
+        }
+        const unsigned long long tmask = __ballot(ts), pmask = __ballot(ps);
+        if (lane == 0) { wave_cnt[0][wave] = __popcll(tmask); wave_cnt[1][wave] = __popcll(pmask); }
+        __syncthreads();
+        int tbefore = n_tgt, ttotal = n_tgt, pbefore = n_pred, ptotal = n_pred;
+        for (int w = 0; w < SEGF1_WAVES; ++w) {
+            const int ct = wave_cnt[0][w], cp = wave_cnt[1][w];
+            if (w < wave) { tbefore += ct; pbefore += cp; }
+            ttotal += ct;
+            ptotal += cp;
+        }
+        if (q < n_kept) {
+            const int t = tbefore + lanes_below(tmask) + (ts ? 1 : 0) - 1;   // the segment that holds q
+            tseg[q] = (unsigned short)t;
+            if (ts) tstart[t] = (unsigned short)q;
+            if (ps) pstart[pbefore + lanes_below(pmask)] = (unsigned short)q;
+        }
+        n_tgt = ttotal;
+        n_pred = ptotal;
+        __syncthreads();
+    }
+    if (tid == 0) { tstart[n_tgt] = (unsigned short)n_kept; pstart[n_pred] = (unsigned short)n_kept; }
+    __syncthreads();
+
+    // 3. one lane per predicted segment: first maximum of inter / union over its candidate range, then one bit per
+    // overlap it reaches (an OR: the bitmaps do not depend on the arrival order)
+    int counted = 0;
+    for (int p = tid; p < n_pred; p += SEGF1_THREADS) {
+        const int o0 = pstart[p], o1 = pstart[p + 1];
+        const long long label = yp[(int64_t)orig[o0] * stride];
+        if (label >= num_classes) continue;                     // metrics.py:38-39
+        ++counted;
+        const int t_first = tseg[o0], t_last = tseg[o1 - 1];
+        double best = 0.0;
+        int idx = -1;
+        for (int t = t_first; t <= t_last; ++t) {
+            const int t0 = tstart[t], t1 = tstart[t + 1];
+            if (yt[(int64_t)orig[t0] * stride] != label) continue;
+            const int inter = min(o1, t1) - max(o0, t0);
+            const int uni = max(o1, t1) - min(o0, t0);
+            const double iou = (double)inter / (double)uni;
+            if (iou > best) { best = iou; idx = t; }
+        }
+        if (idx < 0) continue;
+        for (int k = 0; k < K; ++k)
+            if (best >= ov.k[k]) atomicOr(&bitmap[k * words + (idx >> 5)], 1u << (idx & 31));
+    }
+    counted = wave_sum_int(counted);
+    if (lane == 0) wave_cnt[0][wave] = counted;
+    __syncthreads();
+    counted = 0;
+    for (int w = 0; w < SEGF1_WAVES; ++w) counted += wave_cnt[0][w];
+
+    // 4. TP_k = set bits of bitmap k (wave w takes k = w, w + 4)
+    const int tgt_words = (n_tgt + 31) >> 5;
+    for (int k = wave; k < K; k += SEGF1_WAVES) {
+        int c = 0;
+        for (int w = lane; w < tgt_words; w += TWOG_WAVE) c += __popc(bitmap[k * words + w]);
+        c = wave_sum_int(c);
+        if (lane == 0) tp_k[k] = c;
+    }
+    __syncthreads();
+    if (tid < K) {
+        const int tp = tp_k[tid], fp = counted - tp, fn = n_tgt - tp;
+        const int64_t o = (int64_t)s * K + tid;
+        tp_out[o] = tp; fp_out[o] = fp; fn_out[o] = fn;
+        f1_out[o] = segment_f1_value(tp, fp, fn);
+    }
+    if (tid == 0) valid_out[s] = 1;
+}
+
+// One workgroup: sums[k] += sum_s f1[s][k], valid_sums[k] += sum_s valid[s], in fp64 and in a fixed order -- thread t adds
+// rows t, t + 256, ... in that order, then a fixed tree over the 256 partial sums.
+__global__ __launch_bounds__(SEGF1_THREADS) void segment_f1_accumulate_kernel(const double* f1, const int* valid, int n_seq,
+                                                                              int K, double* f1_sums, double* valid_sums) {
+    __shared__ double red[SEGF1_THREADS];
+    const int tid = threadIdx.x;
+    for (int k = 0; k <= K; ++k) {   // column K is `valid`
+        double v = 0.0;
+        for (int s = tid; s < n_seq; s += SEGF1_THREADS) v += k < K ? f1[(int64_t)s * K + k] : (double)valid[s];
+        red[tid] = v;
+        __syncthreads();
+        for (int h = SEGF1_THREADS / 2; h > 0; h >>= 1) {
+            if (tid < h) red[tid] += red[tid + h];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            if (k < K) f1_sums[k] += red[0];
+            else for (int j = 0; j < K; ++j) valid_sums[j] += red[0];
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 extern "C" int twog_predict_labels(const float* logp, int bs, int n_classes, int T, int E, int downsampling, int T_out,
@@ -227,6 +433,45 @@ extern "C" int twog_confusion_counts(const int64_t* y_true, const int64_t* y_pre
     hipLaunchKernelGGL(confusion_counts_kernel, dim3(eval_grid(n)), dim3(256), lds, (hipStream_t)stream,
                        reinterpret_cast<const long long*>(y_true), reinterpret_cast<const long long*>(y_pred), n,
                        n_classes, reinterpret_cast<long long*>(counts), reinterpret_cast<long long*>(flags));
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int twog_segment_f1_limits(int* max_steps, int* max_overlaps) {
+    if (max_steps) *max_steps = SEGF1_MAX_STEPS;
+    if (max_overlaps) *max_overlaps = SEGF1_MAX_OVERLAPS;
+    return 0;
+}
+
+extern "C" int twog_segment_f1(const int64_t* y_true, const int64_t* y_pred, int n_seq, int n_steps, int entities,
+                               int num_classes, const double* overlaps, int n_overlaps, int64_t ignore_value,
+                               int use_ignore, int32_t* tp, int32_t* fp, int32_t* fn, double* f1, int32_t* valid,
+                               void* stream) {
+    if (n_seq < 0 || n_steps < 0 || entities < 0 || (entities > 0 && n_seq % entities != 0)) return -1;
+    if (n_overlaps < 1 || n_overlaps > SEGF1_MAX_OVERLAPS || !overlaps) return -1;
+    SegF1Overlaps ov = {};
+    for (int k = 0; k < n_overlaps; ++k) {
+        if (!(overlaps[k] > 0.0)) return -1;   // zero, negative or NaN: only twog_f1_at_k serves those
+        ov.k[k] = overlaps[k];
+    }
+    if (n_steps > SEGF1_MAX_STEPS) return -2;
+    if (n_seq == 0) return 0;
+    static_assert(4 * (SEGF1_MAX_STEPS + 2) * 2 + SEGF1_MAX_OVERLAPS * (SEGF1_MAX_STEPS / 32 + 1) * 4 + 64 <= 64 * 1024,
+                  "the LDS layout at the longest sequence stays below what a launch may ask for without an attribute");
+    hipLaunchKernelGGL(segment_f1_kernel, dim3(n_seq), dim3(SEGF1_THREADS), segf1_lds_bytes(n_steps), (hipStream_t)stream,
+                       reinterpret_cast<const long long*>(y_true), reinterpret_cast<const long long*>(y_pred), n_steps,
+                       entities, (long long)num_classes, ov, n_overlaps, (long long)ignore_value, use_ignore, tp, fp, fn,
+                       f1, valid);
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int twog_segment_f1_accumulate(const double* f1, const int32_t* valid, int n_seq, int n_overlaps,
+                                          double* f1_sums, double* valid_sums, void* stream) {
+    if (n_seq < 0 || n_overlaps < 1 || n_overlaps > SEGF1_MAX_OVERLAPS) return -1;
+    if (n_seq == 0) return 0;
+    hipLaunchKernelGGL(segment_f1_accumulate_kernel, dim3(1), dim3(SEGF1_THREADS), 0, (hipStream_t)stream, f1, valid, n_seq,
+                       n_overlaps, f1_sums, valid_sums);
     TWOG_CHECK_LAUNCH();
     return 0;
 }

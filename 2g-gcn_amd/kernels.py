@@ -1447,6 +1447,57 @@ class HipKernels:
                     'twog_confusion_counts')
         return counts
 
+    def segment_f1_limits(self):
+        """(longest sequence segment_f1 takes, most overlaps of one call)."""
+        max_steps, max_overlaps = C.c_int(0), C.c_int(0)
+        self._check(self.lib.twog_segment_f1_limits(C.byref(max_steps), C.byref(max_overlaps)), 'twog_segment_f1_limits')
+        return max_steps.value, max_overlaps.value
+
+    def segment_f1(self, y_true, y_pred, num_classes, overlaps, ignore_value=None, entity_minor=False):
+        """Per-sequence segmental F1@k for every overlap from one matching, one launch. int64 labels, read in place:
+        (n_seq, n_steps), or with entity_minor (bs, n_steps, E) as eval_update writes them (sequence b * E + e). Returns
+        (f1 float64 (n_seq, K), tp, fp, fn int32 (n_seq, K), valid int32 (n_seq,), packed): the five are views of the one
+        int64 buffer `packed`, so that a caller who wants them on the host makes one copy (see unpack_segment_f1)."""
+        assert y_true.dtype == torch.int64 and y_pred.dtype == torch.int64 and y_true.shape == y_pred.shape
+        assert y_true.dim() == (3 if entity_minor else 2), tuple(y_true.shape)
+        y_true, y_pred = y_true.contiguous(), y_pred.contiguous()
+        if entity_minor:
+            bs, n_steps, E = y_true.shape
+            n_seq = bs * E
+        else:
+            (n_seq, n_steps), E = y_true.shape, 0
+        K = len(overlaps)
+        ov = (C.c_double * max(K, 1))(*[float(o) for o in overlaps])
+        packed = torch.empty(segment_f1_words(n_seq, K), dtype=torch.int64, device=y_true.device)
+        f1, tp, fp, fn, valid = unpack_segment_f1(packed, n_seq, K)
+        self._check(self.lib.twog_segment_f1(y_true.data_ptr(), y_pred.data_ptr(), n_seq, n_steps, E, int(num_classes), ov, K,
+                                             int(ignore_value) if ignore_value is not None else 0,
+                                             int(ignore_value is not None), tp.data_ptr(), fp.data_ptr(), fn.data_ptr(),
+                                             f1.data_ptr(), valid.data_ptr(), self._stream()), 'twog_segment_f1')
+        return f1, tp, fp, fn, valid, packed
+
+    def segment_f1_accumulate(self, f1, valid, f1_sums, valid_sums):
+        """f1_sums[k] += f1[:, k].sum(), valid_sums[k] += valid.sum() in fp64 on the device, in a fixed order, in place."""
+        n_seq, K = f1.shape
+        assert f1.dtype == torch.float64 and f1.is_contiguous() and valid.dtype == torch.int32 and valid.numel() == n_seq
+        for t in (f1_sums, valid_sums):
+            assert t.dtype == torch.float64 and t.is_contiguous() and t.numel() == K
+        self._check(self.lib.twog_segment_f1_accumulate(f1.data_ptr(), valid.data_ptr(), n_seq, K, f1_sums.data_ptr(),
+                                                        valid_sums.data_ptr(), self._stream()), 'twog_segment_f1_accumulate')
+
+
+def segment_f1_words(n_seq, K):
+    """8-byte words of the packed result of segment_f1: n_seq * K fp64, then (3 * n_seq * K + n_seq) int32."""
+    return n_seq * K + (3 * n_seq * K + n_seq + 1) // 2
+
+
+def unpack_segment_f1(packed, n_seq, K):
+    """(f1, tp, fp, fn, valid) as views of the packed int64 buffer of segment_f1, on whichever device it is."""
+    f1 = packed[:n_seq * K].view(torch.float64).view(n_seq, K)
+    ints = packed[n_seq * K:].view(torch.int32)
+    tp, fp, fn = (ints[j * n_seq * K:(j + 1) * n_seq * K].view(n_seq, K) for j in range(3))
+    return f1, tp, fp, fn, ints[3 * n_seq * K:3 * n_seq * K + n_seq]
+
 
 _backend = None
 

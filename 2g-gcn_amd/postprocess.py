@@ -13,11 +13,13 @@ twog_confusion_counts); every metric is a few hundred fp64 divisions on those in
 scikit-learn's semantics, so scikit-learn itself is not needed. `EvaluationAccumulator` keeps the counts and the F1@k
 sums on the device over a whole test set and merges over ranks by a sum.
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 import torch.distributed as dist
 
-from .kernels import get_kernels
+from .kernels import get_kernels, unpack_segment_f1
 
 
 def match_shape(out: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
@@ -78,6 +80,127 @@ def evaluate_f1_at_k(targets: dict, outputs: dict, num_subactivities, num_afford
         results[index] = f1_at_k(target.reshape(-1, steps), output.reshape(-1, steps), num_classes, overlap=overlap,
                                  ignore_value=-1.0)
     return results
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# segmental F1@k per example: every overlap from one matching (twog_segment_f1)
+SegmentF1 = namedtuple('SegmentF1', 'f1 tp fp fn valid route')
+SegmentF1.__doc__ = """f1 float64 (n_seq, K); tp / fp / fn int32 (n_seq, K), None on the 'thread' route; valid int32 (n_seq,), 0
+for a sequence without a kept step (its rows are zero); route: 'workgroup' (twog_segment_f1) or 'thread' (twog_f1_at_k)."""
+
+
+def _positive(overlaps):
+    return all(o > 0 for o in overlaps)   # False for zero, a negative value and NaN
+
+
+def _label_matrices(y_true, y_pred):
+    dev = y_pred.device if isinstance(y_pred, torch.Tensor) else (y_true.device if isinstance(y_true, torch.Tensor) else 'cuda')
+    to = lambda y: torch.as_tensor(np.asarray(y) if not isinstance(y, torch.Tensor) else y).to(dev).to(torch.int64)
+    return to(y_true), to(y_pred)
+
+
+def _segment_f1(K, yt, yp, num_classes, overlaps, ignore_value, entity_minor, need_counts=False):
+    """SegmentF1 plus the packed buffer (None on the 'thread' route) for int64 label tensors on one device: sequence-major
+    (n_seq, n_steps), or (bs, n_steps, E) with entity_minor. twog_segment_f1 takes positive overlaps and sequences up to
+    its max_steps; anything else goes through the per-thread kernel, one launch per overlap, which has no counts."""
+    overlaps = [float(o) for o in overlaps]
+    max_steps, max_overlaps = K.segment_f1_limits()
+    fits = len(overlaps) >= 1 and _positive(overlaps) and yt.shape[1] <= max_steps
+    if fits and len(overlaps) <= max_overlaps:
+        f1, tp, fp, fn, valid, packed = K.segment_f1(yt, yp, num_classes, overlaps, ignore_value, entity_minor=entity_minor)
+        return SegmentF1(f1, tp, fp, fn, valid, 'workgroup'), packed
+    if fits:   # more overlaps than one launch takes
+        parts = [_segment_f1(K, yt, yp, num_classes, overlaps[j:j + max_overlaps], ignore_value, entity_minor)[0]
+                 for j in range(0, len(overlaps), max_overlaps)]
+        cat = lambda field: torch.cat([getattr(p, field) for p in parts], 1)
+        return SegmentF1(cat('f1'), cat('tp'), cat('fp'), cat('fn'), parts[0].valid, 'workgroup'), None
+    if need_counts:
+        raise ValueError(f'tp / fp / fn exist only on the workgroup route: it takes overlaps > 0 and up to {max_steps} steps, '
+                         f'not overlaps {overlaps} on {yt.shape[1]} steps')
+    if entity_minor:
+        steps = yt.shape[1]
+        yt, yp = yt.transpose(1, 2).reshape(-1, steps), yp.transpose(1, 2).reshape(-1, steps)
+    n_seq = yt.shape[0]
+    f1 = torch.empty(n_seq, len(overlaps), dtype=torch.float64, device=yt.device)
+    valid = torch.zeros(n_seq, dtype=torch.int32, device=yt.device)
+    for j, overlap in enumerate(overlaps):
+        f1_j, valid_j = K.f1_at_k(yt, yp, num_classes, overlap, ignore_value)
+        f1[:, j] = f1_j
+        valid = valid_j.to(torch.int32)
+    return SegmentF1(f1, None, None, None, valid, 'thread'), None
+
+
+def f1_at_k_per_example(y_true, y_pred, num_classes: int, overlaps, ignore_value: float = None, *, need_counts: bool = False):
+    """pyrutils/metrics.py:7-65 for every sequence of (n_seq, n_steps) label matrices and every overlap, in one launch:
+    the values `dump_f1_scores_per_example` prints and `f1_at_k` averages. Returns a SegmentF1 of device tensors. Overlaps
+    <= 0 and sequences longer than twog_segment_f1 holds are served by the per-thread kernel (f1 stored in fp32 there, no
+    tp / fp / fn: `need_counts` makes that an error instead)."""
+    yt, yp = _label_matrices(y_true, y_pred)
+    return _segment_f1(get_kernels(), yt.reshape(-1, yt.shape[-1]), yp.reshape(-1, yp.shape[-1]), num_classes, overlaps,
+                       ignore_value, False, need_counts)[0]
+
+
+def _to_host(res, packed):
+    """(f1 (n_seq, K) float64, valid (n_seq,)) as numpy arrays: one copy of the packed buffer on the workgroup route."""
+    if packed is not None:
+        f1, _, _, _, valid = unpack_segment_f1(packed.cpu(), *res.f1.shape)
+        return f1.numpy(), valid.numpy()
+    return res.f1.cpu().numpy(), res.valid.cpu().numpy()
+
+
+def _entity_minor(target, output):
+    """int64 (N, T, E) labels of one index on the output's device; (N, T) becomes (N, T, 1)."""
+    target, output = _label_matrices(target, output)
+    if target.ndim == 2:
+        target, output = target.unsqueeze(-1), output.unsqueeze(-1)
+    if target.ndim != 3 or target.shape != output.shape:
+        raise ValueError(f'labels (N, T) or (N, T, E) of equal shape expected, not {tuple(target.shape)} and {tuple(output.shape)}')
+    return target, output
+
+
+def evaluate_f1_at_k_multi(targets: dict, outputs: dict, num_subactivities, num_affordances, overlaps=(0.10, 0.25, 0.50)):
+    """The `evaluate_f1_at_k` calls of `predict_all` (predict.py:358-360, :425-426), one per overlap, from one launch and
+    one copy per index: {index: labels (N, T) or (N, T, E)} -> {overlap: {index: F1@overlap}}. The labels are read in
+    place (no transposition); the mean adds the per-sequence fp64 values in sequence order, like metrics.py:70-81."""
+    K = get_kernels()
+    results = {overlap: {} for overlap in overlaps}
+    for index, target in sorted(targets.items()):
+        target, output = _entity_minor(target, outputs[index])
+        num_classes = num_affordances if 'affordance' in str(index) else num_subactivities
+        f1, valid = _to_host(*_segment_f1(K, target, output, num_classes, overlaps, -1, True))
+        n_valid = float(valid.sum())
+        for j, overlap in enumerate(overlaps):
+            total = 0.0
+            for v in f1[valid != 0, j]:
+                total += float(v)
+            results[overlap][index] = total / n_valid if n_valid else float('nan')   # the reference divides by zero there
+    return results
+
+
+def f1_scores_per_example(outputs: dict, targets: dict, test_ids, num_subactivities, num_affordances, overlap: float,
+                          file=None) -> str:
+    """The text `dump_f1_scores_per_example` (predict.py:456-472) writes: per problem type, in the order of `outputs`, one
+    line f'{problem_type}_{test_id}_{ent_id}: {f1:.4f}' for every entity of every clip that has a target step, then a blank
+    line. {problem_type: labels (N, T, E)}; one launch and one copy per problem type. Returns the text and writes it to
+    `file` (a path or an object with write) when one is given."""
+    K = get_kernels()
+    lines = []
+    for problem_type in outputs:
+        target, output = _entity_minor(targets[problem_type], outputs[problem_type])
+        num_classes = num_subactivities if 'sub-activity' in str(problem_type) else num_affordances
+        f1, valid = _to_host(*_segment_f1(K, target, output, num_classes, [overlap], -1, True))
+        E = target.shape[2]
+        for n, test_id in zip(range(target.shape[0]), test_ids):
+            lines += [f'{problem_type}_{test_id}_{e}: {f1[n * E + e, 0]:.4f}\n' for e in range(E) if valid[n * E + e]]
+        lines.append('\n')
+    text = ''.join(lines)
+    if file is not None:
+        if hasattr(file, 'write'):
+            file.write(text)
+        else:
+            with open(file, mode='w') as f:
+                f.write(text)
+    return text
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -259,9 +382,17 @@ class EvaluationAccumulator:
     `all_reduce` sums the state over the ranks of a sharded test set and `result` makes the one copy to the host.
 
     names: the evaluated outputs in model order (the last `len(names)` outputs and targets of a batch are used, like
-    predict.py:61-63). num_classes: one int for all of them, or one per name."""
+    predict.py:61-63). num_classes: one int for all of them, or one per name. f1_route: 'thread' runs twog_f1_at_k once per
+    overlap on transposed copies of the labels (fp32 per-sequence values); 'workgroup' runs twog_segment_f1 once for all
+    overlaps on the labels as eval_update wrote them and twog_segment_f1_accumulate (fp64 throughout), and falls back to
+    'thread' for a batch it cannot take (an overlap <= 0, more steps than its limit). `last_f1_route` names what the last
+    update ran."""
 
-    def __init__(self, names, num_classes, downsampling: int = 1, overlaps=(0.1, 0.25, 0.5)):
+    def __init__(self, names, num_classes, downsampling: int = 1, overlaps=(0.1, 0.25, 0.5), f1_route: str = 'thread'):
+        if f1_route not in ('thread', 'workgroup'):
+            raise ValueError(f"f1_route must be 'thread' or 'workgroup', not {f1_route!r}")
+        self.f1_route = f1_route
+        self.last_f1_route = None
         self.names = list(names)
         self.num_classes = [int(num_classes)] * len(self.names) if np.ndim(num_classes) == 0 else [int(c) for c in num_classes]
         if len(self.num_classes) != len(self.names):
@@ -306,6 +437,9 @@ class EvaluationAccumulator:
                 step_index = step_index.to(device=out.device, dtype=torch.int32)
             labels, kept = K.eval_update(out, self.downsampling, tgt.to(torch.int64), step_index, self._counts[i],
                                          self._flags[i], want_labels=True)
+            if self.f1_route == 'workgroup' and self.overlaps and self._update_f1_workgroup(K, i, kept, labels):
+                continue
+            self.last_f1_route = 'thread'
             # f1_at_k wants sequence-major (n_seq, n_steps): the transposition of evaluate_f1_at_k
             steps = labels.shape[1]
             labels, kept = labels.transpose(1, 2).reshape(-1, steps), kept.transpose(1, 2).reshape(-1, steps)
@@ -313,6 +447,19 @@ class EvaluationAccumulator:
                 f1, valid = K.f1_at_k(kept, labels, self.num_classes[i], overlap, -1)
                 self._f1[i][j:j + 1].add_(f1.sum(dtype=torch.float64))
                 self._valid[i][j:j + 1].add_(valid.sum(dtype=torch.float64))
+
+    def _update_f1_workgroup(self, K, i, kept, labels) -> bool:
+        """One twog_segment_f1 per max_overlaps overlaps on the entity-minor labels, one accumulate each; False (nothing
+        issued) when the batch needs the per-thread kernel."""
+        max_steps, max_overlaps = K.segment_f1_limits()
+        if not _positive(self.overlaps) or labels.shape[1] > max_steps:
+            return False
+        for j in range(0, len(self.overlaps), max_overlaps):
+            f1, _, _, _, valid, _ = K.segment_f1(kept, labels, self.num_classes[i], self.overlaps[j:j + max_overlaps], -1,
+                                                 entity_minor=True)
+            K.segment_f1_accumulate(f1, valid, self._f1[i][j:j + max_overlaps], self._valid[i][j:j + max_overlaps])
+        self.last_f1_route = 'workgroup'
+        return True
 
     def all_reduce(self, group=None):
         """Sum the state over the ranks of `group` (every rank evaluated its own shard of the clips). A process without

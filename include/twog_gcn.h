@@ -816,6 +816,18 @@ int twog_mtl_weight_bwd(const twog_mtl_t* spec, const float* losses, const float
  *   a prediction outside [0, C) whose target is not -1 is counted in flags[0] too.
  * twog_eval_limits: max_classes, and the positions one trip of the capped grid covers (more than that and the
  *   grid-stride loop of the two kernels above runs again).
+ * twog_segment_f1: the same metric as twog_f1_at_k for up to max_overlaps thresholds from ONE matching, one workgroup per
+ *   sequence. Sequence s of y_true / y_pred (int64, compared as int64) is read in place: entities == 0 is sequence-major
+ *   [n_seq][n_steps]; entities == E > 0 is [n_seq / E][n_steps][E] as twog_eval_update writes labels (s = b * E + e, step
+ *   stride E). Per sequence and overlap k: tp / fp / fn int32 [n_seq][K] (the counts of metrics.py:40-48) and f1 fp64
+ *   [n_seq][K] (precision, recall and F1 with the reference's zero-denominator rules, in the reference's own fp64
+ *   expressions); valid int32 [n_seq] is 0 for a sequence with no kept step, whose rows are all zero. `overlaps` is a HOST
+ *   array of n_overlaps doubles, read before the call returns. Integer counting and LDS bit-OR only: results are
+ *   bit-identical from run to run. Returns -1 for an overlap <= 0 or NaN (there a zero IoU can match and only the
+ *   sequential matching of twog_f1_at_k is right) and for n_overlaps outside [1, max_overlaps]; -2 for n_steps > max_steps.
+ * twog_segment_f1_accumulate: one workgroup; f1_sums[k] += sum_s f1[s][k] and valid_sums[k] += sum_s valid[s] (device
+ *   fp64, k < n_overlaps), in a fixed order.
+ * twog_segment_f1_limits: the longest sequence the LDS layout of twog_segment_f1 holds, and its largest n_overlaps.
  * =============================================================================================================== */
 int twog_predict_labels(const float* logp, int bs, int n_classes, int T, int E, int downsampling, int T_out,
                         int64_t* labels, void* stream);
@@ -827,6 +839,12 @@ int twog_eval_update(const float* logp, int bs, int n_classes, int T, int E, int
 int twog_confusion_counts(const int64_t* y_true, const int64_t* y_pred, int64_t n, int n_classes, int64_t* counts,
                           int64_t* flags, void* stream);
 int twog_eval_limits(int* max_classes, int* positions_per_trip);
+int twog_segment_f1(const int64_t* y_true, const int64_t* y_pred, int n_seq, int n_steps, int entities, int num_classes,
+                    const double* overlaps, int n_overlaps, int64_t ignore_value, int use_ignore, int32_t* tp, int32_t* fp,
+                    int32_t* fn, double* f1, int32_t* valid, void* stream);
+int twog_segment_f1_accumulate(const double* f1, const int32_t* valid, int n_seq, int n_overlaps, double* f1_sums,
+                               double* valid_sums, void* stream);
+int twog_segment_f1_limits(int* max_steps, int* max_overlaps);
 
 #ifdef __cplusplus
 }
