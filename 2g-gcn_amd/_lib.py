@@ -256,6 +256,7 @@ SIGNATURES = {
     'twog_ssp_bwd': [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     'twog_gate_fwd': [C.POINTER(Gate), _P],
     'twog_gate_bwd': [C.POINTER(Gate), _P, _P, _P, _P, _P],
+    'twog_gumbel_noise_fill': [_P, _I, _I, _I, C.c_uint32, _P, _P, _P],
     'twog_rank1_update': [Rows, _P, _P, _I, _I, _P],
     'twog_colsum': [Rows, _P, _I, _I, _P, _I, _P, _I, _P],
     'twog_colsum_n_partial_floats': [C.POINTER(ColSum), _I],

@@ -10,7 +10,7 @@ averaging is folded into the fused Adam kernel (no extra pass over the gradients
 BatchNorm statistics of the geometry branch stay local to each rank (standard DDP semantics); Gumbel noise is drawn
 per rank. Dead parameters (constructed by the reference but never used) keep a zero gradient.
 The three cross-sample couplings of SURVEY 8e have an exact-equivalence switch each: sync_bn (a), count_weighted_loss
-(b), global_noise_seed (c).
+(b), global_noise_seed or device_noise_seed (c).
 """
 import os
 import weakref
@@ -165,13 +165,17 @@ class DataParallel:
 
     def __init__(self, model: torch.nn.Module, process_group=None, bucket_mb: int = 64, broadcast: bool = True,
                  sync_bn: bool = False, global_noise_seed: int = None, overlap: bool = True,
-                 count_weighted_loss: bool = False, force_collectives: bool = False, extra_modules=()):
+                 count_weighted_loss: bool = False, force_collectives: bool = False, extra_modules=(),
+                 device_noise_seed: int = None):
         """sync_bn: the geometric-level BatchNorm uses the statistics of the GLOBAL batch (one all-reduce of 2*4N fp64
         sums per step). count_weighted_loss: every term of the criterion (losses.multi_task_loss) is
         normalised by the GLOBAL number of valid (non-ignored) targets instead of the rank's own (one all-reduce of the
         6-12 per-term counts per step; 8e (b)) -- with ragged clips (-1 targets) the averaged rank gradients are then the
         gradient of the global mean, not a mean of per-rank means. global_noise_seed: every rank draws the Gumbel noise of
-        the global batch from a generator seeded with this value and keeps its shard (8e (c)). With all three (and equal
+        the global batch from a generator seeded with this value and keeps its shard (8e (c)); device_noise_seed gives the
+        same equivalence without the W-fold host draw: the noise is drawn on the device (model.use_device_noise(seed)) as a
+        function of (seed, forward number, GLOBAL clip index rank * bs + b, time step, entity), so every rank draws its own
+        clips only. The two are mutually exclusive. With all three (and equal
         shard sizes) W ranks compute what one process computes on the whole batch; the throughput default keeps them off
         (standard DDP semantics; equal-length synthetic clips make the counts equal anyway).
         force_collectives: run every collective (broadcast, stage-hooked asynchronous all-reduces, count / statistics
@@ -181,6 +185,8 @@ class DataParallel:
         their parameters live in the same flat buffers after the model's, are broadcast and all-reduced with them and
         stepped by the same FusedAdam (the reference's optimizer.add_param_group, train.py:42-46); FusedAdam's clipping
         leaves them out."""
+        if global_noise_seed is not None and device_noise_seed is not None:
+            raise ValueError('global_noise_seed and device_noise_seed are two routes to the same noise: pass one of them')
         self.model = model
         self.extra_modules = list(extra_modules)
         self.group = process_group
@@ -228,6 +234,11 @@ class DataParallel:
             shard = (rank, self.world, torch.Generator().manual_seed(int(global_noise_seed)))
             ops.set_model_extra(model, 'noise_shard', shard)
             self._installed['noise_shard'] = shard
+        if device_noise_seed is not None:
+            model.use_device_noise(device_noise_seed)
+            noise = ops.get_model_extra(model, 'device_noise')
+            noise['rank'] = rank   # clip b of this rank's batch is clip rank * bs + b of the global batch (equal shard sizes)
+            self._installed['device_noise'] = noise
         # gradients are laid out in the order the backward pass finishes them (ops.grad_ready_stage), so that each
         # stage's all-reduce can start from inside the backward pass and overlap with the rest of it
         self.flat = FlatParameters(model, stage_of=ops.grad_ready_stage if overlap else None,
@@ -245,13 +256,16 @@ class DataParallel:
             self.collective_calls += 1
 
     def close(self):
-        """Detaches this wrapper from the model (stage hook, sync-BN / noise-shard / loss-count settings)."""
+        """Detaches this wrapper from the model (stage hook, sync-BN / noise-shard / device-noise / loss-count settings: the
+        model draws its noise on the host again). Also available as remove()."""
         from . import ops
         hook = ops.get_model_extra(self.model, 'stage_hook')
         if isinstance(hook, weakref.WeakMethod) and hook() == self._stage_ready:
             ops.set_grad_stage_hook(self.model, None)
         _remove_installed(self.model, self._installed)
         self._count_reducer = None
+
+    remove = close
 
     def loss_scope(self):
         """Context manager for the criterion call(s) of ONE training step: inside it, with count_weighted_loss=True, every

@@ -63,6 +63,12 @@ def n_rows(t):
     return t.shape[0] if t.dim() == 2 else t.shape[0] * t.shape[1]
 
 
+def _as_int64(v):
+    """A Python int modulo 2^64 as the signed value with the same 64 bits (torch has no unsigned 64-bit dtype)."""
+    v = int(v) & (2 ** 64 - 1)
+    return v - 2 ** 64 if v >= 2 ** 63 else v
+
+
 class HipKernels:
     """The product backend. `tests/fake_kernels.py` implements the same methods in plain torch for CPU-side tests of
     the host logic; it is never reachable from this package."""
@@ -980,6 +986,28 @@ class HipKernels:
         self._check(self.lib.twog_gate_bwd(C.byref(g), _ptr(d_hard), _ptr(d_soft), _ptr(st_mask), dlogit.data_ptr(),
                                            self._stream()), 'twog_gate_bwd')
         return dlogit
+
+    def new_noise_state(self, seed, calls=0, device=None):
+        """The generator state of gumbel_noise_fill: int64 [seed, calls] on `device` (both taken modulo 2^64)."""
+        return torch.tensor([_as_int64(seed), _as_int64(calls)], dtype=torch.int64, device=device)
+
+    def gumbel_noise_fill(self, noise, T, noise_entities, bs, clip_offset, state, words=None):
+        """noise fp32 (T * noise_entities * bs * 2 values, the layout gate_fwd reads) = the Gumbel noise of call state[1] under
+        seed state[0] for the clips clip_offset .. clip_offset + bs - 1 (twog_gumbel_noise_fill: Philox4x32-10, a pure function
+        of seed, call, clip, time step and slot); state[1] += 1 on the device behind it. Nothing is read or written on the host.
+        words: optional int32 buffer of twice the size that receives the raw generator output. Not a recordable (taped) call:
+        issue it before a loop is composed."""
+        n = T * noise_entities * bs
+        assert noise.dtype == torch.float32 and noise.is_contiguous() and noise.numel() == 2 * n, (tuple(noise.shape), n)
+        assert state.dtype == torch.int64 and state.is_contiguous() and state.numel() == 2 and state.device == noise.device
+        if words is not None:
+            assert words.dtype == torch.int32 and words.is_contiguous() and words.numel() == 4 * n \
+                and words.device == noise.device
+        if not 0 <= clip_offset < 1 << 32:
+            raise ValueError(f'clip_offset {clip_offset} is not a 32-bit unsigned value')
+        self._check(self.lib.twog_gumbel_noise_fill(noise.data_ptr(), int(T), int(noise_entities), int(bs), int(clip_offset),
+                                                    state.data_ptr(), _ptr(words), self._stream()), 'twog_gumbel_noise_fill')
+        return noise
 
     def rank1_update(self, dst, s, v):
         """dst[r][c] += s[r] * v[c] on a row-strided view."""

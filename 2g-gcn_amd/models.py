@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .kernels import get_kernels
 
 _ACT = {'identity': nn.Identity, 'logsigmoid': nn.LogSigmoid, 'logsoftmax': nn.LogSoftmax, 'relu': nn.ReLU,
         'sigmoid': nn.Sigmoid, 'softmax': nn.Softmax, 'softplus': nn.Softplus, 'tanh': nn.Tanh}
@@ -237,6 +238,39 @@ class TGGCN(nn.Module):
             bad.append('periodic position embedding with an odd hidden_size')   # the reference asserts (models.py:1787)
         self._unsupported = bad
 
+    # ---- where the Gumbel noise of the 'gs' gates comes from. The constructor keeps the reference's keywords and state_dict()
+    # the reference's keys, so the choice is made by methods and kept in the model's side table (ops.set_model_extra): a
+    # copy.deepcopy / torch.save of the model does not carry it and draws on the host like the reference.
+    def use_device_noise(self, seed: int, calls: int = 0):
+        """From the next forward on the noise is drawn on the device (kernels.gumbel_noise_fill): the pair of (clip, time step,
+        gated entity) in the calls-th forward after this is a function of (seed, calls, clip, t, entity) alone. No torch
+        generator is touched and nothing is copied from the host; every forward, train or eval, advances the call number on the
+        device. The state [seed, calls] is allocated on the device of the first forward's x_human."""
+        ops.set_model_extra(self, 'device_noise', dict(seed=int(seed), calls=int(calls), state=None, rank=0))
+        return self
+
+    def use_host_noise(self):
+        """Back to the reference's draw on the CPU default generator (the default)."""
+        ops.set_model_extra(self, 'device_noise', None)
+        return self
+
+    def device_noise_state(self):
+        """(seed, calls) of the device generator, both in [0, 2^64): calls is the number the NEXT forward will use. One
+        device-to-host copy. Store the pair beside a checkpoint and hand it to use_device_noise() to continue the sequence."""
+        dn = ops.get_model_extra(self, 'device_noise')
+        if dn is None:
+            raise RuntimeError('device noise is not enabled on this model (use_device_noise)')
+        seed, calls = dn['state'].tolist() if dn['state'] is not None else (dn['seed'], dn['calls'])
+        return seed % 2 ** 64, calls % 2 ** 64
+
+    def _device_noise(self, dn, T, n_gated, bs, like):
+        K = get_kernels()
+        if dn['state'] is None or dn['state'].device != like.device:
+            seed, calls = self.device_noise_state()
+            dn['state'] = K.new_noise_state(seed, calls, device=like.device)
+        noise = K.empty(T * n_gated, bs, 2, like=like)
+        return K.gumbel_noise_fill(noise, T, n_gated, bs, dn['rank'] * bs, dn['state'])
+
     def forward(self, x_human, x_objects, objects_mask, human_segmentation=None, objects_segmentation=None,
                 human_human_distances=None, human_object_distances=None, object_object_distances=None,
                 steps_per_example=None, inspect_model=False):
@@ -271,6 +305,9 @@ class TGGCN(nn.Module):
         if plan.gs and n_gated:
             if self._gumbel_noise_override is not None:
                 noise = self._gumbel_noise_override
+            elif ops.get_model_extra(self, 'device_noise') is not None:
+                # opt-in (use_device_noise): one fill launch, no host draw, no copy; clip b of rank r is global clip r * bs + b
+                noise = self._device_noise(ops.get_model_extra(self, 'device_noise'), T, n_gated, bs, x_human)
             elif ops.get_model_extra(self, 'noise_shard') is not None:
                 # data-parallel equivalence mode (distributed.DataParallel(global_noise=True)): every rank draws the noise
                 # of the GLOBAL batch from an identically seeded generator and keeps its own clips

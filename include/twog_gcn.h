@@ -586,6 +586,26 @@ int twog_gate_fwd(const twog_gate_t* g, void* stream);
  * (st_mask NULL => 1; with force_last the last step's d_hard is dropped). */
 int twog_gate_bwd(const twog_gate_t* g, const float* d_hard, const float* d_soft, const float* st_mask, float* dlogit,
                   void* stream);
+/* twog_gumbel_noise_fill: the 'gs' noise drawn on the device instead of on the host's default generator (the reference's
+ * sample_gumbel / gumbel_sigmoid, pyrutils/torch/distributions.py:4-36: g = -log(-log(u)), one (bs, 2) draw per gate call).
+ * Fills noise[T][noise_entities][bs][2], the layout twog_gate_t.noise is read in. The pair at (t, slot, b) is a pure function
+ * of (seed, calls, clip_offset + b, t, slot) and of nothing else -- not of bs, T, noise_entities, the launch geometry or the
+ * rank that holds the clip -- through Philox4x32-10 (Salmon et al., SC'11; 10 rounds):
+ *   multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57; Weyl constants W0 = 0x9E3779B9, W1 = 0xBB67AE85;
+ *   one round: c' = [hi(M1*c2) ^ c1 ^ k0, lo(M1*c2), hi(M0*c0) ^ c3 ^ k1, lo(M0*c0)], then k0 += W0, k1 += W1;
+ *   key     = (low, high 32 bits of state[0])                                   -- the seed
+ *   counter = (calls low, calls high, clip_offset + b, t * 256 + slot)          -- calls = state[1]
+ *   output words w0, w1 (w2, w3 unused): u_i = ((w_i >> 9) + 0.5f) * 2^-23, exact in fp32 and inside [2^-24, 1 - 2^-24];
+ *   g_i = -logf(-logf(u_i)): finite by construction, about [-2.81, 16.64].
+ * state: two DEVICE int64 words [seed, calls]. The fill reads both from the device and the same call then advances calls by
+ * one, behind the fill in stream order (a second, one-thread launch): the host neither reads nor writes the call number, so
+ * the two launches captured into a graph draw the next call's noise at every replay. clip_offset: index of this buffer's clip 0
+ * in the global batch (data parallel: rank * bs). words_or_null: when non-NULL also receives the raw Philox output
+ * [T][noise_entities][bs][4] (the generator checked bit for bit; 16-byte aligned). noise must be 8-byte aligned.
+ * Returns -1 for state == NULL, noise_entities > 256, T >= 2^24, a negative size or a misaligned buffer, -2 for
+ * T * noise_entities * bs >= 2^31. */
+int twog_gumbel_noise_fill(float* noise, int T, int noise_entities, int bs, uint32_t clip_offset, int64_t* state,
+                           uint32_t* words_or_null, void* stream);
 /* dst[r][c] += s[r] * v[c]  (gate input gradient, one call per column block) */
 int twog_rank1_update(twog_rows_t dst, const float* s, const float* v, int rows, int cols, void* stream);
 /* out[c] (+)= sum_r rowscale[r] * x[r][c] (rowscale NULL => 1): bias gradients and gate weight gradients.
