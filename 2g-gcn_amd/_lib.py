@@ -216,6 +216,15 @@ SIGNATURES = {
     'twog_gcn_attn2_fwd': [_P, _P, _I, _I, _P, _P, _P],
     'twog_gcn_attn2_bwd_blocks': [_I],
     'twog_gcn_attn2_bwd': [_P, _P, _P, _P, _I, _I, _P, _P, _I, _P],
+    'twog_gcn_wide_max_nodes': [],
+    'twog_gcn_wide_launch_plan': [_I, _I, _I, C.POINTER(C.c_int)],
+    'twog_gcn_wide_bn_stats': [_P, _L, _I, _I, _P, _I, _P],
+    'twog_gcn_wide_bn_finalize': [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],
+    'twog_gcn_wide_embed1_fwd': [_P, _L, _I, _I, _P, _P, _P, _P, _P],
+    'twog_gcn_wide_embed1_bwd': [_P, _L, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
+    'twog_gcn_wide_input_bwd': [_P, _L, _I, _I, _I, _L, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P],
+    'twog_gcn_wide_fwd': [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    'twog_gcn_wide_bwd': [_P, _P, _P, _P, _I, _I, _P, _P, _I, _P],
     'twog_gru_step_fwd': [C.POINTER(GruStep), _I, _P],
     'twog_gru_step_bwd': [C.POINTER(GruStepBwd), _I, _P],
     'twog_bigru_fwd': [C.POINTER(BiGru), _I, _I, _I, _I, _P, C.c_size_t, _P],

@@ -17,7 +17,10 @@ namespace {
 constexpr int MAX_NODES = 64;
 
 // channel of BatchNorm1d for node n, feature c: c*N + n (models_gcn.py:47); memory position in a frame: n*4 + c
-__global__ __launch_bounds__(256) void bn_stats_kernel(const float* x, int64_t fstride, int n_frames, int N,
+// (CAP = the node cap of the kernel family: 64 for the tuned kernels, 256 for the wide family of geo_wide.hip; one thread per
+// memory position, so the workgroup has 4 * CAP threads)
+template <int CAP>
+__global__ __launch_bounds__(4 * CAP) void bn_stats_kernel(const float* x, int64_t fstride, int n_frames, int N,
                                                        double* partials) {
     const int pos = threadIdx.x;  // n*4 + c
     const int nch = 4 * N;
@@ -51,6 +54,8 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* x, int64_t f
 // projections of compute_similarity (models_gcn.py:95-100) for the fused forward kernel (geo_fused.hip):
 // md_out[n][k] = sum_o Wk[o][n] Wq[o][k] (n, k < 64), md_out[64][n] = sum_o Wk[o][n] bq[o]  (theta_i . phi_j = x_i^T M x_j
 // + d . x_j + terms constant in j) -- 0.5 MFLOP, not worth a launch of its own.
+// CAP = 256 (wide family): 4 CAP = 1024 channels take CAP / 64 workgroups of 256 channels each in front of the md workgroups.
+template <int CAP>
 __global__ __launch_bounds__(1024) void bn_finalize_kernel(const double* partials, int n_blocks, int n_frames, int nch,
                                                            const float* gamma, const float* beta, float* rmean,
                                                            float* rvar, long long* nbt, int training, float* ab,
@@ -58,10 +63,11 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const double* partial
                                                            const float* bq, float* md_out) {
     __shared__ double red[2][4][256];
     __shared__ float mred[16][64];
-    if (blockIdx.x > 0) {
-        // blocks 1 .. 65: row n = blockIdx.x - 1 of md (row 64 = d). Thread = (output k, one of 16 slices of the 128-term sum):
+    constexpr int CHB = CAP / 64;   // workgroups that take 256 channels each
+    if (blockIdx.x >= CHB) {
+        // blocks CHB .. CHB + 64: row n = blockIdx.x - CHB of md (row 64 = d). Thread = (output k, one of 16 slices of the 128-term sum):
         // eight independent loads per operand in flight, the 16 slice sums added in fixed order through LDS
-        const int n = blockIdx.x - 1, k = threadIdx.x & 63, sl = threadIdx.x >> 6;
+        const int n = blockIdx.x - CHB, k = threadIdx.x & 63, sl = threadIdx.x >> 6;
         float a[8], b[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -82,8 +88,8 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const double* partial
         }
         return;
     }
-    const int ch = threadIdx.x & 255, part = threadIdx.x >> 8;
-    if (threadIdx.x == 0 && training && nbt) *nbt += 1;
+    const int cl = threadIdx.x & 255, ch = blockIdx.x * 256 + cl, part = threadIdx.x >> 8;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && training && nbt) *nbt += 1;
     if (training) {
         double s = 0.0, q = 0.0;
         if (ch < nch) {
@@ -103,15 +109,15 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const double* partial
                 q += partials[((int64_t)b * 2 + 1) * nch + ch];
             }
         }
-        red[0][part][ch] = s;
-        red[1][part][ch] = q;
+        red[0][part][cl] = s;
+        red[1][part][cl] = q;
     }
     __syncthreads();
     if (part == 0 && ch < nch) {
         float mean, var;
         if (training) {
-            const double s = (red[0][0][ch] + red[0][1][ch]) + (red[0][2][ch] + red[0][3][ch]);
-            const double q = (red[1][0][ch] + red[1][1][ch]) + (red[1][2][ch] + red[1][3][ch]);
+            const double s = (red[0][0][cl] + red[0][1][cl]) + (red[0][2][cl] + red[0][3][cl]);
+            const double q = (red[1][0][cl] + red[1][1][cl]) + (red[1][2][cl] + red[1][3][cl]);
             const double m = s / n_frames;
             double v = q / n_frames - m * m;
             if (v < 0.0) v = 0.0;
@@ -162,15 +168,16 @@ __global__ __launch_bounds__(256) void embed1_fwd_kernel(const float* x, int64_t
 
 // Backward of embed1 given de1 = dL/d(pre-activation) (already ReLU-masked). Per block partial sums of
 // dW1[64][4], db1[64], da[4N], db[4N] in `partials` (row = block, layout [256 | 64 | 4N | 4N]).
+template <int CAP>
 __global__ __launch_bounds__(256) void embed1_bwd_kernel(const float* x, int64_t fstride, int n_frames, int N,
                                                          const float* ab, const float* w1, const float* de1,
                                                          float* partials) {
     __shared__ float s_dw[4][64][5];           // per wave: dW1[j][0..3], db1[j]
-    __shared__ float s_ab[4][2][4 * MAX_NODES];  // per wave: da[ch], db[ch]
+    __shared__ float s_ab[4][2][4 * CAP];      // per wave: da[ch], db[ch]
     const int j = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nch = 4 * N;
     const float4 w = *reinterpret_cast<const float4*>(w1 + j * 4);
-    for (int i = j; i < 2 * 4 * MAX_NODES; i += 64) (&s_ab[wv][0][0])[i] = 0.f;
+    for (int i = j; i < 2 * 4 * CAP; i += 64) (&s_ab[wv][0][0])[i] = 0.f;
     float dw0 = 0.f, dw1 = 0.f, dw2 = 0.f, dw3 = 0.f, dbj = 0.f;
     const int64_t rows = (int64_t)n_frames * N;
     __syncthreads();
@@ -269,12 +276,13 @@ __device__ __forceinline__ float row16_sum(float v) {
 // reads) get zeros from the same launch. Streaming: 16 lanes take one node's 256 B of de1 as one float4 each (a wave
 // instruction reads 1 KB contiguous), four nodes per group in flight; the 16 partial dot products meet through DPP;
 // lane 0 of the group reads x and writes dx as float4. Fixed summation order, no atomics: bit-reproducible.
+template <int CAP>
 __global__ __launch_bounds__(256) void input_bwd_kernel(const float* x, int64_t fstride, int n_frames, int N, int H,
                                                         int64_t hstride, const float* ab, const float* mean_invstd,
                                                         const float* w1, const float* de1, const float* dgamma,
                                                         const float* dbeta, int training, float* dx) {
     // per memory position n*4 + c: a, mean, invstd, dbeta/M, dgamma/M
-    __shared__ __attribute__((aligned(16))) float s_p[5][4 * MAX_NODES];
+    __shared__ __attribute__((aligned(16))) float s_p[5][4 * CAP];
     const int nch = 4 * N;
     for (int pos = threadIdx.x; pos < nch; pos += blockDim.x) {
         const int ch = (pos & 3) * N + (pos >> 2);
@@ -494,31 +502,37 @@ extern "C" int twog_gcn_launch_plan(int kernel, int n_frames, int n_nodes, int o
     }
 }
 
-extern "C" int twog_bn_stats(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, double* partials,
-                             int n_blocks, void* stream) {
-    if (n_nodes > MAX_NODES || n_nodes < 1) return -1;
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, x_geo, frame_stride,
+// The per-row entry points of both kernel families: CAP = MAX_NODES for the tuned kernels, TWOG_GCN_WIDE_MAX_NODES for the
+// twog_gcn_wide_* twins (same signatures, same semantics; the attention kernels of that family are in geo_wide.hip).
+namespace {
+template <int CAP>
+int bn_stats_launch(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, double* partials, int n_blocks,
+                    void* stream) {
+    if (n_nodes > CAP || n_nodes < 1) return -1;
+    hipLaunchKernelGGL(bn_stats_kernel<CAP>, dim3(n_blocks), dim3(4 * CAP), 0, (hipStream_t)stream, x_geo, frame_stride,
                        n_frames, n_nodes, partials);
     TWOG_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int twog_bn_finalize(const double* partials, int n_blocks, int n_frames, int n_nodes, const float* gamma,
-                                const float* beta, float* running_mean, float* running_var,
-                                int64_t* num_batches_tracked, int training, float* ab, float* mean_invstd,
-                                const float* wq, const float* wk, const float* bq, float* md_out, void* stream) {
-    if (n_nodes > MAX_NODES || n_nodes < 1) return -1;
+template <int CAP>
+int bn_finalize_launch(const double* partials, int n_blocks, int n_frames, int n_nodes, const float* gamma,
+                       const float* beta, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                       int training, float* ab, float* mean_invstd, const float* wq, const float* wk, const float* bq,
+                       float* md_out, void* stream) {
+    if (n_nodes > CAP || n_nodes < 1) return -1;
     if (md_out && !(wq && wk && bq)) return -2;
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(md_out ? 66 : 1), dim3(1024), 0, (hipStream_t)stream, partials, n_blocks, n_frames,
-                       4 * n_nodes, gamma, beta, running_mean, running_var, (long long*)num_batches_tracked, training,
-                       ab, mean_invstd, wq, wk, bq, md_out);
+    hipLaunchKernelGGL(bn_finalize_kernel<CAP>, dim3(CAP / 64 + (md_out ? 65 : 0)), dim3(1024), 0, (hipStream_t)stream, partials,
+                       n_blocks, n_frames, 4 * n_nodes, gamma, beta, running_mean, running_var,
+                       (long long*)num_batches_tracked, training, ab, mean_invstd, wq, wk, bq, md_out);
     TWOG_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int twog_gcn_embed1_fwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes,
-                                   const float* ab, const float* w1, const float* b1, float* e1, void* stream) {
-    if (n_nodes > MAX_NODES || n_nodes < 1) return -1;
+template <int CAP>
+int embed1_fwd_launch(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, const float* ab,
+                      const float* w1, const float* b1, float* e1, void* stream) {
+    if (n_nodes > CAP || n_nodes < 1) return -1;
     const int grid = embed1_fwd_grid((int64_t)n_frames * n_nodes);
     hipLaunchKernelGGL(embed1_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x_geo, frame_stride, n_frames,
                        n_nodes, ab, w1, b1, e1);
@@ -526,13 +540,13 @@ extern "C" int twog_gcn_embed1_fwd(const float* x_geo, int64_t frame_stride, int
     return 0;
 }
 
-extern "C" int twog_gcn_embed1_bwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes,
-                                   const float* ab, const float* mean_invstd, const float* w1, const float* de1,
-                                   float* partials, int n_blocks, float* dw1, float* db1, float* dgamma, float* dbeta,
-                                   void* stream) {
-    if (n_nodes > MAX_NODES || n_nodes < 1) return -1;
+template <int CAP>
+int embed1_bwd_launch(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, const float* ab,
+                      const float* mean_invstd, const float* w1, const float* de1, float* partials, int n_blocks,
+                      float* dw1, float* db1, float* dgamma, float* dbeta, void* stream) {
+    if (n_nodes > CAP || n_nodes < 1) return -1;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(embed1_bwd_kernel, dim3(n_blocks), dim3(256), 0, st, x_geo, frame_stride, n_frames, n_nodes, ab,
+    hipLaunchKernelGGL(embed1_bwd_kernel<CAP>, dim3(n_blocks), dim3(256), 0, st, x_geo, frame_stride, n_frames, n_nodes, ab,
                        w1, de1, partials);
     TWOG_CHECK_LAUNCH();
     hipLaunchKernelGGL(embed1_bwd_final_kernel, dim3((320 + 4 * n_nodes + 63) / 64), dim3(1024), 0, st, partials, n_blocks, 4 * n_nodes,
@@ -541,11 +555,11 @@ extern "C" int twog_gcn_embed1_bwd(const float* x_geo, int64_t frame_stride, int
     return 0;
 }
 
-extern "C" int twog_gcn_input_bwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, int n_humans,
-                                  int64_t human_stride, const float* ab, const float* mean_invstd, const float* w1,
-                                  const float* de1, const float* dgamma, const float* dbeta, int training,
-                                  float* dx_geo, int n_blocks, void* stream) {
-    if (n_nodes > MAX_NODES || n_nodes < 1) return -1;
+template <int CAP>
+int input_bwd_launch(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, int n_humans,
+                     int64_t human_stride, const float* ab, const float* mean_invstd, const float* w1, const float* de1,
+                     const float* dgamma, const float* dbeta, int training, float* dx_geo, int n_blocks, void* stream) {
+    if (n_nodes > CAP || n_nodes < 1) return -1;
     if (!x_geo || !ab || !w1 || !de1 || !dx_geo || n_humans < 1 || n_blocks < 1 || n_frames < 0) return -2;
     if (training && !(mean_invstd && dgamma && dbeta)) return -2;
     // float4 accesses: 16-byte aligned geometry blocks, rows a whole number of float4 apart
@@ -553,11 +567,81 @@ extern "C" int twog_gcn_input_bwd(const float* x_geo, int64_t frame_stride, int 
     if ((frame_stride & 3) || (human_stride & 3) || human_stride < 4 * n_nodes ||
         frame_stride < (int64_t)n_humans * human_stride) return -2;
     if (n_frames == 0) return 0;
-    hipLaunchKernelGGL(input_bwd_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, x_geo, frame_stride,
+    hipLaunchKernelGGL(input_bwd_kernel<CAP>, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, x_geo, frame_stride,
                        n_frames, n_nodes, n_humans, human_stride, ab, mean_invstd, w1, de1, dgamma, dbeta, training,
                        dx_geo);
     TWOG_CHECK_LAUNCH();
     return 0;
+}
+}  // namespace
+
+int twog_internal_embed1_fwd_grid(int64_t rows) { return embed1_fwd_grid(rows); }
+
+extern "C" int twog_bn_stats(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, double* partials,
+                             int n_blocks, void* stream) {
+    return bn_stats_launch<MAX_NODES>(x_geo, frame_stride, n_frames, n_nodes, partials, n_blocks, stream);
+}
+
+extern "C" int twog_bn_finalize(const double* partials, int n_blocks, int n_frames, int n_nodes, const float* gamma,
+                                const float* beta, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                int training, float* ab, float* mean_invstd, const float* wq, const float* wk, const float* bq,
+                                float* md_out, void* stream) {
+    return bn_finalize_launch<MAX_NODES>(partials, n_blocks, n_frames, n_nodes, gamma, beta, running_mean, running_var,
+                                   num_batches_tracked, training, ab, mean_invstd, wq, wk, bq, md_out, stream);
+}
+
+extern "C" int twog_gcn_embed1_fwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, const float* ab,
+                                   const float* w1, const float* b1, float* e1, void* stream) {
+    return embed1_fwd_launch<MAX_NODES>(x_geo, frame_stride, n_frames, n_nodes, ab, w1, b1, e1, stream);
+}
+
+extern "C" int twog_gcn_embed1_bwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, const float* ab,
+                                   const float* mean_invstd, const float* w1, const float* de1, float* partials, int n_blocks,
+                                   float* dw1, float* db1, float* dgamma, float* dbeta, void* stream) {
+    return embed1_bwd_launch<MAX_NODES>(x_geo, frame_stride, n_frames, n_nodes, ab, mean_invstd, w1, de1, partials, n_blocks, dw1,
+                                  db1, dgamma, dbeta, stream);
+}
+
+extern "C" int twog_gcn_input_bwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, int n_humans,
+                                  int64_t human_stride, const float* ab, const float* mean_invstd, const float* w1,
+                                  const float* de1, const float* dgamma, const float* dbeta, int training, float* dx_geo,
+                                  int n_blocks, void* stream) {
+    return input_bwd_launch<MAX_NODES>(x_geo, frame_stride, n_frames, n_nodes, n_humans, human_stride, ab, mean_invstd, w1, de1,
+                                 dgamma, dbeta, training, dx_geo, n_blocks, stream);
+}
+
+// the wide family (n_nodes <= twog_gcn_wide_max_nodes(), include/twog_gcn.h)
+extern "C" int twog_gcn_wide_bn_stats(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, double* partials,
+                                      int n_blocks, void* stream) {
+    return bn_stats_launch<TWOG_GCN_WIDE_MAX_NODES>(x_geo, frame_stride, n_frames, n_nodes, partials, n_blocks, stream);
+}
+
+extern "C" int twog_gcn_wide_bn_finalize(const double* partials, int n_blocks, int n_frames, int n_nodes, const float* gamma,
+                                         const float* beta, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                         int training, float* ab, float* mean_invstd, const float* wq, const float* wk, const float* bq,
+                                         float* md_out, void* stream) {
+    return bn_finalize_launch<TWOG_GCN_WIDE_MAX_NODES>(partials, n_blocks, n_frames, n_nodes, gamma, beta, running_mean, running_var,
+                                   num_batches_tracked, training, ab, mean_invstd, wq, wk, bq, md_out, stream);
+}
+
+extern "C" int twog_gcn_wide_embed1_fwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, const float* ab,
+                                        const float* w1, const float* b1, float* e1, void* stream) {
+    return embed1_fwd_launch<TWOG_GCN_WIDE_MAX_NODES>(x_geo, frame_stride, n_frames, n_nodes, ab, w1, b1, e1, stream);
+}
+
+extern "C" int twog_gcn_wide_embed1_bwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, const float* ab,
+                                        const float* mean_invstd, const float* w1, const float* de1, float* partials, int n_blocks,
+                                        float* dw1, float* db1, float* dgamma, float* dbeta, void* stream) {
+    return embed1_bwd_launch<TWOG_GCN_WIDE_MAX_NODES>(x_geo, frame_stride, n_frames, n_nodes, ab, mean_invstd, w1, de1, partials, n_blocks, dw1,
+                                  db1, dgamma, dbeta, stream);
+}
+
+extern "C" int twog_gcn_wide_input_bwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, int n_humans,
+                                       int64_t human_stride, const float* ab, const float* mean_invstd, const float* w1,
+                                       const float* de1, const float* dgamma, const float* dbeta, int training, float* dx_geo,
+                                       int n_blocks, void* stream) {
+    return input_bwd_launch<TWOG_GCN_WIDE_MAX_NODES>(x_geo, frame_stride, n_frames, n_nodes, n_humans, human_stride, ab, mean_invstd, w1, de1,
+                                 dgamma, dbeta, training, dx_geo, n_blocks, stream);
 }
 
 extern "C" int twog_gcn_attn_fwd(const float* qk, const float* x, int n_frames, int n_nodes, float* s_out, float* z,

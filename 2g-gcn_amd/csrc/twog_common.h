@@ -42,6 +42,10 @@ int twog_internal_gru_fwd_mode(void);   // TWOG_GRU_FWD_FUSION (part of the chai
 int twog_internal_plan_fused_fwd(int n_frames, int n_nodes, int out[4]);
 int twog_internal_plan_attn2(int kernel, int n_frames, int n_nodes, int out[4]);
 
+// the wide family of the geometric-level GCN (geo_wide.hip; its per-row kernels are the second instantiation of geo_gcn.hip's)
+constexpr int TWOG_GCN_WIDE_MAX_NODES = 256;
+int twog_internal_embed1_fwd_grid(int64_t rows);   // geo_gcn.hip: the grid of embed1_fwd_kernel, for both families
+
 // address of row r in a twog_rows_t (see include/twog_gcn.h)
 __device__ __forceinline__ int64_t twog_row_off(const twog_rows_t& m, int r) {
     if (m.inner <= 1) return (int64_t)r * m.ld_outer;

@@ -79,6 +79,7 @@ class HipKernels:
         self.lib = L.load()
         self._ws = {}
         self._tape = None
+        self._force_wide = False   # tests only: the wide GCN family also for n_nodes <= twog_gcn_max_nodes()
 
     # ---------------------------------------------------------------- utilities
     def _stream(self):
@@ -354,6 +355,32 @@ class HipKernels:
         self._check(self.lib.twog_gcn_launch_plan(kernel, n_frames, n_nodes, out), 'twog_gcn_launch_plan')
         return tuple(out)
 
+    # twog_gcn_wide_launch_plan: TWOG_GCN_WIDE_PLAN_* of include/twog_gcn.h
+    WIDE_PLAN_FWD, WIDE_PLAN_BWD, WIDE_PLAN_EMBED1_FWD = range(3)
+
+    def gcn_wide_launch_plan(self, kernel, n_frames, n_nodes):
+        """gcn_launch_plan of the wide family (n_nodes <= twog_gcn_wide_max_nodes()): (grid, frames per trip, dynamic LDS bytes,
+        variant) for `kernel` (WIDE_PLAN_*); host arithmetic of the library, no GPU call."""
+        out = (C.c_int * 4)()
+        self._check(self.lib.twog_gcn_wide_launch_plan(kernel, n_frames, n_nodes, out), 'twog_gcn_wide_launch_plan')
+        return tuple(out)
+
+    def _gcn_wide(self, n_nodes):
+        """Which kernel family the six geometric-level GCN methods below call: the tuned kernels up to twog_gcn_max_nodes(), the
+        wide family (csrc/geo_wide.hip) beyond. The only place where the choice is made."""
+        return self._force_wide or n_nodes > self.lib.twog_gcn_max_nodes()
+
+    def _gcn_entry(self, name, n_nodes):
+        """(entry point, its name) of the tuned kernel `name` or of its twog_gcn_wide_* twin."""
+        if self._gcn_wide(n_nodes):
+            name = self._WIDE_TWIN[name]
+        return getattr(self.lib, name), name
+
+    _WIDE_TWIN = {'twog_bn_stats': 'twog_gcn_wide_bn_stats', 'twog_bn_finalize': 'twog_gcn_wide_bn_finalize',
+                  'twog_gcn_embed1_fwd': 'twog_gcn_wide_embed1_fwd', 'twog_gcn_fused_fwd': 'twog_gcn_wide_fwd',
+                  'twog_gcn_attn2_bwd': 'twog_gcn_wide_bwd', 'twog_gcn_embed1_bwd': 'twog_gcn_wide_embed1_bwd',
+                  'twog_gcn_input_bwd': 'twog_gcn_wide_input_bwd'}
+
     @staticmethod
     def bn_stats_blocks(n_frames):
         """Workgroups of twog_bn_stats: >= 8 frames per block, at most 240 blocks (the finalize kernel sums them 4-wide)."""
@@ -378,24 +405,25 @@ class HipKernels:
         nblk = self.bn_stats_blocks(nf)
         partials = torch.empty(nblk * 2 * nch, dtype=torch.float64, device=dev)
         if training:
-            self._check(self.lib.twog_bn_stats(ptr, fstride, nf, n_nodes, partials.data_ptr(), nblk, self._stream()),
-                        'twog_bn_stats')
+            fn, what = self._gcn_entry('twog_bn_stats', n_nodes)
+            self._check(fn(ptr, fstride, nf, n_nodes, partials.data_ptr(), nblk, self._stream()), what)
             if stats_reduce is not None:
                 partials, nf = stats_reduce(partials.view(nblk, 2 * nch).sum(0), nf)
                 partials, nblk = partials.contiguous(), 1
         md = torch.empty(65, 64, dtype=torch.float32, device=dev) if fold is not None else None
         wq, wk, bq = fold if fold is not None else (None, None, None)
-        self._check(self.lib.twog_bn_finalize(partials.data_ptr(), nblk, nf, n_nodes, gamma.data_ptr(),
-                                              beta.data_ptr(), running_mean.data_ptr(), running_var.data_ptr(),
-                                              _ptr(num_batches_tracked), int(training), ab.data_ptr(), mi.data_ptr(),
-                                              _ptr(wq), _ptr(wk), _ptr(bq), _ptr(md), self._stream()), 'twog_bn_finalize')
+        fn, what = self._gcn_entry('twog_bn_finalize', n_nodes)
+        self._check(fn(partials.data_ptr(), nblk, nf, n_nodes, gamma.data_ptr(), beta.data_ptr(), running_mean.data_ptr(),
+                       running_var.data_ptr(), _ptr(num_batches_tracked), int(training), ab.data_ptr(), mi.data_ptr(),
+                       _ptr(wq), _ptr(wk), _ptr(bq), _ptr(md), self._stream()), what)
         return (ab, mi) if fold is None else (ab, mi, md)
 
     def gcn_embed1_fwd(self, x_human, n_nodes, ab, w1, b1):
         ptr, fstride, nf = self._geo(x_human)
         e1 = torch.empty(nf * n_nodes, 64, dtype=torch.float32, device=x_human.device)
-        self._check(self.lib.twog_gcn_embed1_fwd(ptr, fstride, nf, n_nodes, ab.data_ptr(), w1.data_ptr(),
-                                                 b1.data_ptr(), e1.data_ptr(), self._stream()), 'twog_gcn_embed1_fwd')
+        fn, what = self._gcn_entry('twog_gcn_embed1_fwd', n_nodes)
+        self._check(fn(ptr, fstride, nf, n_nodes, ab.data_ptr(), w1.data_ptr(), b1.data_ptr(), e1.data_ptr(), self._stream()),
+                    what)
         return e1
 
     def gcn_fused_fwd(self, x_human, n_nodes, ab, w1, b1, w2, b2, md, save_x=True):
@@ -405,9 +433,9 @@ class HipKernels:
         X = torch.empty(nf * n_nodes, 64, dtype=torch.float32, device=dev) if save_x else None
         adj = torch.empty(nf, n_nodes, n_nodes, dtype=torch.float32, device=dev)
         Z = torch.empty(nf * n_nodes, 64, dtype=torch.float32, device=dev)
-        self._check(self.lib.twog_gcn_fused_fwd(ptr, fstride, nf, n_nodes, ab.data_ptr(), w1.data_ptr(), b1.data_ptr(),
-                                                w2.data_ptr(), b2.data_ptr(), md.data_ptr(), _ptr(X), adj.data_ptr(),
-                                                Z.data_ptr(), self._stream()), 'twog_gcn_fused_fwd')
+        fn, what = self._gcn_entry('twog_gcn_fused_fwd', n_nodes)
+        self._check(fn(ptr, fstride, nf, n_nodes, ab.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                       md.data_ptr(), _ptr(X), adj.data_ptr(), Z.data_ptr(), self._stream()), what)
         return X, adj, Z
 
     def gcn_embed1_bwd(self, x_human, n_nodes, ab, mean_invstd, w1, de1):
@@ -419,10 +447,10 @@ class HipKernels:
         db1 = torch.empty(64, dtype=torch.float32, device=dev)
         dgamma = torch.empty(4 * n_nodes, dtype=torch.float32, device=dev)
         dbeta = torch.empty(4 * n_nodes, dtype=torch.float32, device=dev)
-        self._check(self.lib.twog_gcn_embed1_bwd(ptr, fstride, nf, n_nodes, ab.data_ptr(), mean_invstd.data_ptr(),
-                                                 w1.data_ptr(), de1.data_ptr(), partials.data_ptr(), nblk,
-                                                 dw1.data_ptr(), db1.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                                 self._stream()), 'twog_gcn_embed1_bwd')
+        fn, what = self._gcn_entry('twog_gcn_embed1_bwd', n_nodes)
+        self._check(fn(ptr, fstride, nf, n_nodes, ab.data_ptr(), mean_invstd.data_ptr(), w1.data_ptr(), de1.data_ptr(),
+                       partials.data_ptr(), nblk, dw1.data_ptr(), db1.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                       self._stream()), what)
         return dw1, db1, dgamma, dbeta
 
     @staticmethod
@@ -439,10 +467,10 @@ class HipKernels:
         assert grad_x_human.shape == x_human.shape and gstride == fstride
         bs, T, H, Fh = x_human.shape
         assert Fh == 2048 + 4 * n_nodes and de1.is_contiguous() and w1.is_contiguous()
-        self._check(self.lib.twog_gcn_input_bwd(ptr, fstride, nf, n_nodes, H, Fh, ab.data_ptr(), _ptr(mean_invstd),
-                                                w1.data_ptr(), de1.data_ptr(), _ptr(dgamma), _ptr(dbeta), int(bool(training)),
-                                                gptr, self.input_bwd_blocks(nf * n_nodes), self._stream()),
-                    'twog_gcn_input_bwd')
+        fn, what = self._gcn_entry('twog_gcn_input_bwd', n_nodes)
+        self._check(fn(ptr, fstride, nf, n_nodes, H, Fh, ab.data_ptr(), _ptr(mean_invstd), w1.data_ptr(), de1.data_ptr(),
+                       _ptr(dgamma), _ptr(dbeta), int(bool(training)), gptr, self.input_bwd_blocks(nf * n_nodes),
+                       self._stream()), what)
         return grad_x_human
 
     def gcn_attn_fwd(self, qk, x, n_frames, n_nodes):
@@ -463,11 +491,14 @@ class HipKernels:
     def gcn_attn2_bwd(self, x, md, s, dz, n_frames, n_nodes):
         """Returns (dx_att [nF*N,64], dmd [65,64] = gradient wrt (Mt | d))."""
         dx = torch.empty(n_frames * n_nodes, 64, dtype=torch.float32, device=x.device)
-        nblk = self.lib.twog_gcn_attn2_bwd_blocks(n_frames)
+        if self._gcn_wide(n_nodes):
+            nblk = self.gcn_wide_launch_plan(self.WIDE_PLAN_BWD, n_frames, n_nodes)[0]
+        else:
+            nblk = self.lib.twog_gcn_attn2_bwd_blocks(n_frames)
         partials = torch.empty(nblk, 65 * 64, dtype=torch.float32, device=x.device)
-        self._check(self.lib.twog_gcn_attn2_bwd(x.data_ptr(), md.data_ptr(), s.data_ptr(), dz.data_ptr(), n_frames,
-                                                n_nodes, dx.data_ptr(), partials.data_ptr(), nblk, self._stream()),
-                    'twog_gcn_attn2_bwd')
+        fn, what = self._gcn_entry('twog_gcn_attn2_bwd', n_nodes)
+        self._check(fn(x.data_ptr(), md.data_ptr(), s.data_ptr(), dz.data_ptr(), n_frames, n_nodes, dx.data_ptr(),
+                       partials.data_ptr(), nblk, self._stream()), what)
         return dx, self.colsum(partials).view(65, 64)
 
     def gcn_attn_bwd(self, qk, x, s, dz, n_frames, n_nodes):

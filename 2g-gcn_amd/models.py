@@ -15,6 +15,8 @@ import torch.nn as nn
 from . import ops
 from .kernels import get_kernels
 
+GCN_MAX_NODES = 256   # twog_gcn_wide_max_nodes() of include/twog_gcn.h (tests/test_gcn_wide_cpu.py holds the two together)
+
 _ACT = {'identity': nn.Identity, 'logsigmoid': nn.LogSigmoid, 'logsoftmax': nn.LogSoftmax, 'relu': nn.ReLU,
         'sigmoid': nn.Sigmoid, 'softmax': nn.Softmax, 'softplus': nn.Softplus, 'tanh': nn.Tanh}
 
@@ -236,6 +238,9 @@ class TGGCN(nn.Module):
         if (c['add_time_position'] or c['add_segment_length']) and c['hidden_size'] % 2 and \
                 c['positional_encoding_style'] not in {'e', 'embedding'}:
             bad.append('periodic position embedding with an odd hidden_size')   # the reference asserts (models.py:1787)
+        if self.gcn_node > GCN_MAX_NODES:
+            bad.append(f'gcn_node = {self.gcn_node} > {GCN_MAX_NODES} (the geometric-level GCN kernels take at most '
+                       f'{GCN_MAX_NODES} nodes: the tuned ones 64, the wide family {GCN_MAX_NODES})')
         self._unsupported = bad
 
     # ---- where the Gumbel noise of the 'gs' gates comes from. The constructor keeps the reference's keywords and state_dict()

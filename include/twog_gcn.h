@@ -170,6 +170,53 @@ int twog_gcn_attn_fwd(const float* qk, const float* x, int n_frames, int n_nodes
 int twog_gcn_attn_bwd(const float* qk, const float* x, const float* s, const float* dz, int n_frames, int n_nodes,
                       float* dx_att, float* dqk, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The wide family of the geometric-level GCN (csrc/geo_wide.hip): the same functions for 1 <= n_nodes <=
+ * twog_gcn_wide_max_nodes() = 256. The reference's Geo_gcn(N, 4, 128) takes any N (models_gcn.py:6-100: conv2d, matmul and
+ * softmax only); the tuned kernels above stop at twog_gcn_max_nodes() = 64. Complete, not tuned: one frame per workgroup trip.
+ * Every entry point returns -1 for n_nodes outside 1 .. twog_gcn_wide_max_nodes() before anything is launched. */
+int twog_gcn_wide_max_nodes(void);
+/* As twog_gcn_launch_plan for the wide kernels: out = {grid, frames per trip (1), dynamic LDS bytes, variant}; variant of FWD =
+ * the column tiles of 16 senders a strip of receivers can hold in its accumulators (4, 8, 12 or 16: the kernel instance),
+ * otherwise 0; EMBED1_FWD: {grid, 1, 0, 0}. Host arithmetic only; the launchers use the same code. Returns 0, -1 for n_nodes outside
+ * 1 .. twog_gcn_wide_max_nodes(), -2 for an unknown kernel. */
+#define TWOG_GCN_WIDE_PLAN_FWD 0         /* twog_gcn_wide_fwd */
+#define TWOG_GCN_WIDE_PLAN_BWD 1         /* twog_gcn_wide_bwd (grid = the n_blocks it must be given) */
+#define TWOG_GCN_WIDE_PLAN_EMBED1_FWD 2  /* twog_gcn_wide_embed1_fwd */
+int twog_gcn_wide_launch_plan(int kernel, int n_frames, int n_nodes, int out[4]);
+/* twog_bn_stats for up to 256 nodes (norm_data, models_gcn.py:43-49): partials[n_blocks][2][4N], fp64. */
+int twog_gcn_wide_bn_stats(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, double* partials,
+                           int n_blocks, void* stream);
+/* twog_bn_finalize for up to 256 nodes = 1024 BatchNorm channels (models_gcn.py:43-50; torch BatchNorm1d running-statistics
+ * rules; md_out != NULL: the fold of compute_similarity, models_gcn.py:95-100, in the same launch). */
+int twog_gcn_wide_bn_finalize(const double* partials, int n_blocks, int n_frames, int n_nodes, const float* gamma,
+                              const float* beta, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                              int training, float* ab, float* mean_invstd, const float* wq, const float* wk,
+                              const float* bq, float* md_out, void* stream);
+/* twog_gcn_embed1_fwd for up to 256 nodes (models_gcn.py:57-59). */
+int twog_gcn_wide_embed1_fwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, const float* ab,
+                             const float* w1, const float* b1, float* e1, void* stream);
+/* twog_gcn_embed1_bwd for up to 256 nodes (backward of models_gcn.py:45-59); partials: scratch [n_blocks][320 + 8N]. */
+int twog_gcn_wide_embed1_bwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, const float* ab,
+                             const float* mean_invstd, const float* w1, const float* de1, float* partials, int n_blocks,
+                             float* dw1, float* db1, float* dgamma, float* dbeta, void* stream);
+/* twog_gcn_input_bwd for up to 256 nodes (the split at vhoi/models.py:636-639, models_gcn.py:45-59), train and eval forms,
+ * same argument checks and return codes. */
+int twog_gcn_wide_input_bwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, int n_humans,
+                            int64_t human_stride, const float* ab, const float* mean_invstd, const float* w1,
+                            const float* de1, const float* dgamma, const float* dbeta, int training, float* dx_geo,
+                            int n_blocks, void* stream);
+/* The contract of twog_gcn_fused_fwd (models_gcn.py:30-34, :45-50, :57-63, :95-100): BN fold, 4 -> 64 ReLU, 64 -> 64 ReLU,
+ * P = X Mt + d, S = softmax_j (no 1/sqrt(d)), Z = S X. Outputs x_out [(f,n)][64] (NULL ok), adj [f][N][N], z [(f,n)][64]. */
+int twog_gcn_wide_fwd(const float* x_geo, int64_t frame_stride, int n_frames, int n_nodes, const float* ab,
+                      const float* w1, const float* b1, const float* w2, const float* b2, const float* md, float* x_out,
+                      float* adj, float* z, void* stream);
+/* The contract of twog_gcn_attn2_bwd (backward of models_gcn.py:95-100, :33-34): dx_att [(f,n)][64] and per-workgroup sums
+ * partials [n_blocks][65*64] of (dMt | dd), n_blocks = out[0] of twog_gcn_wide_launch_plan(TWOG_GCN_WIDE_PLAN_BWD) (-2
+ * otherwise); the caller column-sums them (twog_colsum). Fixed summation order, no atomics: bit-reproducible. */
+int twog_gcn_wide_bwd(const float* x, const float* md, const float* adj, const float* dz, int n_frames, int n_nodes,
+                      float* dx_att, float* partials, int n_blocks, void* stream);
+
 /* ===============================================================================================================
  * GRU gate math (torch.nn.GRU / GRUCell semantics, gate order r,z,n) for the frame-level BiGRUs
  * (vhoi/models.py:983-1002) and the gated segment-level step h_t = u*GRUCell(x,h) + (1-u)*h (vhoi/models.py:1535-1564).
