@@ -283,6 +283,7 @@ SIGNATURES = {
     'twog_copy_blocks': [C.POINTER(Copy), _I, _P],
     'twog_debug_occupy': [_I, _I, _I, _P],
     'twog_adam_step': [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P],
+    'twog_stream_grid': [_I, _L, _L],
     'twog_multitask_loss_fwd': [C.POINTER(Loss), _I, _P, _P, _P, _P],
     'twog_multitask_loss_bwd': [C.POINTER(Loss), _I, _P, _P, _P],
     'twog_grad_norm': [_P, C.POINTER(Ranges), _F, _F, _P, _P, _P],

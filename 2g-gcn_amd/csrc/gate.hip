@@ -242,14 +242,12 @@ extern "C" int twog_rank1_update(twog_rows_t dst, const float* s, const float* v
     if (rows <= 0 || cols <= 0) return 0;
     if ((cols & 3) == 0 && (reinterpret_cast<uintptr_t>(dst.ptr) & 15) == 0 && (reinterpret_cast<uintptr_t>(v) & 15) == 0 &&
         (dst.ld_outer & 3) == 0 && (dst.inner <= 1 || (dst.ld_inner & 3) == 0) && (int64_t)rows * (cols >> 2) < (int64_t(1) << 31)) {
-        const int64_t nq = (int64_t)rows * (cols >> 2);
-        const int grid = (int)((nq + 255) / 256 > 8192 ? 8192 : (nq + 255) / 256);
+        const int grid = twog_stream_blocks(TWOG_STREAM_RANK1_VEC, (int64_t)rows * cols);
         hipLaunchKernelGGL(rank1_vec_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dst, s, v, rows, cols >> 2);
         TWOG_CHECK_LAUNCH();
         return 0;
     }
-    int64_t n = (int64_t)rows * cols;
-    int grid = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
+    const int grid = twog_stream_blocks(TWOG_STREAM_RANK1, (int64_t)rows * cols);
     hipLaunchKernelGGL(rank1_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dst, s, v, rows, cols);
     TWOG_CHECK_LAUNCH();
     return 0;

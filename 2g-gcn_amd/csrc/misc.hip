@@ -172,13 +172,6 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
     }
 }
 
-inline int grid_for(int64_t n, int block = 256, int cap = 4096) {
-    int64_t g = (n + block - 1) / block;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 inline bool rows_vec_ok(const twog_rows_t& m) {
     return (reinterpret_cast<uintptr_t>(m.ptr) % 16 == 0) && (m.ld_outer % 4 == 0) &&
            (m.inner <= 1 || m.ld_inner % 4 == 0);
@@ -189,12 +182,10 @@ inline bool rows_vec_ok(const twog_rows_t& m) {
 extern "C" int twog_relu_bwd(twog_rows_t dy, twog_rows_t y, twog_rows_t dx, int rows, int cols, void* stream) {
     if (rows <= 0 || cols <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    if (cols % 4 == 0 && rows_vec_ok(dy) && rows_vec_ok(y) && rows_vec_ok(dx))
-        hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for((int64_t)rows * cols / 4)), dim3(256), 0, st, dy, y, dx, rows,
-                           cols);
-    else
-        hipLaunchKernelGGL(relu_bwd_scalar_kernel, dim3(grid_for((int64_t)rows * cols)), dim3(256), 0, st, dy, y, dx,
-                           rows, cols);
+    const bool vec = cols % 4 == 0 && rows_vec_ok(dy) && rows_vec_ok(y) && rows_vec_ok(dx);
+    const int grid = twog_stream_blocks(vec ? TWOG_STREAM_RELU_BWD_VEC : TWOG_STREAM_RELU_BWD, (int64_t)rows * cols);
+    if (vec) hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid), dim3(256), 0, st, dy, y, dx, rows, cols);
+    else hipLaunchKernelGGL(relu_bwd_scalar_kernel, dim3(grid), dim3(256), 0, st, dy, y, dx, rows, cols);
     TWOG_CHECK_LAUNCH();
     return 0;
 }
@@ -218,7 +209,8 @@ extern "C" int twog_rowops(const twog_rowop_t* ops, int n_ops, void* stream) {
             if (n > most) most = n;
         }
         if (most == 0) continue;
-        hipLaunchKernelGGL(rowops_kernel, dim3(grid_for(most, 256, 1024), m), dim3(256), 0, (hipStream_t)stream, G);
+        const int grid = twog_stream_blocks(TWOG_STREAM_ROWOPS, most);
+        hipLaunchKernelGGL(rowops_kernel, dim3(grid, m), dim3(256), 0, (hipStream_t)stream, G);
         TWOG_CHECK_LAUNCH();
     }
     return 0;
@@ -226,8 +218,8 @@ extern "C" int twog_rowops(const twog_rowop_t* ops, int n_ops, void* stream) {
 
 extern "C" int twog_add_rows(twog_rows_t src, twog_rows_t dst, int rows, int cols, void* stream) {
     if (rows <= 0 || cols <= 0) return 0;
-    hipLaunchKernelGGL(add_rows_kernel, dim3(grid_for((int64_t)rows * cols)), dim3(256), 0, (hipStream_t)stream, src,
-                       dst, rows, cols);
+    const int grid = twog_stream_blocks(TWOG_STREAM_ADD_ROWS, (int64_t)rows * cols);
+    hipLaunchKernelGGL(add_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, dst, rows, cols);
     TWOG_CHECK_LAUNCH();
     return 0;
 }
@@ -258,6 +250,12 @@ static int reorder_chunks(int pairs, int cols) {
     const int most = cols / 64 > 0 ? cols / 64 : 1;
     if (n > most) n = most;
     return n < 1 ? 1 : n;
+}
+
+extern "C" int twog_stream_grid(int kernel, int64_t work, int64_t cols) {
+    if (kernel != TWOG_STREAM_REORDER) return twog_stream_blocks(kernel, work);
+    if (work < 0 || work > INT32_MAX || cols < 0 || cols > INT32_MAX) return -2;
+    return work == 0 ? 1 : reorder_chunks((int)work, (int)cols);
 }
 
 extern "C" int twog_reorder_fwd(const float* hx, const float* gate, float* out, int bs, int T, int E, int cols,
@@ -308,9 +306,8 @@ __global__ __launch_bounds__(256) void fill_zero_kernel(char* p, size_t nbytes) 
 extern "C" int twog_fill_zero(void* p, size_t nbytes, void* stream) {
     if (nbytes == 0) return 0;
     if (!p) return -2;
-    const size_t body = nbytes / 16;
-    const size_t want = (body + 255) / 256;
-    const unsigned blocks = (unsigned)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
+    if (nbytes > (size_t)INT64_MAX) return -2;
+    const unsigned blocks = (unsigned)twog_stream_blocks(TWOG_STREAM_FILL_ZERO, (int64_t)nbytes);
     hipLaunchKernelGGL(fill_zero_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<char*>(p), nbytes);
     TWOG_CHECK_LAUNCH();
     return 0;
@@ -343,8 +340,8 @@ extern "C" int twog_copy_blocks(const twog_copy_t* blocks, int n_blocks, void* s
         if (blocks[i].n > most) most = blocks[i].n;
     }
     if (most == 0) return 0;
-    hipLaunchKernelGGL(copy_blocks_kernel, dim3(grid_for((most + 3) / 4, 256, 512), n_blocks), dim3(256), 0,
-                       (hipStream_t)stream, G);
+    const int grid = twog_stream_blocks(TWOG_STREAM_COPY_BLOCKS, most);
+    hipLaunchKernelGGL(copy_blocks_kernel, dim3(grid, n_blocks), dim3(256), 0, (hipStream_t)stream, G);
     TWOG_CHECK_LAUNCH();
     return 0;
 }
@@ -432,8 +429,9 @@ extern "C" int twog_adam_step(float* param, const float* grad, float* exp_avg, f
     if (n <= 0) return 0;
     const float bc1 = 1.f - powf(beta1, (float)step);
     const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, param, grad,
-                       exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale);
+    const int grid = twog_stream_blocks(TWOG_STREAM_ADAM, n);
+    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr,
+                       beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale);
     TWOG_CHECK_LAUNCH();
     return 0;
 }

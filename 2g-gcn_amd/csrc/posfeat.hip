@@ -108,11 +108,6 @@ __global__ __launch_bounds__(256) void scale_rows_kernel(twog_rows_t x, const fl
     }
 }
 
-inline int grid_for(int64_t n) {
-    int64_t g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
-
 }  // namespace
 
 extern "C" int twog_pos_embed_fwd(const float* s, const float* steps, int bs, int T, int E, int divide, const float* w,
@@ -159,15 +154,16 @@ extern "C" int twog_seglen_bwd(const float* u, const float* steps, int bs, int T
 
 extern "C" int twog_mul(const float* a, const float* b, float* out, int64_t n, int accumulate, void* stream) {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(mul_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, a, b, out, n, accumulate);
+    const int grid = twog_stream_blocks(TWOG_STREAM_MUL, n);
+    hipLaunchKernelGGL(mul_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, b, out, n, accumulate);
     TWOG_CHECK_LAUNCH();
     return 0;
 }
 
 extern "C" int twog_scale_rows(twog_rows_t x, const float* s, int rows, int cols, void* stream) {
     if (rows <= 0 || cols <= 0) return 0;
-    hipLaunchKernelGGL(scale_rows_kernel, dim3(grid_for((int64_t)rows * cols)), dim3(256), 0, (hipStream_t)stream, x, s,
-                       rows, cols);
+    const int grid = twog_stream_blocks(TWOG_STREAM_SCALE_ROWS, (int64_t)rows * cols);
+    hipLaunchKernelGGL(scale_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, s, rows, cols);
     TWOG_CHECK_LAUNCH();
     return 0;
 }

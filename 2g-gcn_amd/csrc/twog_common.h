@@ -46,6 +46,30 @@ int twog_internal_plan_attn2(int kernel, int n_frames, int n_nodes, int out[4]);
 constexpr int TWOG_GCN_WIDE_MAX_NODES = 256;
 int twog_internal_embed1_fwd_grid(int64_t rows);   // geo_gcn.hip: the grid of embed1_fwd_kernel, for both families
 
+// The capped grid of a grid-stride streaming kernel (TWOG_STREAM_* of include/twog_gcn.h) for `work` items: the launchers of
+// misc.hip / gate.hip / posfeat.hip launch with exactly this number and twog_stream_grid (misc.hip) reports it. -2 = unknown.
+inline int twog_stream_blocks(int kernel, int64_t work) {
+    if (work < 0) return -2;
+    int64_t items = work, cap;
+    switch (kernel) {
+        case TWOG_STREAM_RELU_BWD_VEC: items = work / 4; cap = 4096; break;
+        case TWOG_STREAM_RELU_BWD:
+        case TWOG_STREAM_ADD_ROWS:
+        case TWOG_STREAM_RANK1: cap = 4096; break;
+        case TWOG_STREAM_RANK1_VEC: items = work / 4; cap = 8192; break;
+        case TWOG_STREAM_ROWOPS: cap = 1024; break;
+        case TWOG_STREAM_ADAM: cap = 2048; break;
+        case TWOG_STREAM_MUL:
+        case TWOG_STREAM_SCALE_ROWS: cap = 8192; break;
+        case TWOG_STREAM_COPY_BLOCKS: items = (work + 3) / 4; cap = 512; break;
+        case TWOG_STREAM_FILL_ZERO: items = work / 16; cap = 4096; break;
+        default: return -2;
+    }
+    int64_t g = (items + TWOG_STREAM_THREADS - 1) / TWOG_STREAM_THREADS;
+    if (g > cap) g = cap;
+    return (int)(g < 1 ? 1 : g);
+}
+
 // address of row r in a twog_rows_t (see include/twog_gcn.h)
 __device__ __forceinline__ int64_t twog_row_off(const twog_rows_t& m, int r) {
     if (m.inner <= 1) return (int64_t)r * m.ld_outer;

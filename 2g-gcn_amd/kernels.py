@@ -169,6 +169,20 @@ class HipKernels:
             HipKernels._side_streams[key] = st
         return HipKernels._Side(st) if st else None
 
+    # twog_stream_grid: TWOG_STREAM_* of include/twog_gcn.h
+    (STREAM_RELU_BWD_VEC, STREAM_RELU_BWD, STREAM_ADD_ROWS, STREAM_RANK1_VEC, STREAM_RANK1, STREAM_ROWOPS, STREAM_ADAM,
+     STREAM_MUL, STREAM_SCALE_ROWS, STREAM_COPY_BLOCKS, STREAM_FILL_ZERO, STREAM_REORDER) = range(12)
+    STREAM_THREADS = 256   # TWOG_STREAM_THREADS
+
+    def stream_grid(self, kernel, work, cols=0):
+        """Workgroups the launcher of the capped grid-stride kernel `kernel` (STREAM_*) uses for `work` items (elements; bytes for
+        STREAM_FILL_ZERO); STREAM_REORDER: the column chunks for `work` (clip, entity) pairs of `cols` columns. Host arithmetic of
+        the library, no GPU call."""
+        g = self.lib.twog_stream_grid(int(kernel), int(work), int(cols))
+        if g < 0:
+            raise RuntimeError(f'twog_stream_grid failed with code {g}')
+        return g
+
     def debug_occupy(self, n_blocks, lds_bytes, usec):
         """Diagnostics (tests): n_blocks workgroups holding lds_bytes of LDS each for usec microseconds on the current stream."""
         self._check(self.lib.twog_debug_occupy(n_blocks, lds_bytes, usec, self._stream()), 'twog_debug_occupy')
@@ -1096,8 +1110,12 @@ class HipKernels:
                                               self._stream()), 'twog_reorder_bwd')
         return dhx
 
-    def logsoftmax_permute_fwd(self, logits, bs, T, E, Cn):
-        out = torch.empty(bs, Cn, T, E, dtype=torch.float32, device=logits.device)
+    def logsoftmax_permute_fwd(self, logits, bs, T, E, Cn, out=None):
+        """out: a caller-owned (bs, Cn, T, E) buffer. The product never passes one; the parameter exists so that a test can
+        hand in a poisoned buffer and see that every position is written and nothing behind the last."""
+        if out is None:
+            out = torch.empty(bs, Cn, T, E, dtype=torch.float32, device=logits.device)
+        assert out.is_contiguous() and out.shape == (bs, Cn, T, E) and out.dtype == torch.float32
         self._check(self.lib.twog_logsoftmax_permute_fwd(logits.data_ptr(), out.data_ptr(), bs, T, E, Cn,
                                                          self._stream()), 'twog_logsoftmax_permute_fwd')
         return out

@@ -771,6 +771,34 @@ int twog_copy_blocks(const twog_copy_t* blocks, int n_blocks, void* stream);
 int twog_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                    float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream);
 
+/* The launch geometry of the small streaming kernels that launch a CAPPED grid of TWOG_STREAM_THREADS-thread workgroups and
+ * stride over the rest of the work. Host arithmetic only -- no GPU call; the launchers take their grid from the same function,
+ * so the answer is what is launched. Returns the number of workgroups along x for `work` items: elements (rows * cols, the
+ * largest operation of a twog_rowops call, the largest block of a twog_copy_blocks call) or, for FILL_ZERO, bytes. A thread
+ * takes `per` = one element per trip, four in the _VEC kernels and COPY_BLOCKS, 16 bytes in FILL_ZERO. Some thread of the main
+ * loop is SURE to make a second trip when  grid * TWOG_STREAM_THREADS * per  <  work - slack:  slack = 0 for the one-element
+ * kernels (there the condition is also necessary); 3 for the _VEC kernels and COPY_BLOCKS, which stride over whole groups of
+ * four (work / 4, rounded down; the n % 4 tail of a copy is a loop of its own); 30 for FILL_ZERO, whose 16-byte body excludes
+ * up to 15 head bytes in front of the first 16-byte boundary and the bytes behind the last. A copy whose source or destination
+ * is not 16-byte aligned takes one float per thread and trip on the same grid, so it makes further trips from a quarter of
+ * that size on. `cols` is read by TWOG_STREAM_REORDER only: work = (clip, entity) pairs, the result = the column chunks
+ * (gridDim.y) of twog_reorder_fwd / _bwd (1 for no pairs). -2 for an unknown kernel, negative work, or, with
+ * TWOG_STREAM_REORDER, work or cols beyond INT32_MAX or negative cols. */
+#define TWOG_STREAM_THREADS 256
+#define TWOG_STREAM_RELU_BWD_VEC 0  /* twog_relu_bwd, 16-byte form (cols % 4 == 0, aligned rows) */
+#define TWOG_STREAM_RELU_BWD 1      /* twog_relu_bwd, scalar form */
+#define TWOG_STREAM_ADD_ROWS 2      /* twog_add_rows */
+#define TWOG_STREAM_RANK1_VEC 3     /* twog_rank1_update, 16-byte form */
+#define TWOG_STREAM_RANK1 4         /* twog_rank1_update, scalar form */
+#define TWOG_STREAM_ROWOPS 5        /* twog_rowops (per launch of up to 16 operations) */
+#define TWOG_STREAM_ADAM 6          /* twog_adam_step */
+#define TWOG_STREAM_MUL 7           /* twog_mul */
+#define TWOG_STREAM_SCALE_ROWS 8    /* twog_scale_rows */
+#define TWOG_STREAM_COPY_BLOCKS 9   /* twog_copy_blocks */
+#define TWOG_STREAM_FILL_ZERO 10    /* twog_fill_zero */
+#define TWOG_STREAM_REORDER 11      /* twog_reorder_fwd / twog_reorder_bwd: column chunks */
+int twog_stream_grid(int kernel, int64_t work, int64_t cols);
+
 /* Adjacency attention of Geo_gcn (compute_similarity + s.matmul(x), pyrutils/torch/models_gcn.py:86-100, :30-34) on the
  * matrix cores with the theta / phi projections folded: md = [65][64] = Mt (Mt[n][k] = sum_o Wk[o][n] Wq[o][k]) followed
  * by d = Wk^T bq; per frame P = X M + d, adj = softmax_j(P X^T), z = adj X (identical to softmax(theta phi^T) X: the

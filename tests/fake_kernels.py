@@ -40,6 +40,23 @@ class FakeKernels:
             for s, d in pairs:
                 d.view(-1).copy_(s.detach().reshape(-1))
 
+    def fill_zero(self, t):
+        assert t.is_contiguous()
+        return t.zero_()
+
+    # HipKernels.stream_grid: the launch-free plan twog_stream_grid of the library itself (host arithmetic, no device is
+    # opened), so that no cap is copied under tests/. What the plan promises -- the launchers launch with its answer -- is
+    # what tests/test_stream_kernels_gpu.py shows: a kernel that did not stride would leave the rest of a capped case unwritten.
+    (STREAM_RELU_BWD_VEC, STREAM_RELU_BWD, STREAM_ADD_ROWS, STREAM_RANK1_VEC, STREAM_RANK1, STREAM_ROWOPS, STREAM_ADAM,
+     STREAM_MUL, STREAM_SCALE_ROWS, STREAM_COPY_BLOCKS, STREAM_FILL_ZERO, STREAM_REORDER) = range(12)
+    STREAM_THREADS = 256
+
+    def stream_grid(self, kernel, work, cols=0):
+        from twog_gcn_amd import _lib
+        g = _lib.load().twog_stream_grid(int(kernel), int(work), int(cols))
+        assert g >= 0, (kernel, work, cols, g)
+        return g
+
     def tape_begin(self):
         assert self._tape is None
         self._tape = []
@@ -668,8 +685,9 @@ class FakeKernels:
         idx = self._reorder_idx(gate)
         return torch.zeros_like(dout).scatter_add_(1, idx.unsqueeze(-1).expand_as(dout), dout)
 
-    def logsoftmax_permute_fwd(self, logits, bs, T, E, Cn):
-        return torch.log_softmax(logits.view(bs, T, E, Cn), -1).permute(0, 3, 1, 2).contiguous()
+    def logsoftmax_permute_fwd(self, logits, bs, T, E, Cn, out=None):
+        r = torch.log_softmax(logits.view(bs, T, E, Cn), -1).permute(0, 3, 1, 2).contiguous()
+        return r if out is None else out.copy_(r)
 
     def logsoftmax_permute_bwd(self, out, dout):
         o = out.permute(0, 2, 3, 1)
@@ -847,7 +865,7 @@ class FakeKernels:
         s = s.reshape(-1).clone()
         x = s.view(-1, 1)
         if periodic:
-            wk = torch.tensor([1e4]) ** torch.linspace(0, 1, hidden // 2)
+            wk = torch.tensor([1e4], dtype=out.dtype) ** torch.linspace(0, 1, hidden // 2, dtype=out.dtype)
             v = torch.cat([torch.sin(x / wk), torch.cos(x / wk)], dim=-1)
         else:
             v = torch.relu(x * w.view(1, -1) + (b.view(1, -1) if b is not None else 0.0))
@@ -857,7 +875,7 @@ class FakeKernels:
     def periodic_embed_bwd(self, dout, s):
         hidden = dout.shape[-1]
         half = hidden // 2
-        wk = torch.tensor([1e4]) ** torch.linspace(0, 1, half)
+        wk = torch.tensor([1e4], dtype=dout.dtype) ** torch.linspace(0, 1, half, dtype=dout.dtype)
         x = s.view(-1, 1)
         d = _mat(dout)
         return ((d[:, :half] * torch.cos(x / wk) - d[:, half:] * torch.sin(x / wk)) / wk).sum(-1)
