@@ -558,6 +558,8 @@ int twog_ssp_bwd(const float* dgi, const float* ph, const float* att, const floa
  *              = 1 / max(#valid senders, 1)          (TWOG_REL_MEAN)
  * over the valid senders (send_mask != 0, and s != r when exclude_self); no valid sender -> all-zero weights (the
  * reference's NaN -> 0). Rows of one instance must be equally strided (inner <= 1 or inner == R resp. S).
+ * No receivers (R == 0, or n_inst <= 0): a descriptor that passes the checks is a no-op in every entry point below, also
+ * inside a multi-descriptor call: no buffer is read or written, gradient buffers that do not accumulate are NOT cleared.
  * =============================================================================================================== */
 #define TWOG_REL_SUM 0
 #define TWOG_REL_DOT 1

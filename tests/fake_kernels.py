@@ -755,13 +755,14 @@ class FakeKernels:
         """Specification of twog_relation_fwd as differentiable torch code (leaf: dict of tensors to differentiate)."""
         nI, ipc, R, S = d['n_inst'], d['inst_per_clip'], d['R'], d['S']
         g = lambda k: (leaf or {}).get(k, d.get(k))
-        valid = torch.ones(nI, R, S)
-        mval = torch.ones(nI, 1, S)
+        dt = d['out'].dtype   # fp32, or fp64 when the whole descriptor is (tests/relation_cases.py)
+        valid = torch.ones(nI, R, S, dtype=dt)
+        mval = torch.ones(nI, 1, S, dtype=dt)
         if d.get('send_mask') is not None:
             mval = d['send_mask'].repeat_interleave(ipc, 0).view(nI, 1, S)
-            valid = valid * (mval != 0).float()
+            valid = valid * (mval != 0).to(dt)
         if d.get('exclude_self'):
-            valid = valid * (1 - torch.eye(R, S)).view(1, R, S)
+            valid = valid * (1 - torch.eye(R, S, dtype=dt)).view(1, R, S)
         mode = d['score_mode']
         if mode == self.REL_DOT:
             q, k = self._rel_rows(g('q'), nI, R), self._rel_rows(g('k'), nI, S)
@@ -773,7 +774,7 @@ class FakeKernels:
             sc = torch.relu(g('a_r').view(nI, R, 1) + g('c_s').view(nI, 1, S))
         elif mode == self.REL_DISTANCE:
             dist = d['dist']
-            valid = valid * (dist != 0).float()
+            valid = valid * (dist != 0).to(dt)
             sc = 1.0 / (dist + 1e-7)
         else:
             sc = None
@@ -795,6 +796,8 @@ class FakeKernels:
         return out, w
 
     def relation_fwd(self, d):
+        if d['R'] == 0:   # no receivers: no buffer is read or written (include/twog_gcn.h at twog_relation_t)
+            return
         out, w = self._rel_forward(d)
         d['out'].copy_(out.reshape(d['out'].shape))
         if d.get('att') is not None:
@@ -824,6 +827,8 @@ class FakeKernels:
 
     def relation_bwd(self, b):
         d = b['f']
+        if d['R'] == 0:   # no receivers: no buffer is read or written, gradient buffers that do not accumulate included
+            return
         keys = [k for k in ('q', 'k', 'msg', 'p_r', 'p_s', 'a_r', 'c_s', 'score_bias') if d.get(k) is not None]
         leaf = {k: d[k].detach().clone().requires_grad_(True) for k in keys}
         if d.get('q') is not None and d.get('k') is not None and d['q'].data_ptr() == d['k'].data_ptr() and \
