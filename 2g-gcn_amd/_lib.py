@@ -227,6 +227,7 @@ SIGNATURES = {
     'twog_gcn_wide_bwd': [_P, _P, _P, _P, _I, _I, _P, _P, _I, _P],
     'twog_gru_step_fwd': [C.POINTER(GruStep), _I, _P],
     'twog_gru_step_bwd': [C.POINTER(GruStepBwd), _I, _P],
+    'twog_gru_step_last_path': [],
     'twog_bigru_fwd': [C.POINTER(BiGru), _I, _I, _I, _I, _P, C.c_size_t, _P],
     'twog_bigru_persistent_supported': [C.POINTER(BiGru), _I, _I, _I],
     'twog_bigru_fwd_persistent': [C.POINTER(BiGru), _I, _I, _I, _I, _P, _P],

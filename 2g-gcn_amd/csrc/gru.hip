@@ -25,6 +25,19 @@ __device__ __forceinline__ float gate_u(const float* u, int64_t ldo, int64_t ldi
     return u[(int64_t)o * ldo + (int64_t)(r - o * inner) * ldi];
 }
 
+// One hidden unit of the gated step, for both forward kernels below. Every multiply-add is written out and the compiler may
+// not regroup them (contraction off): the scalar and the 16-byte kernel then round alike whatever the code around the call
+// looks like. Left to the compiler, the two kernels contracted (1 - z) * n + z * h0 differently and were NOT bit-identical.
+__device__ __forceinline__ float gru_gate_unit(float ir, float iz, float in_, float hr, float hz, float hn, float h0, bool has_u,
+                                               float uu, float& rg, float& z, float& n) {
+#pragma clang fp contract(off)
+    rg = 1.0f / (1.0f + expf(-(ir + hr)));
+    z = 1.0f / (1.0f + expf(-(iz + hz)));
+    n = tanhf(fmaf(rg, hn, in_));
+    const float gnew = fmaf(z, h0, (1.0f - z) * n);
+    return has_u ? fmaf(uu, gnew, (1.0f - uu) * h0) : gnew;
+}
+
 __global__ __launch_bounds__(256) void gru_step_fwd_kernel(const FwdGroup g) {
     const twog_gru_step_t& S = g.s[blockIdx.y];
     const int r = blockIdx.x;
@@ -46,12 +59,9 @@ __global__ __launch_bounds__(256) void gru_step_fwd_kernel(const FwdGroup g) {
             in_ += gi2[2 * H + j];
         }
         const float hr = gh[j], hz = gh[H + j], hn = gh[2 * H + j];
-        const float rg = 1.0f / (1.0f + expf(-(ir + hr)));
-        const float z = 1.0f / (1.0f + expf(-(iz + hz)));
-        const float n = tanhf(in_ + rg * hn);
         const float h0 = hp ? hp[j] : 0.f;
-        const float gnew = (1.0f - z) * n + z * h0;
-        ho[j] = S.u ? uu * gnew + (1.0f - uu) * h0 : gnew;
+        float rg, z, n;
+        ho[j] = gru_gate_unit(ir, iz, in_, hr, hz, hn, h0, S.u != nullptr, uu, rg, z, n);
         if (sv) {
             sv[j] = rg;
             sv[H + j] = z;
@@ -62,7 +72,7 @@ __global__ __launch_bounds__(256) void gru_step_fwd_kernel(const FwdGroup g) {
 }
 
 // The same step, four hidden units per thread (16-byte accesses; round 6): the launch of the segment level's forward chain
-// at a real batch moves 39 MB per step and was at 3.4 TB/s with scalar accesses. Same arithmetic per element: bit-identical.
+// at a real batch moves 39 MB per step and was at 3.4 TB/s with scalar accesses. Same arithmetic per element (gru_gate_unit): bit-identical.
 // Host-side condition: hidden % 4 == 0, hidden / 4 <= 256, every row pointer 16-byte aligned (gru_step_vec_ok).
 __global__ __launch_bounds__(256) void gru_step_fwd_vec_kernel(const FwdGroup g) {
     const twog_gru_step_t& S = g.s[blockIdx.y];
@@ -88,11 +98,9 @@ __global__ __launch_bounds__(256) void gru_step_fwd_vec_kernel(const FwdGroup g)
     f4 rg, z, n, ho;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        rg[k] = 1.0f / (1.0f + expf(-(ir[k] + hr[k])));
-        z[k] = 1.0f / (1.0f + expf(-(iz[k] + hz[k])));
-        n[k] = tanhf(in_[k] + rg[k] * hn[k]);
-        const float gnew = (1.0f - z[k]) * n[k] + z[k] * h0[k];
-        ho[k] = S.u ? uu * gnew + (1.0f - uu) * h0[k] : gnew;
+        float rk, zk, nk;
+        ho[k] = gru_gate_unit(ir[k], iz[k], in_[k], hr[k], hz[k], hn[k], h0[k], S.u != nullptr, uu, rk, zk, nk);
+        rg[k] = rk; z[k] = zk; n[k] = nk;
     }
     *reinterpret_cast<f4*>(twog_row_ptr(S.h_out, r) + j) = ho;
     if (S.save.ptr) {
@@ -163,6 +171,8 @@ __global__ __launch_bounds__(256) void gru_step_bwd_kernel(const BwdGroup g) {
     }
 }
 
+thread_local int g_step_path = 0;  // twog_gru_step_last_path(): what this thread's most recent twog_gru_step_fwd call launched
+
 inline twog_rows_t rows_be(const float* cbase, int E, int64_t row_w, int T) {
     float* base = const_cast<float*>(cbase);
     // rows (b, e) of a [bs][T][E][row_w] tensor at a fixed t (base already offset to t and column)
@@ -183,8 +193,11 @@ inline twog_rows_t rows_plain(const float* cbase, int64_t ld) {
 
 }  // namespace
 
+extern "C" int twog_gru_step_last_path(void) { return g_step_path; }
+
 extern "C" int twog_gru_step_fwd(const twog_gru_step_t* steps, int n_steps, void* stream) {
     int done = 0;
+    g_step_path = 0;
     while (done < n_steps) {
         const int n = (n_steps - done) < MAXS ? (n_steps - done) : MAXS;
         FwdGroup g;
@@ -201,10 +214,13 @@ extern "C" int twog_gru_step_fwd(const twog_gru_step_t* steps, int n_steps, void
             if (vec) {
                 const int rpb = 256 / (maxh >> 2);
                 hipLaunchKernelGGL(gru_step_fwd_vec_kernel, dim3((maxrows + rpb - 1) / rpb, n), dim3(256), 0, (hipStream_t)stream, g);
+                g_step_path = (g_step_path & ~0xffff) | TWOG_GRU_STEP_PATH_VEC | 256 << TWOG_GRU_STEP_PATH_THREADS_SHIFT;
             } else {
                 int bt = maxh >= 256 ? 256 : ((maxh + 63) / 64) * 64;
                 hipLaunchKernelGGL(gru_step_fwd_kernel, dim3(maxrows, n), dim3(bt), 0, (hipStream_t)stream, g);
+                g_step_path = (g_step_path & ~0xffff) | bt << TWOG_GRU_STEP_PATH_THREADS_SHIFT;
             }
+            g_step_path += 1 << TWOG_GRU_STEP_PATH_LAUNCHES_SHIFT;
             TWOG_CHECK_LAUNCH();
         }
         done += n;

@@ -844,6 +844,14 @@ class HipKernels:
             return
         self._check(self.lib.twog_gru_step_fwd(arr, len(steps), self._stream()), 'twog_gru_step_fwd')
 
+    GRU_STEP_VEC, GRU_STEP_THREADS_SHIFT, GRU_STEP_LAUNCHES_SHIFT = 1, 4, 16  # TWOG_GRU_STEP_PATH_*
+
+    def gru_step_last_path(self):
+        """(16-byte kernel?, workgroup size) of the last chunk the most recent gru_step_fwd call of this thread launched, and
+        the number of launches the whole call made (twog_gru_step_last_path)."""
+        w = int(self.lib.twog_gru_step_last_path())
+        return bool(w & self.GRU_STEP_VEC), (w >> self.GRU_STEP_THREADS_SHIFT) & 0xfff, w >> self.GRU_STEP_LAUNCHES_SHIFT
+
     def gru_step_bwd(self, steps):
         """steps: dicts with dh, dh2 (or None), save, h_prev (or None), dgi, dgh, dh_prev, u, du (same view form as u)."""
         arr = (L.GruStepBwd * len(steps))()

@@ -236,6 +236,14 @@ typedef struct {
     int32_t pad_;
 } twog_gru_step_t;
 int twog_gru_step_fwd(const twog_gru_step_t* steps, int n_steps, void* stream);
+/* What the most recent twog_gru_step_fwd call of this thread launched (host-side decisions, taken per chunk of 8 descriptors
+ * over all descriptors of the chunk); tests assert it, so that a case written for the 16-byte kernel cannot silently move to
+ * the scalar one. Bit 0 and the workgroup size describe the last chunk that launched; the launch count is the whole call's
+ * (chunks whose descriptors all have rows == 0 launch nothing). A call that launches nothing leaves 0. */
+#define TWOG_GRU_STEP_PATH_VEC             1  /* four hidden units per thread, 16-byte accesses (else one unit per thread) */
+#define TWOG_GRU_STEP_PATH_THREADS_SHIFT   4  /* workgroup size = (word >> 4) & 0xfff                                      */
+#define TWOG_GRU_STEP_PATH_LAUNCHES_SHIFT  16 /* launches of the call = word >> 16                                         */
+int twog_gru_step_last_path(void);
 
 typedef struct {
     twog_rows_t dh;      /* [rows][h] gradient wrt h_out of this step                                  */

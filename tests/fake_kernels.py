@@ -292,7 +292,7 @@ class FakeKernels:
         for d in steps:
             h = d['hidden']
             gi = d['gi'] if d.get('gi2') is None else d['gi'] + d['gi2'].reshape(d['gi'].shape)
-            hp = d['h_prev'] if d.get('h_prev') is not None else torch.zeros(*d['h_out'].shape)
+            hp = d['h_prev'] if d.get('h_prev') is not None else torch.zeros_like(d['h_out'])
             r, z, n, hn, g = self._gates(gi, d['gh'].reshape(gi.shape), hp.reshape(d['h_out'].shape), h)
             u = d.get('u')
             new = g if u is None else u.unsqueeze(-1) * g + (1 - u.unsqueeze(-1)) * hp.reshape(g.shape)
@@ -307,7 +307,7 @@ class FakeKernels:
         for d in steps:
             h = d['hidden']
             dh = d['dh'] if d.get('dh2') is None else d['dh'] + d['dh2'].reshape(d['dh'].shape)
-            hp = d['h_prev'] if d.get('h_prev') is not None else torch.zeros(*d['dh'].shape)
+            hp = d['h_prev'] if d.get('h_prev') is not None else torch.zeros_like(d['dh'])
             save = d['save'].reshape(*dh.shape[:-1], 4 * h)
             dgi, dgh, dprev, du = self._gates_bwd(dh, save, hp.reshape(dh.shape), h, d.get('u'))
             d['dgi'].copy_(dgi.reshape(d['dgi'].shape))
@@ -324,10 +324,10 @@ class FakeKernels:
         for y in types:
             gi = y['gi']
             E = gi.shape[2]
-            out = torch.zeros(bs, T, E, 2 * h, device=gi.device)
-            save = torch.zeros(2, bs, T, E, 4 * h, device=gi.device)
+            out = torch.zeros(bs, T, E, 2 * h, dtype=gi.dtype, device=gi.device)
+            save = torch.zeros(2, bs, T, E, 4 * h, dtype=gi.dtype, device=gi.device)
             for d, (w, b) in enumerate(((y['w_hh_f'], y.get('b_hh_f')), (y['w_hh_r'], y.get('b_hh_r')))):
-                hp = torch.zeros(bs, E, h, device=gi.device)
+                hp = torch.zeros(bs, E, h, dtype=gi.dtype, device=gi.device)
                 order = range(T) if d == 0 else range(T - 1, -1, -1)
                 for t in order:
                     gh = hp @ w.t() + (b if b is not None else 0.0)
@@ -346,14 +346,14 @@ class FakeKernels:
         for y in types:
             d_out, save, out = y['d_out'], y['save'], y['out']
             E = d_out.shape[2]
-            d_gi = torch.zeros(bs, T, E, 6 * h, device=d_out.device)
+            d_gi = torch.zeros(bs, T, E, 6 * h, dtype=d_out.dtype, device=d_out.device)
             d_gh = torch.zeros_like(d_gi)
             for d, w in enumerate((y['w_hh_f'], y['w_hh_r'])):
-                carry = torch.zeros(bs, E, h, device=d_out.device)
+                carry = torch.zeros(bs, E, h, dtype=d_out.dtype, device=d_out.device)
                 order = range(T - 1, -1, -1) if d == 0 else range(T)
                 for t in order:
                     tp = t - 1 if d == 0 else t + 1
-                    hp = out[:, tp, :, d * h:(d + 1) * h] if 0 <= tp < T else torch.zeros(bs, E, h, device=d_out.device)
+                    hp = out[:, tp, :, d * h:(d + 1) * h] if 0 <= tp < T else torch.zeros(bs, E, h, dtype=d_out.dtype, device=d_out.device)
                     dh = d_out[:, t, :, d * h:(d + 1) * h] + carry
                     dgi, dgh, dprev, _ = self._gates_bwd(dh, save[d, :, t], hp, h)
                     d_gi[:, t, :, d * 3 * h:(d + 1) * 3 * h] = dgi

@@ -33,6 +33,7 @@ def test_library_exports_every_declared_symbol():
     assert set(_lib.exported_symbols()) == set(names), set(names) ^ set(_lib.exported_symbols())
     lib.twog_version.restype = ctypes.c_char_p
     assert b'gfx950' in lib.twog_version()
+    assert lib.twog_gru_step_last_path() >= 0   # the path query answers without a device (0 until this thread launches a step)
 
 
 def test_struct_layouts_match_the_c_compiler(tmp_path):
