@@ -197,7 +197,7 @@ class DataParallel:
         if self.world > 1 and torch.cuda.is_available() and _ranks_share_a_device(process_group, self.world):
             # several ranks on one device (a test rig, not a deployment): no launch may assume it owns every compute unit
             from . import kernels as _kernels
-            _kernels.HipKernels.shared_devices.add(torch.cuda.current_device())   # per device, not per process
+            _kernels.PERSIST.shared_devices.add(torch.cuda.current_device())   # per device, not per process
         rank = dist.get_rank(process_group) if self.collective else 0
         self._works, self._launched = [], set()
         self._markers, self._late_failure = [], None

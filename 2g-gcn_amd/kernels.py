@@ -15,6 +15,9 @@ import os
 import torch
 
 from . import _lib as L
+from .persist import PersistentLaunches
+
+PERSIST = PersistentLaunches()   # admission and failure handling of the persistent launches: the one instance of the process
 
 
 def _ptr(t):
@@ -67,6 +70,27 @@ def _as_int64(v):
     """A Python int modulo 2^64 as the signed value with the same 64 bits (torch has no unsigned 64-bit dtype)."""
     v = int(v) & (2 ** 64 - 1)
     return v - 2 ** 64 if v >= 2 ** 63 else v
+
+
+class _DeferredWord:
+    """The error word of a persistent launch on its way to pinned host memory behind the launch: an entry of PERSIST.pending.
+    Host slot and event come from a ring per device, so that a training step allocates nothing."""
+    _rings = {}   # device index -> ([pinned int32 [1] tensors], [events], next)
+
+    def __init__(self, i, word, what, n=32):
+        ring = self._rings.get(i)
+        if ring is None:
+            pinned = torch.zeros(n, dtype=torch.int32).pin_memory()
+            ring = self._rings[i] = [[pinned[k:k + 1] for k in range(n)], [torch.cuda.Event() for _ in range(n)], 0]
+        k = ring[2]
+        ring[2] = (k + 1) % n
+        self.host, self.ev, self.what = ring[0][k], ring[1][k], what
+        self.host.copy_(word, non_blocking=True)
+        self.ev.record()
+
+    def value(self):
+        self.ev.synchronize()
+        return int(self.host[0])
 
 
 class HipKernels:
@@ -545,122 +569,49 @@ class HipKernels:
                                                              _ptr(y.get('b_hh_r')))
             a.out, a.save, a.tmp_gh, a.zeros, a.E = out.data_ptr(), save.data_ptr(), tmp.data_ptr(), zeros.data_ptr(), E
             outs.append((out, save))
-        self.last_bigru_persistent = self.bigru_persistent(arr, n, bs, h, dev)
-        if self.last_bigru_persistent:
-            # one persistent launch, W_hh slices resident in LDS (csrc/gru_persist.hip); sync words zeroed per call
-            sync = self.zeros(1024, device=dev)
-            keep.append(sync)
-            rc = self.lib.twog_bigru_fwd_persistent(arr, n, bs, T, h, sync.data_ptr(), self._stream())
-            if self._persistent_ok(rc, sync, dev, 'twog_bigru_fwd_persistent'):
-                return outs
-            self.last_bigru_persistent = False   # not resident / a wait ran out: the launch-per-step path re-runs the pass
-        self._check(self.lib.twog_bigru_fwd(arr, n, bs, T, h, *self.chain_workspace(dev), self._stream()), 'twog_bigru_fwd')
+        mode = os.environ.get('TWOG_BIGRU_PERSIST', 'auto')
+        # small batches: one persistent launch, W_hh slices resident in LDS (csrc/gru_persist.hip); =1: wherever it is served
+        self.last_bigru_persistent = self._try_persistent(
+            'bigru_fwd', dev, mode, lambda: self.lib.twog_bigru_persistent_supported(arr, n, bs, h),
+            lambda sync: self.lib.twog_bigru_fwd_persistent(arr, n, bs, T, h, sync, self._stream()),
+            n_sync=1024, err_index=128, threshold=1 if mode == '1' else 2)
+        if not self.last_bigru_persistent:
+            self._check(self.lib.twog_bigru_fwd(arr, n, bs, T, h, *self.chain_workspace(dev), self._stream()), 'twog_bigru_fwd')
         return outs
 
-    # The persistent launches need every workgroup of their grid resident at once. Three lines of defence:
-    #  (1) a device this process shares with other ranks of its own group (distributed.DataParallel finds out at
-    #      construction: more ranks than devices) is listed in `shared_devices` and never gets a persistent launch;
-    #  (2) the library asks the runtime's occupancy figure before launching and refuses a grid the device cannot hold
-    #      (rc TWOG_PERSIST_NOT_RESIDENT);
-    #  (3) a tenant nobody told us about (another process, another stream's long kernel, a CU mask): every wait inside the
-    #      launch is bounded, a time-out sets the launch's error word and drains the grid; the host reads the word right
-    #      after the launch (one 4-byte read-back; the stream is drained at that point, which costs the pipeline about one
-    #      launch latency) and re-runs the pass on the launch-per-step path -- same buffers, written in place. A device on
-    #      which that happened gets no persistent launches for the next PERSISTENT_BACKOFF calls.
-    shared_devices = set()       # device indices (per process): ranks of one group share them
-    persistent_fallbacks = 0     # passes re-run on the launch-per-step path after a persistent launch gave up (tests)
-    persistent_refused = 0       # persistent launches the occupancy check refused
-    PERSISTENT_BACKOFF = 64
-    _backoff = {}                # device index -> calls left without persistent launches
-    _refused = set()             # (launch, device index, shape ...) the occupancy check refused: not asked again
-
+    # ---- the persistent launches: policy and state in persist.py (PERSIST); here the launches and the device side of the checks
     @staticmethod
-    def _dev_index(dev):
-        return dev.index if dev.index is not None else torch.cuda.current_device()
+    def _dev_index(dev=None):
+        return dev.index if dev is not None and dev.index is not None else torch.cuda.current_device()
 
-    def persistent_allowed(self, dev):
-        """False on a shared device, and for a while after a persistent launch on this device gave up."""
-        i = self._dev_index(dev)
-        if i in HipKernels.shared_devices:
+    def persistent_allowed(self, launch, dev):
+        """PERSIST.allowed for the launch 'bigru_fwd' | 'bigru_bwd' | 'segrnn_fwd' | 'segrnn_bwd' on its device."""
+        return PERSIST.allowed(self._dev_index(dev))
+
+    def _persistent_admitted(self, launch, dev, mode, rating, threshold=2, key=None, allow=True):
+        """The admission decision of every persistent launch, in the one order that matters: the launch's environment switch
+        (mode), the caller's veto, the memo of refused grids, the library's rating() of the shape (0 not served, 1 served, 2
+        also the faster path) and LAST persistent_allowed: it consumes a back-off credit, which only a launch that would
+        otherwise be attempted may do."""
+        return (mode != '0' and allow and key not in PERSIST.refused and int(rating()) >= threshold
+                and self.persistent_allowed(launch, dev))
+
+    def _try_persistent(self, launch, dev, mode, rating, run, n_sync, err_index, threshold=2, key=None, allow=True):
+        """Decide, attempt, else fall through, for all four launches (csrc/gru_persist.hip, seg_persist.hip). True: the
+        persistent launch served the pass. False (not admitted, not resident, or a wait ran out): the caller runs the
+        launch-per-step path, on the same buffers. run(sync pointer) launches on n_sync sync words, zeroed per call, and returns
+        the return code; the launch's error word is word err_index of them."""
+        if not self._persistent_admitted(launch, dev, mode, rating, threshold, key, allow):
             return False
-        left = HipKernels._backoff.get(i, 0)
-        if left > 0:
-            HipKernels._backoff[i] = left - 1
-            return False
-        return True
-
-    # When is the error word read? Reading it right after the launch drains the stream while the host waits, and the host
-    # then has to refill the queue launch by launch (measured at 8 clips: ~0.4 ms of the 21.5 ms step per read-back). So:
-    # the first PERSIST_SYNC_CALLS persistent launches on a device -- and every launch for PERSISTENT_BACKOFF calls after
-    # a failure -- are checked AT ONCE and recovered transparently (the pass is re-run per step before anything consumes
-    # its outputs). After that many clean launches the device is evidently ours: the word is copied to pinned host memory
-    # behind the launch (asynchronously) and read at the END of the forward / backward pass (verify_persistent, called by
-    # ops.tggcn_forward / tggcn_backward), when the copy has long landed. A failure found that late -- a tenant that
-    # arrived in mid-training -- cannot be repaired behind the caller's back (consumers have run on incomplete outputs):
-    # it raises, loudly, with the process and the context alive, and the next calls are checked at once again.
-    # TWOG_PERSIST_CHECK=sync: always at once; =lazy: always at the end of the pass.
-    PERSIST_SYNC_CALLS = 8
-    _clean = {}       # device index -> persistent launches checked at once that completed
-    _lazy = {}        # device index -> [(event, pinned int32 tensor, what)]
-    persistent_late_failures = 0
-
-    def _persistent_ok(self, rc, sync, dev, what, err_index=128):
-        """True if the persistent launch ran to completion (or will be verified at the end of the pass). False -> the
-        caller re-runs the pass on the launch-per-step path."""
-        if rc == L.PERSIST_NOT_RESIDENT:
-            HipKernels.persistent_refused += 1
-            return False
-        self._check(rc, what)
-        i = self._dev_index(dev)
-        mode = os.environ.get('TWOG_PERSIST_CHECK', 'auto')
-        word = sync.view(torch.int32)[err_index:err_index + 1]
-        if mode == 'lazy' or (mode != 'sync' and HipKernels._clean.get(i, 0) >= self.PERSIST_SYNC_CALLS):
-            host, ev = self._lazy_slot(i)
-            host.copy_(word, non_blocking=True)
-            ev.record()
-            HipKernels._lazy.setdefault(i, []).append((ev, host, what))
-            return True
-        if int(word.item()) == 0:   # (drains the stream: see above)
-            HipKernels._clean[i] = HipKernels._clean.get(i, 0) + 1
-            return True
-        HipKernels.persistent_fallbacks += 1
-        HipKernels._backoff[i] = self.PERSISTENT_BACKOFF
-        HipKernels._clean[i] = 0
-        return False
-
-    _slots = {}   # device index -> ([pinned int32 [1] tensors], [events], next): a ring, so that a training step allocates nothing
-
-    def _lazy_slot(self, i, n=32):
-        ring = HipKernels._slots.get(i)
-        if ring is None:
-            pinned = torch.zeros(n, dtype=torch.int32).pin_memory()
-            ring = [[pinned[k:k + 1] for k in range(n)], [torch.cuda.Event() for _ in range(n)], 0]
-            HipKernels._slots[i] = ring
-        k = ring[2]
-        ring[2] = (k + 1) % n
-        return ring[0][k], ring[1][k]
+        sync = self.zeros(n_sync, device=dev)
+        rc = run(sync.data_ptr())
+        i, what, word = self._dev_index(dev), f'twog_{launch}_persistent', sync.view(torch.int32)[err_index:err_index + 1]
+        return PERSIST.completed(i, rc, what, lambda: int(word.item()), lambda: _DeferredWord(i, word, what), key)
 
     def verify_persistent(self, dev=None):
         """End of a forward / backward pass: every persistent launch of the pass whose error word was left for later must
-        have completed. Raises RuntimeError otherwise (see above)."""
-        i = self._dev_index(dev if dev is not None else torch.device('cuda', torch.cuda.current_device()))
-        pending = HipKernels._lazy.pop(i, None)
-        if not pending:
-            return
-        failed = []
-        for ev, host, what in pending:
-            ev.synchronize()
-            if int(host[0]) != 0:
-                failed.append(what)
-        if failed:
-            HipKernels.persistent_late_failures += 1
-            HipKernels._backoff[i] = self.PERSISTENT_BACKOFF
-            HipKernels._clean[i] = 0
-            raise RuntimeError(f'{", ".join(failed)}: a persistent launch could not keep its grid resident (another tenant '
-                               'is holding compute units of this GPU) and gave up; the results of this pass are incomplete. '
-                               'Repeat the step: the next calls run the launch-per-step path and persistent launches are '
-                               're-admitted one checked launch at a time (TWOG_BIGRU_PERSIST=0 TWOG_SEG_PERSIST=0 switch '
-                               'them off for good).')
+        have completed. Raises RuntimeError otherwise (persist.py)."""
+        PERSIST.verify(self._dev_index(dev))
 
     def guard_persistent(self, dev, outs):
         """End of a forward pass that a backward pass will follow: instead of waiting for the pass's deferred error words
@@ -668,8 +619,7 @@ class HipKernels:
         step), ONE small launch behind them overwrites `outs` with NaN if any is set. The words stay pending: the check at
         the end of the backward pass (or at the start of the next forward) raises. True when nothing is pending or the guard
         was enqueued; False -> the caller verifies at once."""
-        i = self._dev_index(dev if dev is not None else torch.device('cuda', torch.cuda.current_device()))
-        pending = HipKernels._lazy.get(i)
+        pending = PERSIST.pending.get(self._dev_index(dev))
         if not pending:
             return True
         outs = [o for o in outs if o is not None and o.numel()]
@@ -677,8 +627,8 @@ class HipKernels:
                 or any(o.dtype != torch.float32 or not o.is_contiguous() for o in outs)):
             return False
         g = L.Guard()
-        for k, (_, host, _) in enumerate(pending):
-            g.words[k] = host.data_ptr()
+        for k, d in enumerate(pending):
+            g.words[k] = d.host.data_ptr()
         for k, o in enumerate(outs):
             g.out[k], g.n[k] = o.data_ptr(), o.numel()
         g.n_words, g.n_out = len(pending), len(outs)
@@ -690,19 +640,21 @@ class HipKernels:
         rates it the faster path (small batches: at most one 16-row tile per wave). TWOG_BIGRU_PERSIST=1: wherever it is
         served; =0: never."""
         mode = os.environ.get('TWOG_BIGRU_PERSIST', 'auto')
-        if mode == '0' or int(self.lib.twog_bigru_persistent_supported(arr, n, bs, h)) < (1 if mode == '1' else 2):
-            return False
-        return self.persistent_allowed(dev if dev is not None else torch.device('cuda', torch.cuda.current_device()))
+        return self._persistent_admitted('bigru_fwd', dev, mode, lambda: self.lib.twog_bigru_persistent_supported(arr, n, bs, h),
+                                         threshold=1 if mode == '1' else 2)
+
+    @staticmethod
+    def _bigru_bwd_key(i, Es, bs, h):
+        """What PERSIST.refused remembers a refused backward BiGRU grid by (the only launch with a memo: DESIGN.md 7)."""
+        return ('bigru_bwd', i, tuple(int(E) for E in Es), bs, h)
 
     def bigru_bwd_would_persist(self, Es, bs, h):
         """Whether bigru_bwd takes the persistent launch for entity counts Es at this batch (asked before the operands exist:
-        the data-parallel backward pass orders its first gradient all-reduce around that launch)."""
-        i = self._dev_index(torch.device('cuda', torch.cuda.current_device()))
-        # the same conditions bigru_bwd applies -- a shared device, the back-off window after a launch that gave up (read, not
-        # consumed: persistent_allowed() counts it down when the launch is really attempted) and a grid the occupancy check
-        # refused before on this device (ADVICE r05: the caller orders its first all-reduce and its side stream around the answer)
-        if (os.environ.get('TWOG_BIGRU_PERSIST', 'auto') == '0' or i in HipKernels.shared_devices
-                or HipKernels._backoff.get(i, 0) > 0 or ('bigru_bwd', i, tuple(Es), bs, h) in HipKernels._refused):
+        the data-parallel backward pass orders its first gradient all-reduce and its side stream around that launch, ADVICE
+        r05). What turns the launch down -- a shared device, the back-off window, a grid refused before on this device --
+        is read here, not consumed: persistent_allowed() counts the window down when the launch is really attempted."""
+        i = self._dev_index()
+        if os.environ.get('TWOG_BIGRU_PERSIST', 'auto') == '0' or PERSIST.blocked(i, self._bigru_bwd_key(i, Es, bs, h)):
             return False
         arr = (L.BiGruBwd * len(Es))()
         for a, E in zip(arr, Es):
@@ -728,22 +680,14 @@ class HipKernels:
             a.w_hh_f, a.w_hh_r = y['w_hh_f'].data_ptr(), y['w_hh_r'].data_ptr()
             a.d_gi, a.d_gh, a.carry, a.E = d_gi.data_ptr(), d_gh.data_ptr(), carry.data_ptr(), E
             outs.append((d_gi, d_gh))
-        mode = os.environ.get('TWOG_BIGRU_PERSIST', 'auto')
-        self.last_bigru_bwd_persistent = (mode != '0' and allow_persistent
-                                          and ('bigru_bwd', self._dev_index(dev), tuple(int(y['d_out'].shape[2]) for y in types), bs, h)
-                                          not in HipKernels._refused
-                                          and int(self.lib.twog_bigru_bwd_persistent_supported(arr, n, bs, h)) >= 2
-                                          and self.persistent_allowed(dev))   # (last: it consumes a back-off credit)
-        if self.last_bigru_bwd_persistent:   # small batches: one persistent launch (csrc/gru_persist.hip)
-            sync = self.zeros(1024, device=dev)
-            keep.append(sync)
-            rc = self.lib.twog_bigru_bwd_persistent(arr, n, bs, T, h, sync.data_ptr(), self._stream())
-            if rc == L.PERSIST_NOT_RESIDENT:
-                HipKernels._refused.add(('bigru_bwd', self._dev_index(dev), tuple(int(y['d_out'].shape[2]) for y in types), bs, h))
-            if self._persistent_ok(rc, sync, dev, 'twog_bigru_bwd_persistent'):
-                return outs
-            self.last_bigru_bwd_persistent = False
-        self._check(self.lib.twog_bigru_bwd(arr, n, bs, T, h, *self.chain_workspace(dev), self._stream()), 'twog_bigru_bwd')
+        self.last_bigru_bwd_persistent = self._try_persistent(   # small batches: one persistent launch (csrc/gru_persist.hip)
+            'bigru_bwd', dev, os.environ.get('TWOG_BIGRU_PERSIST', 'auto'),
+            lambda: self.lib.twog_bigru_bwd_persistent_supported(arr, n, bs, h),
+            lambda sync: self.lib.twog_bigru_bwd_persistent(arr, n, bs, T, h, sync, self._stream()),
+            n_sync=1024, err_index=128, allow=allow_persistent,
+            key=self._bigru_bwd_key(self._dev_index(dev), (y['d_out'].shape[2] for y in types), bs, h))
+        if not self.last_bigru_bwd_persistent:
+            self._check(self.lib.twog_bigru_bwd(arr, n, bs, T, h, *self.chain_workspace(dev), self._stream()), 'twog_bigru_bwd')
         return outs
 
     # ---------------------------------------------------------------- single-direction frame GRU (baseline models)
@@ -953,17 +897,14 @@ class HipKernels:
                     zeros=self.zeros(bs * max(H, O, 1), h, device=dev))
         s = L.SegRnn()
         self._fill_seg(s, p, bufs)
-        mode = os.environ.get('TWOG_SEG_PERSIST', 'auto')
-        self.last_segrnn_persistent = (mode != '0' and int(self.lib.twog_segrnn_persistent_supported(C.byref(s))) >= 2
-                                       and self.persistent_allowed(dev))   # (last: it consumes a back-off credit)
-        if self.last_segrnn_persistent:   # small batches: the whole recurrence in one launch (csrc/seg_persist.hip)
-            n_sync = int(self.lib.twog_segrnn_persistent_sync_bytes()) // 4
-            sync = self.zeros(n_sync, device=dev)
-            rc = self.lib.twog_segrnn_fwd_persistent(C.byref(s), sync.data_ptr(), self._stream())
-            if self._persistent_ok(rc, sync, dev, 'twog_segrnn_fwd_persistent', err_index=n_sync - 32):
-                return bufs
-            self.last_segrnn_persistent = False
-        self._check(self.lib.twog_segrnn_fwd(C.byref(s), *self.chain_workspace(dev), self._stream()), 'twog_segrnn_fwd')
+        n_sync = int(self.lib.twog_segrnn_persistent_sync_bytes()) // 4
+        self.last_segrnn_persistent = self._try_persistent(   # small batches: the whole recurrence in one launch (csrc/seg_persist.hip)
+            'segrnn_fwd', dev, os.environ.get('TWOG_SEG_PERSIST', 'auto'),
+            lambda: self.lib.twog_segrnn_persistent_supported(C.byref(s)),
+            lambda sync: self.lib.twog_segrnn_fwd_persistent(C.byref(s), sync, self._stream()),
+            n_sync=n_sync, err_index=n_sync - 32)
+        if not self.last_segrnn_persistent:
+            self._check(self.lib.twog_segrnn_fwd(C.byref(s), *self.chain_workspace(dev), self._stream()), 'twog_segrnn_fwd')
         return bufs
 
     def segrnn_bwd(self, p, bufs, d_hs_h, d_hs_o):
@@ -988,20 +929,17 @@ class HipKernels:
         b.d_hs_h, b.d_hs_o = _ptr(d_hs_h), _ptr(d_hs_o)
         for k, v in list(out.items()) + list(scratch.items()):
             setattr(b, k, _ptr(v))
-        mode = os.environ.get('TWOG_SEG_PERSIST', 'auto')
-        self.last_segrnn_bwd_persistent = (mode != '0' and int(self.lib.twog_segrnn_persistent_supported(C.byref(s))) >= 2
-                                           and self.persistent_allowed(dev))
-        if self.last_segrnn_bwd_persistent:   # small batches: backward through time in one launch (csrc/seg_persist.hip)
-            n_scr = int(self.lib.twog_segrnn_bwd_persistent_scratch_bytes(C.byref(s)))
-            scr = self.workspace(n_scr, dev, 'segp_bwd')
-            n_sync = int(self.lib.twog_segrnn_persistent_sync_bytes()) // 4
-            sync = self.zeros(n_sync, device=dev)
-            rc = self.lib.twog_segrnn_bwd_persistent(C.byref(s), C.byref(b), scr.data_ptr(), scr.numel() * 4, sync.data_ptr(),
-                                                     self._stream())
-            if self._persistent_ok(rc, sync, dev, 'twog_segrnn_bwd_persistent', err_index=n_sync - 32):
-                return out
-            self.last_segrnn_bwd_persistent = False
-        self._check(self.lib.twog_segrnn_bwd(C.byref(s), C.byref(b), *self.chain_workspace(dev), self._stream()), 'twog_segrnn_bwd')
+
+        def run(sync):
+            scr = self.workspace(int(self.lib.twog_segrnn_bwd_persistent_scratch_bytes(C.byref(s))), dev, 'segp_bwd')
+            return self.lib.twog_segrnn_bwd_persistent(C.byref(s), C.byref(b), scr.data_ptr(), scr.numel() * 4, sync, self._stream())
+
+        n_sync = int(self.lib.twog_segrnn_persistent_sync_bytes()) // 4
+        self.last_segrnn_bwd_persistent = self._try_persistent(   # small batches: backward through time in one launch
+            'segrnn_bwd', dev, os.environ.get('TWOG_SEG_PERSIST', 'auto'),
+            lambda: self.lib.twog_segrnn_persistent_supported(C.byref(s)), run, n_sync=n_sync, err_index=n_sync - 32)
+        if not self.last_segrnn_bwd_persistent:
+            self._check(self.lib.twog_segrnn_bwd(C.byref(s), C.byref(b), *self.chain_workspace(dev), self._stream()), 'twog_segrnn_bwd')
         return out
 
     def graph_cache_stats(self):

@@ -239,8 +239,8 @@ def test_segment_recurrence_launch_per_step_over_the_entity_range(K, bs, T, H, O
 def test_segment_recurrence_persistent_launch_over_the_entity_range(K, bs, T, H, O, h, monkeypatch):
     """The persistent launch must serve these shapes (asserted: a shape the library refuses is a failure, not a skip); its
     results against the launch-per-step path at the bar of the existing persistent test, and against fp64."""
-    from twog_gcn_amd.kernels import HipKernels
-    HipKernels._backoff.clear()
+    from twog_gcn_amd.kernels import PERSIST
+    PERSIST.backoff.clear()
     monkeypatch.setenv('TWOG_PERSIST_CHECK', 'sync')
     b32, b64, (dh_h, dh_o), o32, o64 = EE.seg_spec(bs, T, H, O, h)
     pg = _seg_params(DEV, bs, T, H, O, h, (True, True, True, True), True)

@@ -631,11 +631,11 @@ def test_persistent_launches_fail_soft_and_the_pass_is_rerun_per_step(K, monkeyp
     error word and every wave leaves. Checked at once (the first launches on a device, and TWOG_PERSIST_CHECK=sync): the host
     sees the word and re-runs the pass on the launch-per-step path before anything consumed the outputs -- results = the
     launch-per-step path's, bit for bit; the process lives; the counters say what ran; the device gets no persistent launch
-    for PERSISTENT_BACKOFF calls; with the limit restored the persistent launches run again and give what they gave."""
-    from twog_gcn_amd.kernels import HipKernels
+    for PERSIST.BACKOFF calls; with the limit restored the persistent launches run again and give what they gave."""
+    from twog_gcn_amd.kernels import PERSIST, HipKernels
     run = _persist_rig(K)
-    HipKernels._backoff.clear()
-    HipKernels._lazy.clear()
+    PERSIST.backoff.clear()
+    PERSIST.pending.clear()
     monkeypatch.setenv('TWOG_PERSIST_CHECK', 'sync')
     monkeypatch.setenv('TWOG_BIGRU_PERSIST', '0')
     monkeypatch.setenv('TWOG_SEG_PERSIST', '0')
@@ -647,36 +647,34 @@ def test_persistent_launches_fail_soft_and_the_pass_is_rerun_per_step(K, monkeyp
     assert ran == (True, True, True, True), 'the persistent launches did not run on an idle device'
     dev_i = torch.cuda.current_device()
     monkeypatch.setenv('TWOG_PERSIST_SPIN_LIMIT', '0')
-    n0 = HipKernels.persistent_fallbacks
+    n0 = PERSIST.fallbacks
     got, ran = run()   # the forward BiGRU launch is tried first, gives up, the device backs off: the other two are not tried
     assert ran == (False, False, False, False)
-    assert HipKernels.persistent_fallbacks == n0 + 1, 'exactly one launch was tried, gave up and was re-run'
-    assert 0 < HipKernels._backoff.get(dev_i, 0) <= HipKernels.PERSISTENT_BACKOFF
+    assert PERSIST.fallbacks == n0 + 1, 'exactly one launch was tried, gave up and was re-run'
+    assert 0 < PERSIST.backoff.get(dev_i, 0) <= PERSIST.BACKOFF
     for a, b in zip(got, want):
         assert torch.isfinite(a).all() and torch.equal(a, b), 'a re-run pass differs from the launch-per-step path'
     # the backward BiGRU launch and the segment launch as the FIRST persistent launch of a call
     for env in ('bwd', 'seg', 'segb'):
-        HipKernels._backoff.clear()
-        n0 = HipKernels.persistent_fallbacks
+        PERSIST.backoff.clear()
+        n0 = PERSIST.fallbacks
         real_allowed = HipKernels.persistent_allowed
         calls = []
 
-        def allowed(self, dev, env=env, calls=calls):   # lets only the launch under test through
+        def allowed(self, launch, dev, env=env, calls=calls):   # lets only the launch under test through
             calls.append(1)
-            import inspect
-            caller = inspect.stack()[1].function
-            want_caller = {'bwd': 'bigru_bwd', 'seg': 'segrnn_fwd', 'segb': 'segrnn_bwd'}[env]
-            return caller == want_caller and real_allowed(self, dev)
+            want_launch = {'bwd': 'bigru_bwd', 'seg': 'segrnn_fwd', 'segb': 'segrnn_bwd'}[env]
+            return launch == want_launch and real_allowed(self, launch, dev)
 
         monkeypatch.setattr(HipKernels, 'persistent_allowed', allowed)
         got, ran = run()
         monkeypatch.setattr(HipKernels, 'persistent_allowed', real_allowed)
-        assert ran == (False, False, False, False) and HipKernels.persistent_fallbacks == n0 + 1, (env, ran)
+        assert ran == (False, False, False, False) and PERSIST.fallbacks == n0 + 1, (env, ran)
         for a, b in zip(got, want):
             assert torch.equal(a, b), env
     # limit restored: persistent again, same results as before
     monkeypatch.delenv('TWOG_PERSIST_SPIN_LIMIT')
-    HipKernels._backoff.clear()
+    PERSIST.backoff.clear()
     again, ran = run()
     assert ran == (True, True, True, True)
     for a, b in zip(again, good):
@@ -684,13 +682,13 @@ def test_persistent_launches_fail_soft_and_the_pass_is_rerun_per_step(K, monkeyp
 
 
 def test_persistent_launch_failure_found_at_the_end_of_the_pass_raises_and_the_next_calls_recover(K, monkeypatch):
-    """After PERSIST_SYNC_CALLS clean launches the error word is read at the END of the pass (no pipeline drain per launch).
+    """After PERSIST.SYNC_CALLS clean launches the error word is read at the END of the pass (no pipeline drain per launch).
     A failure found that late cannot be repaired behind the caller's back: verify_persistent raises -- process and context
     alive -- the device backs off, and the next pass runs per step with correct results."""
-    from twog_gcn_amd.kernels import HipKernels
+    from twog_gcn_amd.kernels import PERSIST
     run = _persist_rig(K)
-    HipKernels._backoff.clear()
-    HipKernels._lazy.clear()
+    PERSIST.backoff.clear()
+    PERSIST.pending.clear()
     monkeypatch.setenv('TWOG_PERSIST_CHECK', 'lazy')
     monkeypatch.setenv('TWOG_BIGRU_PERSIST', '0')
     monkeypatch.setenv('TWOG_SEG_PERSIST', '0')
@@ -701,19 +699,19 @@ def test_persistent_launch_failure_found_at_the_end_of_the_pass_raises_and_the_n
     assert ran == (True, True, True, True)
     K.verify_persistent()            # clean launches: nothing to report
     monkeypatch.setenv('TWOG_PERSIST_SPIN_LIMIT', '0')
-    n0 = HipKernels.persistent_late_failures
+    n0 = PERSIST.late_failures
     _, ran = run()
     assert ran == (True, True, True, True)   # nobody has looked yet
     with pytest.raises(RuntimeError, match='could not keep its grid resident'):
         K.verify_persistent()
-    assert HipKernels.persistent_late_failures == n0 + 1
+    assert PERSIST.late_failures == n0 + 1
     K.verify_persistent()            # reported once
     got, ran = run()                 # backing off: per step, correct
     assert ran == (False, False, False, False)
     for a, b in zip(got, want):
         assert torch.equal(a, b)
-    HipKernels._backoff.clear()
-    HipKernels._lazy.clear()
+    PERSIST.backoff.clear()
+    PERSIST.pending.clear()
 
 
 def test_guard_launch_poisons_the_outputs_of_a_pass_whose_persistent_launch_gave_up(K, monkeypatch):
@@ -722,14 +720,14 @@ def test_guard_launch_poisons_the_outputs_of_a_pass_whose_persistent_launch_gave
     outputs into NaN if any word is set, and the words are read -- and raise -- at the end of the backward pass. Here: a
     clean pass leaves the outputs alone; with a forced give-up (TWOG_PERSIST_SPIN_LIMIT=0) every guarded tensor is NaN and
     verify_persistent raises afterwards."""
-    from twog_gcn_amd.kernels import HipKernels
+    from twog_gcn_amd.kernels import PERSIST
     run = _persist_rig(K)
-    HipKernels._backoff.clear()
-    HipKernels._lazy.clear()
+    PERSIST.backoff.clear()
+    PERSIST.pending.clear()
     monkeypatch.setenv('TWOG_PERSIST_CHECK', 'lazy')
     outs = [torch.ones(1000, device=DEV), torch.full((3, 7), 2.0, device=DEV)]
     _, ran = run()
-    assert ran == (True, True, True, True) and len(HipKernels._lazy[0]) == 4
+    assert ran == (True, True, True, True) and len(PERSIST.pending[0]) == 4
     assert K.guard_persistent(torch.device(DEV), outs)
     torch.cuda.synchronize()
     assert float(outs[0].sum()) == 1000.0 and float(outs[1].sum()) == 42.0
@@ -742,8 +740,8 @@ def test_guard_launch_poisons_the_outputs_of_a_pass_whose_persistent_launch_gave
     assert bool(torch.isnan(outs[0]).all()) and bool(torch.isnan(outs[1]).all())
     with pytest.raises(RuntimeError, match='could not keep its grid resident'):
         K.verify_persistent()
-    HipKernels._backoff.clear()
-    HipKernels._lazy.clear()
+    PERSIST.backoff.clear()
+    PERSIST.pending.clear()
 
 
 def test_persistent_launch_beside_a_tenant_that_holds_compute_units(K, monkeypatch):
@@ -751,10 +749,10 @@ def test_persistent_launch_beside_a_tenant_that_holds_compute_units(K, monkeypat
     each, for 60 ms), so half of a persistent grid is resident and waits for the half that is not. With a spin limit of
     ~2 ms the resident waves give up, the grid drains, the host re-runs the pass per step: correct results, no hang, no trap;
     the tenant finishes undisturbed."""
-    from twog_gcn_amd.kernels import HipKernels
+    from twog_gcn_amd.kernels import PERSIST
     run = _persist_rig(K)
-    HipKernels._backoff.clear()
-    HipKernels._lazy.clear()
+    PERSIST.backoff.clear()
+    PERSIST.pending.clear()
     monkeypatch.setenv('TWOG_PERSIST_CHECK', 'sync')
     monkeypatch.setenv('TWOG_BIGRU_PERSIST', '0')
     monkeypatch.setenv('TWOG_SEG_PERSIST', '0')
@@ -763,17 +761,17 @@ def test_persistent_launch_beside_a_tenant_that_holds_compute_units(K, monkeypat
     monkeypatch.delenv('TWOG_SEG_PERSIST')
     monkeypatch.setenv('TWOG_PERSIST_SPIN_LIMIT', '2000')
     side = torch.cuda.Stream()
-    n0 = HipKernels.persistent_fallbacks
+    n0 = PERSIST.fallbacks
     t0 = time.time()
     with torch.cuda.stream(side):
         K.debug_occupy(128, 100 * 1024, 60000)
     got, ran = run()
     torch.cuda.synchronize()
     assert time.time() - t0 < 30.0
-    assert HipKernels.persistent_fallbacks >= n0 + 1, 'no persistent launch gave up beside the tenant'
+    assert PERSIST.fallbacks >= n0 + 1, 'no persistent launch gave up beside the tenant'
     for a, b in zip(got, want):
         assert torch.isfinite(a).all() and torch.equal(a, b)
-    HipKernels._backoff.clear()
+    PERSIST.backoff.clear()
 
 
 def test_masked_side_stream_runs_the_same_kernels_on_a_subset_of_the_compute_units(K):
@@ -926,8 +924,8 @@ def test_segment_recurrence_persistent_launch_matches_the_stepwise_recurrence(K,
     """Forward segment recurrence in one launch against the specification (the torch test double) and against the
     launch-per-step path: states, saved gate activations, sender messages, aggregated messages, attention weights; two
     runs bit-identical (fixed summation order; a wrong hand-off gives garbage, not noise)."""
-    from twog_gcn_amd.kernels import HipKernels
-    HipKernels._backoff.clear()
+    from twog_gcn_amd.kernels import PERSIST
+    PERSIST.backoff.clear()
     monkeypatch.setenv('TWOG_PERSIST_CHECK', 'sync')
     rels = (True, True, True, True)
     pc = _seg_params('cpu', bs, T, H, O, h, rels, True)

@@ -36,4 +36,4 @@ for (bs, T, H, O, h) in [(8, 120, 2, 4, 512), (16, 120, 2, 9, 64), (1, 120, 1, 5
             used = K.last_segrnn_persistent if what == 'fwd' else K.last_segrnn_bwd_persistent
             print(f'bs={bs} T={T} H={H} O={O} h={h} {what} persistent={used}: {dt * 1e3:.3f} ms per pass, '
                   f'{dt / T * 1e6:.1f} us per step', flush=True)
-        kernels.HipKernels._lazy.clear()
+        kernels.PERSIST.pending.clear()
