@@ -201,6 +201,8 @@ SIGNATURES = {
     'twog_stream_destroy': [_P],
     'twog_gemm_colsum_fused': [C.POINTER(Gemm), _I, _I, _I, _P, C.c_size_t],
     'twog_gemm_last_class': [],
+    'twog_gemm_set_precision': [_I],
+    'twog_gemm_get_precision': [],
     'twog_chain_workspace_bytes': [],
     'twog_gemm_f32_chain': [C.POINTER(Gemm), _I, _I, _I, _P, C.c_size_t, _P],
     'twog_gcn_max_nodes': [],

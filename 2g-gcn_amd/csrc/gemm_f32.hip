@@ -442,6 +442,28 @@ __device__ __forceinline__ void split3(const f32x4 v, i32x2& ph, i32x2& pm, i32x
     pl = i32x2{(int)pack_hi16(r2[0], r2[1]), (int)pack_hi16(r2[2], r2[3])};
 }
 
+// The reduced plane counts (twog_gemm_set_precision: 'high' = two planes, 'medium' = one; specification with the error
+// constants in tests/matmul_precision_ref.py). Both round to nearest even -- a truncating split would leave a bias towards
+// zero of ~2^-9 |a b| with one plane and ~2^-17 |a b| with two, no longer below the accumulate's -- through v_cvt_pk_bf16_f32, whose packed
+// result {bf16(x1), bf16(x0)} is the layout pack_hi16 produces. h = rne(x), m = rne(x - h) (the subtraction is exact).
+// |x| >= 0x7f7f8000 rounds to Inf as IEEE asks ('high' then gives NaN like any Inf operand: x - h = Inf - Inf).
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t rne_pack(float x0, float x1) {   // {bf16(x1), bf16(x0)}
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
+}
+__device__ __forceinline__ void split1(const f32x4 v, i32x2& ph) {
+    const float f0 = v[0], f1 = v[1], f2 = v[2], f3 = v[3];
+    ph = i32x2{(int)rne_pack(f0, f1), (int)rne_pack(f2, f3)};
+}
+__device__ __forceinline__ void split2(const f32x4 v, i32x2& ph, i32x2& pm) {
+    const float f0 = v[0], f1 = v[1], f2 = v[2], f3 = v[3];
+    const uint32_t h01 = rne_pack(f0, f1), h23 = rne_pack(f2, f3);
+    ph = i32x2{(int)h01, (int)h23};
+    pm = i32x2{(int)rne_pack(f0 - __uint_as_float(h01 << 16), f1 - __uint_as_float(h01 & 0xffff0000u)),
+               (int)rne_pack(f2 - __uint_as_float(h23 << 16), f3 - __uint_as_float(h23 & 0xffff0000u))};
+}
+
 #ifndef TWOG_X3_PRODUCTS
 #define TWOG_X3_PRODUCTS 6
 #endif
@@ -465,10 +487,14 @@ __device__ __forceinline__ int x3_swz(int k) { return ((k & 3) << 2) | ((k >> 2)
 // (Built, measured and dropped in round 6, all bit-identical and none faster for the launches of at most one tile per CU:
 // two k-tiles per barrier interval, sixteen waves as two k-groups on one tile, fragment reads one k-tile ahead of the MFMAs;
 // profiles/r06_gemm128_*.txt.)
-template <bool AKM, bool BKM, bool KG, bool TTMP = false>
+// NP: bf16 planes per operand. 3 = the exact split and X3_PRODUCTS products (the default: fp32 results); 2 = planes h, m and
+// the products h m, m h, h h; 1 = plane h and the product h h (split2 / split1 above). The LDS layout is the three-plane one
+// for every NP -- the unused planes are neither written nor read -- so addressing and occupancy do not depend on it.
+template <bool AKM, bool BKM, bool KG, bool TTMP = false, int NP = 3>
 __device__ __forceinline__ void gemm_mainloop_x3(const twog_rows_t A, const twog_rows_t B, int M, int N, int m0, int n0,
                                                  int k_begin, int k_end, float* smem, f32x16 (&acc)[1][2], f32x4& cs, bool cs_on) {
     constexpr int BM = 128, BN = 128, NT = 512, XK = X3_BK;
+    static_assert(NP == 3 || ((NP == 2 || NP == 1) && !TTMP), "two or one plane: the plain accumulator only");
     constexpr int PA = AKM ? X3_TPLANE : X3_RPLANE, PB = BKM ? X3_TPLANE : X3_RPLANE;
     // stage b: A planes at b * X3_STAGE, B planes behind them
     char* lds = reinterpret_cast<char*>(smem);
@@ -543,14 +569,28 @@ __device__ __forceinline__ void gemm_mainloop_x3(const twog_rows_t A, const twog
         if constexpr (AKM && BKM && !KG) {
             if (cs_on && t < nkt) cs += r.a;
         }
-        split3(r.a, ph, pm, pl);
-        *reinterpret_cast<i32x2*>(base + sa_off) = ph;
-        *reinterpret_cast<i32x2*>(base + sa_off + PA) = pm;
-        *reinterpret_cast<i32x2*>(base + sa_off + 2 * PA) = pl;
-        split3(r.b, ph, pm, pl);
-        *reinterpret_cast<i32x2*>(base + sb_off) = ph;
-        *reinterpret_cast<i32x2*>(base + sb_off + PB) = pm;
-        *reinterpret_cast<i32x2*>(base + sb_off + 2 * PB) = pl;
+        if constexpr (NP == 3) {
+            split3(r.a, ph, pm, pl);
+            *reinterpret_cast<i32x2*>(base + sa_off) = ph;
+            *reinterpret_cast<i32x2*>(base + sa_off + PA) = pm;
+            *reinterpret_cast<i32x2*>(base + sa_off + 2 * PA) = pl;
+            split3(r.b, ph, pm, pl);
+            *reinterpret_cast<i32x2*>(base + sb_off) = ph;
+            *reinterpret_cast<i32x2*>(base + sb_off + PB) = pm;
+            *reinterpret_cast<i32x2*>(base + sb_off + 2 * PB) = pl;
+        } else if constexpr (NP == 2) {
+            split2(r.a, ph, pm);
+            *reinterpret_cast<i32x2*>(base + sa_off) = ph;
+            *reinterpret_cast<i32x2*>(base + sa_off + PA) = pm;
+            split2(r.b, ph, pm);
+            *reinterpret_cast<i32x2*>(base + sb_off) = ph;
+            *reinterpret_cast<i32x2*>(base + sb_off + PB) = pm;
+        } else {
+            split1(r.a, ph);
+            *reinterpret_cast<i32x2*>(base + sa_off) = ph;
+            split1(r.b, ph);
+            *reinterpret_cast<i32x2*>(base + sb_off) = ph;
+        }
     };
     // fragment addressing: lane l = (r = l & 31 row / column of the 32x32 block, h = l >> 5 half of the 16-deep k-step)
     const int r32 = lane & 31, h = lane >> 5;
@@ -590,11 +630,11 @@ __device__ __forceinline__ void gemm_mainloop_x3(const twog_rows_t A, const twog
         // nearest even, unbiased); the B fragments of a block are read right before its chain, so the temporary takes the
         // registers the second block's fragments held. Default: all products into the running sum (round 3's form).
         constexpr int PI[8] = {2, 1, 2, 0, 1, 1, 0, 0}, PJ[8] = {1, 2, 0, 2, 1, 0, 1, 0};
-        constexpr int FIRST = 8 - X3_PRODUCTS;
+        constexpr int FIRST = NP == 3 ? 8 - X3_PRODUCTS : NP == 2 ? 5 : 7;   // NP 2: h m, m h, h h; NP 1: h h (the list's tail)
         static_assert(X3_PRODUCTS == 8 || X3_PRODUCTS == 6, "l m and m l are the two optional products");
         bf16x8 af[3];
 #pragma unroll
-        for (int p = 0; p < 3; ++p) af[p] = AKM ? frag_t(base + p * PA, tchA) : frag_r(base + p * PA, fa_r);
+        for (int p = 0; p < NP; ++p) af[p] = AKM ? frag_t(base + p * PA, tchA) : frag_r(base + p * PA, fa_r);
         if constexpr (TTMP) {
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
@@ -614,7 +654,7 @@ __device__ __forceinline__ void gemm_mainloop_x3(const twog_rows_t A, const twog
 #pragma unroll
             for (int b = 0; b < 2; ++b)
 #pragma unroll
-                for (int p = 0; p < 3; ++p)
+                for (int p = 0; p < NP; ++p)
                     bf[b][p] = BKM ? frag_t(base + 3 * PA + p * PB, tchB + 4 * b) : frag_r(base + p * PB, fb_r + b * 32 * X3_RROW);
 #pragma unroll
             for (int t = FIRST; t < 8; ++t)
@@ -876,7 +916,7 @@ __device__ __forceinline__ void gemm_mainloop_x3s(const twog_rows_t A, const two
 // counters are zero again at the launch boundary (graph replays need no memset node). The hand-off form is the
 // guide's split-K recipe (cdna_hip_programming.md section 5 item 2 / MI355X_MICROARCH.md "Valid forms": sc1 payload,
 // every storing wave drained, workgroup barrier, one relaxed agent atomic; the last arriver's loads all sc1).
-template <int BM, int BN, int NT, bool AKM, bool BKM, int D, bool KG, bool GATE, int KS = 1, bool XS = false, bool X3 = false, int KU = 1, bool TTMP = false>
+template <int BM, int BN, int NT, bool AKM, bool BKM, int D, bool KG, bool GATE, int KS = 1, bool XS = false, bool X3 = false, int KU = 1, bool TTMP = false, int NP = 3>
 __device__ __forceinline__ void gemm_tile(const Group& g, const GateArgs* ga) {
     constexpr int NTG = NT / KS;
     constexpr int WM = BM / (NTG / 128), WN = BN / 2;  // per-wave tile; the waves of a k-group in a (NTG/128) x 2 grid
@@ -1045,7 +1085,7 @@ __device__ __forceinline__ void gemm_tile(const Group& g, const GateArgs* ga) {
             static_assert(!X3 || BM != 128 || (BN == 128 && NT == 512 && KS == 1 && KU == 1 && !GATE && !XS), "X3: the 8-wave 128x128 class");
             f32x4 cs = {0.f, 0.f, 0.f, 0.f};
             const bool cs_on = AKM && BKM && !KG && G.cs != nullptr && tn_idx == 0;   // uniform over the workgroup
-            gemm_mainloop_x3<AKM, BKM, KG, TTMP>(A, B, M, N, m0, n0, k_begin, k_end, smem, acc, cs, cs_on);
+            gemm_mainloop_x3<AKM, BKM, KG, TTMP, NP>(A, B, M, N, m0, n0, k_begin, k_end, smem, acc, cs, cs_on);
             if constexpr (AKM && BKM && !KG) {
                 if (cs_on) {
                     // thread (k row tid / 32, column quad tid % 32) holds its k rows' sums: the 16 k rows are added in row order
@@ -1305,9 +1345,9 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(const Group g) {
     gemm_tile<BM, BN, NT, AKM, BKM, D, KG, false>(g, nullptr);
 }
 
-template <bool AKM, bool BKM, bool KG>
+template <bool AKM, bool BKM, bool KG, int NP = 3>   // NP: bf16 planes per operand (gemm_mainloop_x3); 3 unless twog_gemm_set_precision asks
 __global__ __launch_bounds__(512, 4) void gemm_x3_kernel(const Group g) {   // 4 waves per SIMD = two workgroups per CU: <= 128 VGPRs
-    gemm_tile<128, 128, 512, AKM, BKM, 2, KG, false, 1, false, true>(g, nullptr);
+    gemm_tile<128, 128, 512, AKM, BKM, 2, KG, false, 1, false, true, 1, false, NP>(g, nullptr);
 }
 // dW = dY^T X with every k-step's products through a fresh accumulator (TTMP): one workgroup per CU
 template <bool KG>
@@ -1580,7 +1620,20 @@ inline int vec_ok(const twog_rows_t& m, int64_t batch_stride, int contiguous_ext
     return (aligned && ld_ok && contiguous_extent >= 4 && contiguous_extent % 4 == 0) ? 1 : 0;
 }
 
-thread_local int g_last_class_x3 = 0;
+thread_local int g_last_class_x3 = 0;    // 0: not the X3 128x128 class; else the planes per operand of the instantiation that ran
+thread_local int g_precision = TWOG_GEMM_PRECISION_HIGHEST;   // twog_gemm_set_precision(): this thread's launches
+
+// the layout branches (AKM x BKM x KG; row-major A and B have no grouped form) of the X3 128x128 class at NP planes per operand
+template <int NP>
+static void launch_x3_128(const Group& g, bool akm, bool bkm, bool kg, dim3 grid, dim3 block, hipStream_t st) {
+    if (!akm && !bkm) hipLaunchKernelGGL((gemm_x3_kernel<false, false, false, NP>), grid, block, 0, st, g);
+    else if (!akm && bkm && !kg) hipLaunchKernelGGL((gemm_x3_kernel<false, true, false, NP>), grid, block, 0, st, g);
+    else if (!akm && bkm) hipLaunchKernelGGL((gemm_x3_kernel<false, true, true, NP>), grid, block, 0, st, g);
+    else if (akm && bkm && !kg) hipLaunchKernelGGL((gemm_x3_kernel<true, true, false, NP>), grid, block, 0, st, g);
+    else if (akm && bkm) hipLaunchKernelGGL((gemm_x3_kernel<true, true, true, NP>), grid, block, 0, st, g);
+    else if (!kg) hipLaunchKernelGGL((gemm_x3_kernel<true, false, false, NP>), grid, block, 0, st, g);
+    else hipLaunchKernelGGL((gemm_x3_kernel<true, false, true, NP>), grid, block, 0, st, g);
+}
 
 // the bf16x3 128x128 class serves this group: aligned operands, whole 16-deep k-tiles (TWOG_GEMM_X3=0: native fp32 MFMA)
 static bool x3_128_ok(const Group& g) {
@@ -1601,7 +1654,12 @@ int launch(Group& g, int akm, int bkm, hipStream_t st) {
         // X3 (fp32-exact operands on the bf16 matrix cores, gemm_mainloop_x3): aligned operands, whole k-tiles, plain rows
         if (x3_128_ok(g)) {
             static const int split_acc = getenv("TWOG_X3_DW_SPLIT_ACC") ? atoi(getenv("TWOG_X3_DW_SPLIT_ACC")) : 0;
-            if (!akm && !bkm) hipLaunchKernelGGL((gemm_x3_kernel<false, false, false>), grid, block, 0, st, g);
+            // opt-in reduced precision (twog_gemm_set_precision): two or one bf16 plane per operand; the split-accumulator TT
+            // launches keep all six products
+            const int np = (akm && bkm && split_acc) ? 3 : g_precision == TWOG_GEMM_PRECISION_HIGH ? 2 : g_precision == TWOG_GEMM_PRECISION_MEDIUM ? 1 : 3;
+            if (np == 2) launch_x3_128<2>(g, akm, bkm, kg, grid, block, st);
+            else if (np == 1) launch_x3_128<1>(g, akm, bkm, kg, grid, block, st);
+            else if (!akm && !bkm) hipLaunchKernelGGL((gemm_x3_kernel<false, false, false>), grid, block, 0, st, g);
             else if (!akm && bkm && !kg) hipLaunchKernelGGL((gemm_x3_kernel<false, true, false>), grid, block, 0, st, g);
             else if (!akm && bkm) hipLaunchKernelGGL((gemm_x3_kernel<false, true, true>), grid, block, 0, st, g);
             else if (akm && bkm && split_acc && !kg) hipLaunchKernelGGL((gemm_x3_tt_split_acc_kernel<false>), grid, block, 0, st, g);
@@ -1611,7 +1669,7 @@ int launch(Group& g, int akm, int bkm, hipStream_t st) {
             else if (!kg) hipLaunchKernelGGL((gemm_x3_kernel<true, false, false>), grid, block, 0, st, g);
             else hipLaunchKernelGGL((gemm_x3_kernel<true, false, true>), grid, block, 0, st, g);
             TWOG_CHECK_LAUNCH();
-            g_last_class_x3 = 1;
+            g_last_class_x3 = np;
             if (g.splitk > 1) {
                 hipLaunchKernelGGL((splitk_reduce_kernel<BM, BN>), dim3(g.total_tiles, (BM * BN) / 1024), dim3(256), 0, st, g);
                 TWOG_CHECK_LAUNCH();
@@ -1642,6 +1700,14 @@ thread_local int g_last_class = 0;  // twog_gemm_last_class(): variant of this t
 }  // namespace
 
 extern "C" int twog_gemm_last_class(void) { return g_last_class; }
+
+extern "C" int twog_gemm_set_precision(int p) {
+    if (p != TWOG_GEMM_PRECISION_HIGHEST && p != TWOG_GEMM_PRECISION_HIGH && p != TWOG_GEMM_PRECISION_MEDIUM) return -1;
+    const int prev = g_precision;
+    g_precision = p;
+    return prev;
+}
+extern "C" int twog_gemm_get_precision(void) { return g_precision; }
 
 // Builds the launch descriptor of one chunk (<= MAXP problems): tile class, class-sorted problem list (order[i] = index of
 // the caller's problem that became sorted problem i), XCD map, split-K. Shared by the plain and the gate-fused launch.
@@ -2118,7 +2184,8 @@ static int gemm_impl(const twog_gemm_t* problems, int n_problems, int a_kmajor, 
         }
         else rc = d64 == 2 ? launch<64, 64, 256, 2>(g, a_kmajor, b_kmajor, st) : launch<64, 64, 256, 1>(g, a_kmajor, b_kmajor, st);
         if (rc) return rc;
-        if (g_last_class_x3) g_last_class |= TWOG_GEMM_CLASS_X3 | TWOG_GEMM_CLASS_WAVES8;
+        if (g_last_class_x3) g_last_class |= TWOG_GEMM_CLASS_X3 | TWOG_GEMM_CLASS_WAVES8 |
+                                             (g_last_class_x3 == 2 ? TWOG_GEMM_CLASS_P3 : g_last_class_x3 == 1 ? TWOG_GEMM_CLASS_P1 : 0);
         done += n;
     }
     return 0;

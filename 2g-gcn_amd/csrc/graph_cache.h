@@ -20,6 +20,8 @@
 #include <unordered_map>
 #include <unordered_set>
 
+extern "C" int twog_gemm_get_precision(void);   // include/twog_gcn.h
+
 namespace twog_graph {
 
 inline uint64_t fnv1a(const void* data, size_t n, uint64_t h = 1469598103934665603ull) {
@@ -61,10 +63,13 @@ inline uint64_t collisions() { return state().collisions; }
 // Graphs are captured and replayed on a stream owned by the library (the caller's stream may be the legacy default
 // stream, which cannot be captured), fenced against the caller's stream with two events.
 template <class F>
-int run(const Desc& d, hipStream_t user, F enqueue) {
+int run(const Desc& d_in, hipStream_t user, F enqueue) {
     // read per call (two getenv calls against hundreds of launches): tests switch it inside one process
     const char* on_env = getenv("TWOG_GRAPHS");
     if (!on_env || atoi(on_env) == 0 || getenv("TWOG_NO_GRAPHS") != nullptr) return enqueue(user);
+    // a captured loop holds the GEMM instantiations of the precision it was captured under (twog_gemm_set_precision)
+    Desc d = d_in;
+    d.pod(twog_gemm_get_precision());
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) {
         (void)hipGetLastError();

@@ -8,6 +8,7 @@ memory and streams; no torch math runs here. There is no CPU / eager fallback: o
 Row-strided views: a matrix operand may be a 2-D view (rows, cols) or a 3-D view (outer, inner, cols) with unit
 stride on cols -- it maps onto twog_rows_t without a copy.
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -370,10 +371,26 @@ class HipKernels:
     GEMM_TILE128, GEMM_WAVES8, GEMM_KG, GEMM_SPLITK, GEMM_GATE, GEMM_KSPLIT, GEMM_GRUFWD, GEMM_ROWS32 = 1, 2, 4, 8, 16, 32, 64, 128  # TWOG_GEMM_CLASS_*
     GEMM_XSPLIT = 256
     GEMM_X3 = 512
+    GEMM_P3, GEMM_P1 = 1024, 2048   # beside GEMM_X3 on the 128x128 class: the 'high' (3 products) / 'medium' (1 product) kernels ran
 
     def gemm_last_class(self):
         """Bit field (GEMM_*) of the kernel variant the most recent gemm() chunk of this thread selected."""
         return int(self.lib.twog_gemm_last_class())
+
+    MATMUL_PRECISIONS = {'highest': 0, 'high': 1, 'medium': 2}   # TWOG_GEMM_PRECISION_*
+
+    @contextlib.contextmanager
+    def matmul_precision(self, name):
+        """The GEMMs of the bf16x3 128x128 class that THIS thread launches inside the block keep six ('highest', the default),
+        three ('high') or one ('medium') chunk product per multiply (twog_gemm_set_precision); every other kernel is unaffected.
+        The previous setting comes back on exit, also when the block raises."""
+        if name not in self.MATMUL_PRECISIONS:
+            raise ValueError(f"matmul precision must be one of {sorted(self.MATMUL_PRECISIONS)}, not {name!r}")
+        prev = int(self.lib.twog_gemm_set_precision(self.MATMUL_PRECISIONS[name]))
+        try:
+            yield
+        finally:
+            self.lib.twog_gemm_set_precision(prev)
 
     # ---------------------------------------------------------------- geometric-level GCN
     @staticmethod

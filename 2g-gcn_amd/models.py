@@ -268,6 +268,23 @@ class TGGCN(nn.Module):
         seed, calls = dn['state'].tolist() if dn['state'] is not None else (dn['seed'], dn['calls'])
         return seed % 2 ** 64, calls % 2 ** 64
 
+    # ---- matmul precision of the dense projections and weight gradients (the bf16x3 128x128 GEMM class). Opt-in per model,
+    # kept in the side table like the noise source: not in state_dict(), not carried by copy.deepcopy, and never taken from
+    # torch.get_float32_matmul_precision() -- what a user set there for another model must not change this one.
+    def use_matmul_precision(self, name: str):
+        """'highest' (the default: fp32 results, six bf16 chunk products per multiply), 'high' (three products on two planes
+        rounded to nearest, about 16 significand bits) or 'medium' (one bf16 product), for the 128x128-class GEMMs of this
+        model's forward and backward passes from the next forward on; INTEGRATION.md, "Matmul precision". Hard gate decisions
+        and ReLU masks can differ from 'highest'."""
+        if name not in ops.MATMUL_PRECISIONS:
+            raise ValueError(f'matmul precision must be one of {list(ops.MATMUL_PRECISIONS)}, not {name!r}')
+        ops.set_model_extra(self, 'matmul_precision', None if name == 'highest' else name)
+        return self
+
+    def matmul_precision(self):
+        """The name set by use_matmul_precision ('highest' unless it was called)."""
+        return ops.get_model_extra(self, 'matmul_precision') or 'highest'
+
     def _device_noise(self, dn, T, n_gated, bs, like):
         K = get_kernels()
         if dn['state'] is None or dn['state'].device != like.device:
@@ -302,6 +319,7 @@ class TGGCN(nn.Module):
                         human_segmentation is not None, objects_segmentation is not None)
         plan.stage_hook = ops.get_model_extra(self, 'stage_hook')   # data-parallel overlap (ops.set_grad_stage_hook)
         plan.dists = dists or None
+        plan.matmul_precision = self.matmul_precision()
         plan.steps = None
         if steps_per_example is not None and (plan.time_s or plan.time_u or plan.seglen):
             plan.steps = steps_per_example.to(device=x_human.device, dtype=torch.float32).contiguous()

@@ -13,6 +13,7 @@ buffers laid out for those kernels:
 
 No torch math is used on the data path (torch owns memory, streams, and the autograd graph edge).
 """
+import contextlib
 import math
 import os
 import weakref
@@ -139,6 +140,9 @@ class Plan:
         # tuning / test switch, read ONCE per forward call: the backward pass of this call follows the same decision even
         # if the variable changes in between (it reads what the forward saved for exactly that form)
         self.no_ssp = bool(os.environ.get('TWOG_NO_SSP'))
+        # opt-in (models.TGGCN.use_matmul_precision): 'high' / 'medium' run the passes of this call inside
+        # kernels.matmul_precision(name); 'highest' makes no call at all
+        self.matmul_precision = 'highest'
 
     def general_frame(self):
         """True when the frame-level messages need the general single-relation kernels (relation.hip) instead of the
@@ -1252,8 +1256,33 @@ def segment_recurrence_general_bwd(K, p, P, G, bufs, gi_unused, u, objects_mask,
     return out
 
 
-def tggcn_forward(K, plan: Plan, P, x_human, x_objects, objects_mask, human_seg, object_seg, noise, training, bn_bufs,
-                  backward_follows=False):
+MATMUL_PRECISIONS = ('highest', 'high', 'medium')
+
+
+def _matmul_precision(K, plan):
+    """The context a pass of `plan` runs in: kernels.matmul_precision(name) when the plan asks for anything but 'highest' --
+    entered by the thread that issues the pass's launches (the backward pass runs on autograd's thread; the setting is
+    thread-local) -- and nothing at all otherwise. A kernels object without the method (the test double) is tolerated."""
+    name = getattr(plan, 'matmul_precision', 'highest')
+    if name == 'highest' or not hasattr(K, 'matmul_precision'):
+        return contextlib.nullcontext()
+    return K.matmul_precision(name)
+
+
+def tggcn_forward(K, plan: Plan, *args, **kwargs):
+    """_tggcn_forward inside the plan's matmul precision."""
+    with _matmul_precision(K, plan):
+        return _tggcn_forward(K, plan, *args, **kwargs)
+
+
+def tggcn_backward(K, plan: Plan, *args, **kwargs):
+    """_tggcn_backward inside the plan's matmul precision."""
+    with _matmul_precision(K, plan):
+        return _tggcn_backward(K, plan, *args, **kwargs)
+
+
+def _tggcn_forward(K, plan: Plan, P, x_human, x_objects, objects_mask, human_seg, object_seg, noise, training, bn_bufs,
+                   backward_follows=False):
     """Returns (outputs list, saved dict). P: dict name -> parameter tensor. backward_follows: the caller records an autograd
     node (the deferred checks of persistent launches may then wait for the end of the backward pass)."""
     p = plan
@@ -1553,8 +1582,8 @@ def tggcn_forward(K, plan: Plan, P, x_human, x_objects, objects_mask, human_seg,
     return outputs, S
 
 
-def tggcn_backward(K, plan: Plan, P, S, x_human, x_objects, objects_mask, d_outputs, sinks=None, input_grads=None,
-                   training=True):
+def _tggcn_backward(K, plan: Plan, P, S, x_human, x_objects, objects_mask, d_outputs, sinks=None, input_grads=None,
+                    training=True):
     """Hand-derived backward pass. d_outputs: list aligned with the forward outputs (None = no gradient).
     Returns dict name -> gradient for every parameter used by the forward that has no entry in `sinks`
     (see _Grads: gradients with a sink have been added into it).

@@ -85,7 +85,24 @@ int twog_gemm_colsum_fused(const twog_gemm_t* problems, int n_problems, int a_km
 #define TWOG_GEMM_CLASS_ROWS32  128 /* 32 x 64 tiles (chain launches of small batches)           */
 #define TWOG_GEMM_CLASS_XSPLIT  256 /* reduction split over workgroups, combined inside the launch (last arriver) */
 #define TWOG_GEMM_CLASS_X3      512 /* on the bf16 matrix cores: fp32 operands split exactly into 3 bf16, 6 products (128x128 class; 64x64 class when K >= 256) */
+#define TWOG_GEMM_CLASS_P3      1024 /* beside X3, 128x128 class: the 'high' instantiation ran (two planes, 3 products)   */
+#define TWOG_GEMM_CLASS_P1      2048 /* beside X3, 128x128 class: the 'medium' instantiation ran (one plane, 1 product)  */
 int twog_gemm_last_class(void);
+
+/* Opt-in matmul precision of the bf16x3 128x128 class (the dense projections and weight gradients), per calling thread;
+ * the names follow torch.set_float32_matmul_precision. HIGHEST (the default): three bf16 planes per operand, six products,
+ * fp32 results. HIGH: two planes rounded to nearest (h = rne(x), m = rne(x - h)), the products h h + h m + m h:
+ * |error| <= (2 + 2^-6) 2^-16 sum |a||b|. MEDIUM: one plane h = rne(x), the product h h: |error| <= (2^-7 + 2^-16) sum |a||b|.
+ * Both accumulate in fp32. Every other GEMM class (64x64, chain, gate- and GRU-fused, persistent), the split-accumulator TT
+ * launches (TWOG_X3_DW_SPLIT_ACC=1) and the native fp32 kernels (TWOG_GEMM_X3=0) ignore the setting.
+ * twog_gemm_set_precision returns the previous value, or -1 (nothing changed) for an unknown p. The setting belongs to the
+ * thread that made it -- a backward pass on autograd's thread has its own -- and applies to every launch that thread issues,
+ * the library's own loops and tape replays included. */
+#define TWOG_GEMM_PRECISION_HIGHEST 0
+#define TWOG_GEMM_PRECISION_HIGH    1
+#define TWOG_GEMM_PRECISION_MEDIUM  2
+int twog_gemm_set_precision(int p);
+int twog_gemm_get_precision(void);
 
 /* The dependent launches of the recurrent chains (vhoi/models.py:983-1002 frame-level BiGRUs, :785-880 segment loop:
  * few output tiles, K = h ... 3h, every launch waiting for the previous one). `chain_ws` is a caller-owned scratch of
