@@ -301,6 +301,8 @@ SIGNATURES = {
     'twog_segment_f1': [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_double), _I, _L, _I, _P, _P, _P, _P, _P, _P],
     'twog_segment_f1_accumulate': [_P, _P, _I, _I, _P, _P, _P],
     'twog_segment_f1_limits': [C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    'twog_segment_edit': [_P, _P, _I, _I, _I, _L, _I, _L, _I, _P, _P, _P, _P, _P, _P],
+    'twog_segment_edit_limits': [C.POINTER(C.c_int)],
 }
 
 _lib = None

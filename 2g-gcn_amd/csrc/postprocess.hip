@@ -375,6 +375,144 @@ __global__ __launch_bounds__(SEGF1_THREADS) void segment_f1_accumulate_kernel(co
     }
 }
 
+// ---- segmental edit score with a workgroup per sequence: 100 * (1 - Levenshtein(true segments, predicted segments) /
+// max(m, n)), unit costs. The ignored steps are dropped first (the rule and the compaction of segment_f1_kernel), both
+// filtered sequences are run-length encoded, and a segment whose label is bg_label is left out of its list WITHOUT
+// merging its neighbours: a step opens a list entry iff it starts a run and its label is not the background.
+// The table D[i][j] (i <= m true segments, j <= n predicted ones) is filled over its anti-diagonals d = i + j: a cell
+// needs D[i-1][j] and D[i][j-1] of diagonal d - 1 and D[i-1][j-1] of diagonal d - 2, so three rolling diagonals indexed
+// by i are the whole state, with one barrier per diagonal (it orders the writes of d before the reads of d + 1, and the
+// reads of d - 2 before d + 1 overwrites that buffer).
+// LDS: tl[] / pl[] the two segment-label lists as int64 (labels are compared exactly, without a second look at global
+// memory), then three diagonals of (rounded + 2) 16-bit entries (values <= SEGF1_MAX_STEPS). orig[] (the step of the
+// q-th kept step, needed until the lists exist) lies on the first diagonal. 16 * rounded + 6 * (rounded + 2) bytes:
+// 90 124 at 4096 steps, one workgroup per CU; 8 460 at the 384 an evaluation batch has.
+inline size_t segedit_lds_bytes(int n_steps) {
+    const int r = segf1_round_steps(n_steps);
+    return (size_t)2 * r * sizeof(long long) + (size_t)3 * (r + 2) * sizeof(unsigned short);
+}
+
+__device__ __forceinline__ double segment_edit_value(int distance, int longer) {
+#pragma clang fp contract(off)
+    const double ratio = (double)distance / (double)longer;
+    const double kept = 1.0 - ratio;
+    return kept * 100.0;
+}
+
+// Diagonal d of the table: its two border cells (0, d) and (d, 0), then the inner cells i = lo + tid, lo + tid + 256, ...
+// without a branch. The diagonal written is none of the four arrays read, which the qualifiers say, so that the loads of
+// several cells are in flight together.
+__device__ __forceinline__ void segment_edit_diagonal(unsigned short* __restrict__ cur, const unsigned short* __restrict__ p1,
+                                                      const unsigned short* __restrict__ p2, const long long* __restrict__ tl,
+                                                      const long long* __restrict__ pl, int d, int m, int n, int tid) {
+    if (tid == 0 && d <= n) cur[0] = (unsigned short)d;
+    if (tid == 1 && d <= m) cur[d] = (unsigned short)d;
+    const int lo = max(1, d - n), hi = min(d - 1, m);
+#pragma unroll 4
+    for (int i = lo + tid; i <= hi; i += SEGF1_THREADS) {
+        const int edge = min((int)p1[i - 1], (int)p1[i]) + 1;                          // deletion, insertion
+        const int subst = (int)p2[i - 1] + (tl[i - 1] != pl[d - i - 1] ? 1 : 0);
+        cur[i] = (unsigned short)min(edge, subst);
+    }
+}
+
+__global__ __launch_bounds__(SEGF1_THREADS) void segment_edit_kernel(
+    const long long* y_true, const long long* y_pred, int n_steps, int entities, long long ignore, int use_ignore,
+    long long bg, int use_bg, double* score_out, int* dist_out, int* n_true_out, int* n_pred_out, int* valid_out) {
+    extern __shared__ long long segedit_lds[];
+    __shared__ int wave_cnt[2][SEGF1_WAVES];
+    const int rounded = (n_steps + 63) & ~63;
+    long long* tl = segedit_lds;
+    long long* pl = tl + rounded;
+    unsigned short* diag0 = reinterpret_cast<unsigned short*>(pl + rounded);
+    unsigned short* diag1 = diag0 + (rounded + 2);
+    unsigned short* diag2 = diag1 + (rounded + 2);
+    unsigned short* orig = diag0;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x;
+    int64_t off, stride;
+    if (entities > 0) { off = (int64_t)(s / entities) * n_steps * entities + s % entities; stride = entities; }
+    else { off = (int64_t)s * n_steps; stride = 1; }
+    const long long* yt = y_true + off;
+    const long long* yp = y_pred + off;
+
+    // 1. drop the ignored steps: orig[q] = step of the q-th kept one
+    int n_kept = 0;
+    for (int base = 0; base < n_steps; base += SEGF1_THREADS) {
+        const int i = base + tid;
+        const bool kept = i < n_steps && !(use_ignore && yt[(int64_t)i * stride] == ignore);
+        const unsigned long long mask = __ballot(kept);
+        if (lane == 0) wave_cnt[0][wave] = __popcll(mask);
+        __syncthreads();
+        int before = n_kept, total = n_kept;
+        for (int w = 0; w < SEGF1_WAVES; ++w) {
+            const int c = wave_cnt[0][w];
+            if (w < wave) before += c;
+            total += c;
+        }
+        if (kept) orig[before + lanes_below(mask)] = (unsigned short)i;
+        n_kept = total;
+        __syncthreads();
+    }
+
+    // 2. the two lists: one entry per run start whose label is not the background
+    int m = 0, n = 0;
+    for (int base = 0; base < n_kept; base += SEGF1_THREADS) {
+        const int q = base + tid;
+        bool ts = false, ps = false;
+        long long tlab = 0, plab = 0;
+        if (q < n_kept) {
+            const int64_t at = (int64_t)orig[q] * stride;
+            tlab = yt[at];
+            plab = yp[at];
+            ts = ps = q == 0;
+            if (q > 0) {
+                const int64_t prev = (int64_t)orig[q - 1] * stride;
+                ts = tlab != yt[prev];
+                ps = plab != yp[prev];
+            }
+            ts = ts && !(use_bg && tlab == bg);
+            ps = ps && !(use_bg && plab == bg);
+        }
+        const unsigned long long tmask = __ballot(ts), pmask = __ballot(ps);
+        if (lane == 0) { wave_cnt[0][wave] = __popcll(tmask); wave_cnt[1][wave] = __popcll(pmask); }
+        __syncthreads();
+        int tbefore = m, ttotal = m, pbefore = n, ptotal = n;
+        for (int w = 0; w < SEGF1_WAVES; ++w) {
+            const int ct = wave_cnt[0][w], cp = wave_cnt[1][w];
+            if (w < wave) { tbefore += ct; pbefore += cp; }
+            ttotal += ct;
+            ptotal += cp;
+        }
+        if (ts) tl[tbefore + lanes_below(tmask)] = tlab;
+        if (ps) pl[pbefore + lanes_below(pmask)] = plab;
+        m = ttotal;
+        n = ptotal;
+        __syncthreads();
+    }
+    const int longer = max(m, n);
+    if (longer == 0) {   // no kept step, or nothing but background: an all-zero row that the mean skips. m and n are
+        if (tid == 0) {  // workgroup-uniform, and no barrier follows
+            score_out[s] = 0.0; dist_out[s] = 0; n_true_out[s] = 0; n_pred_out[s] = 0; valid_out[s] = 0;
+        }
+        return;
+    }
+
+    // 3. the table, diagonal by diagonal (orig[] is dead: the last barrier of phase 2 is behind every read of it)
+    unsigned short *cur = diag0, *p1 = diag2, *p2 = diag1;   // diagonals d, d - 1, d - 2
+    for (int d = 0; d <= m + n; ++d) {
+        segment_edit_diagonal(cur, p1, p2, tl, pl, d, m, n, tid);
+        __syncthreads();
+        unsigned short* freed = p2;
+        p2 = p1; p1 = cur; cur = freed;
+    }
+    if (tid == 0) {   // p1 is the last diagonal written, d = m + n, whose one cell is i = m
+        const int distance = p1[m];
+        score_out[s] = segment_edit_value(distance, longer);
+        dist_out[s] = distance; n_true_out[s] = m; n_pred_out[s] = n; valid_out[s] = 1;
+    }
+}
+
 }  // namespace
 
 extern "C" int twog_predict_labels(const float* logp, int bs, int n_classes, int T, int E, int downsampling, int T_out,
@@ -472,6 +610,31 @@ extern "C" int twog_segment_f1_accumulate(const double* f1, const int32_t* valid
     if (n_seq == 0) return 0;
     hipLaunchKernelGGL(segment_f1_accumulate_kernel, dim3(1), dim3(SEGF1_THREADS), 0, (hipStream_t)stream, f1, valid, n_seq,
                        n_overlaps, f1_sums, valid_sums);
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int twog_segment_edit_limits(int* max_steps) {
+    if (max_steps) *max_steps = SEGF1_MAX_STEPS;
+    return 0;
+}
+
+extern "C" int twog_segment_edit(const int64_t* y_true, const int64_t* y_pred, int n_seq, int n_steps, int entities,
+                                 int64_t ignore_value, int use_ignore, int64_t bg_label, int use_bg, double* score,
+                                 int32_t* distance, int32_t* n_true, int32_t* n_pred, int32_t* valid, void* stream) {
+    if (n_seq < 0 || n_steps < 0 || entities < 0 || (entities > 0 && n_seq % entities != 0)) return -1;
+    if (n_steps > SEGF1_MAX_STEPS) return -2;
+    if (n_seq == 0) return 0;
+    // n_steps == 0 is launched like any other length, as twog_segment_f1 does: every sequence is empty, and the kernel
+    // writes its all-zero row
+    constexpr int LDS_LIMIT = 2 * SEGF1_MAX_STEPS * 8 + 3 * (SEGF1_MAX_STEPS + 2) * 2;
+    static_assert(LDS_LIMIT + 64 <= 160 * 1024, "the LDS layout at the longest sequence fits one CU");
+    static std::atomic<uint32_t> lds_attr_done{0};
+    twog_allow_dynamic_lds(segment_edit_kernel, LDS_LIMIT, lds_attr_done);
+    hipLaunchKernelGGL(segment_edit_kernel, dim3(n_seq), dim3(SEGF1_THREADS), segedit_lds_bytes(n_steps),
+                       (hipStream_t)stream, reinterpret_cast<const long long*>(y_true),
+                       reinterpret_cast<const long long*>(y_pred), n_steps, entities, (long long)ignore_value, use_ignore,
+                       (long long)bg_label, use_bg, score, distance, n_true, n_pred, valid);
     TWOG_CHECK_LAUNCH();
     return 0;
 }

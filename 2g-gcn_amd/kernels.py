@@ -1525,6 +1525,34 @@ class HipKernels:
         self._check(self.lib.twog_segment_f1_accumulate(f1.data_ptr(), valid.data_ptr(), n_seq, K, f1_sums.data_ptr(),
                                                         valid_sums.data_ptr(), self._stream()), 'twog_segment_f1_accumulate')
 
+    def segment_edit_limits(self):
+        """The longest sequence segment_edit takes: the max_steps of segment_f1_limits."""
+        max_steps = C.c_int(0)
+        self._check(self.lib.twog_segment_edit_limits(C.byref(max_steps)), 'twog_segment_edit_limits')
+        return max_steps.value
+
+    def segment_edit(self, y_true, y_pred, ignore_value=None, bg_label=None, entity_minor=False):
+        """Per-sequence segmental edit score, one launch. int64 labels, read in place in the layouts of segment_f1:
+        (n_seq, n_steps), or with entity_minor (bs, n_steps, E). Returns (score float64 (n_seq,), distance, n_true, n_pred,
+        valid int32 (n_seq,), packed): the five are views of the one int64 buffer `packed` (see unpack_segment_edit)."""
+        assert y_true.dtype == torch.int64 and y_pred.dtype == torch.int64 and y_true.shape == y_pred.shape
+        assert y_true.dim() == (3 if entity_minor else 2), tuple(y_true.shape)
+        y_true, y_pred = y_true.contiguous(), y_pred.contiguous()
+        if entity_minor:
+            bs, n_steps, E = y_true.shape
+            n_seq = bs * E
+        else:
+            (n_seq, n_steps), E = y_true.shape, 0
+        packed = torch.empty(segment_edit_words(n_seq), dtype=torch.int64, device=y_true.device)
+        score, distance, n_true, n_pred, valid = unpack_segment_edit(packed, n_seq)
+        self._check(self.lib.twog_segment_edit(y_true.data_ptr(), y_pred.data_ptr(), n_seq, n_steps, E,
+                                               int(ignore_value) if ignore_value is not None else 0,
+                                               int(ignore_value is not None), int(bg_label) if bg_label is not None else 0,
+                                               int(bg_label is not None), score.data_ptr(), distance.data_ptr(),
+                                               n_true.data_ptr(), n_pred.data_ptr(), valid.data_ptr(), self._stream()),
+                    'twog_segment_edit')
+        return score, distance, n_true, n_pred, valid, packed
+
 
 def segment_f1_words(n_seq, K):
     """8-byte words of the packed result of segment_f1: n_seq * K fp64, then (3 * n_seq * K + n_seq) int32."""
@@ -1537,6 +1565,20 @@ def unpack_segment_f1(packed, n_seq, K):
     ints = packed[n_seq * K:].view(torch.int32)
     tp, fp, fn = (ints[j * n_seq * K:(j + 1) * n_seq * K].view(n_seq, K) for j in range(3))
     return f1, tp, fp, fn, ints[3 * n_seq * K:3 * n_seq * K + n_seq]
+
+
+def segment_edit_words(n_seq):
+    """8-byte words of the packed result of segment_edit: n_seq fp64, then 4 * n_seq int32."""
+    return 3 * n_seq
+
+
+def unpack_segment_edit(packed, n_seq):
+    """(score, distance, n_true, n_pred, valid) as views of the packed int64 buffer of segment_edit, on whichever device
+    it is."""
+    score = packed[:n_seq].view(torch.float64)
+    ints = packed[n_seq:3 * n_seq].view(torch.int32)
+    distance, n_true, n_pred, valid = (ints[j * n_seq:(j + 1) * n_seq] for j in range(4))
+    return score, distance, n_true, n_pred, valid
 
 
 _backend = None

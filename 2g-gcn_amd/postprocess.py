@@ -12,6 +12,9 @@ recall and F1, the per-class report), the Bimanual 15-fps fix-up `downsample_bad
 twog_confusion_counts); every metric is a few hundred fp64 divisions on those integers, done on the host in numpy with
 scikit-learn's semantics, so scikit-learn itself is not needed. `EvaluationAccumulator` keeps the counts and the F1@k
 sums on the device over a whole test set and merges over ranks by a sum.
+
+The segmental edit score (twog_segment_edit) is the third number an action-segmentation model is reported with; the
+reference does not compute it, so its definition is stated at `edit_score_per_example`.
 """
 from collections import namedtuple
 
@@ -19,7 +22,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .kernels import get_kernels, unpack_segment_f1
+from .kernels import get_kernels, unpack_segment_edit, unpack_segment_f1
 
 
 def match_shape(out: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
@@ -201,6 +204,59 @@ def f1_scores_per_example(outputs: dict, targets: dict, test_ids, num_subactivit
             with open(file, mode='w') as f:
                 f.write(text)
     return text
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# segmental edit score per example (twog_segment_edit)
+SegmentEdit = namedtuple('SegmentEdit', 'score distance n_true n_pred valid')
+SegmentEdit.__doc__ = """score float64 (n_seq,); distance, n_true, n_pred int32 (n_seq,): the Levenshtein distance between the
+true and the predicted list of segment labels and their lengths; valid int32 (n_seq,), 0 for a sequence without a kept
+step or with both lists empty (its other entries are zero)."""
+
+
+def _sequential_mean(values, valid) -> float:
+    """The values of the valid sequences added in sequence order in fp64, over their number; NaN when there is none."""
+    total = 0.0
+    for v in values[valid != 0]:
+        total += float(v)
+    n_valid = float(valid.sum())
+    return total / n_valid if n_valid else float('nan')
+
+
+def edit_score_per_example(y_true, y_pred, ignore_value: float = None, *, bg_label=None) -> SegmentEdit:
+    """The segmental edit score of every sequence of (n_seq, n_steps) label matrices, in one launch, as a SegmentEdit of
+    device tensors. Steps whose target is `ignore_value` are dropped from both sequences, both are run-length encoded
+    into lists of segment labels, with `bg_label` the segments of that label are removed from both lists (the neighbours
+    this brings together are NOT merged: A bg A is [A, A]), and score = 100 * (1 - Levenshtein distance / length of the
+    longer list) with unit insertion, deletion and substitution costs. Raises RuntimeError above the kernel's step limit
+    (`get_kernels().segment_edit_limits()`): there is no second route."""
+    yt, yp = _label_matrices(y_true, y_pred)
+    res = get_kernels().segment_edit(yt.reshape(-1, yt.shape[-1]), yp.reshape(-1, yp.shape[-1]), ignore_value, bg_label)
+    return SegmentEdit(*res[:5])
+
+
+def edit_score(y_true, y_pred, *, ignore_value: float = None, bg_label=None) -> float:
+    """The mean of `edit_score_per_example` over the valid sequences, added on the host in sequence order in fp64 after
+    one copy; NaN when no sequence is valid."""
+    yt, yp = _label_matrices(y_true, y_pred)
+    n_seq = yt.numel() // yt.shape[-1] if yt.shape[-1] else 0
+    packed = get_kernels().segment_edit(yt.reshape(-1, yt.shape[-1]), yp.reshape(-1, yp.shape[-1]), ignore_value, bg_label)[5]
+    score, _, _, _, valid = unpack_segment_edit(packed.cpu(), n_seq)
+    return _sequential_mean(score.numpy(), valid.numpy())
+
+
+def evaluate_edit_score(targets: dict, outputs: dict, bg_label=None) -> dict:
+    """{index: labels (N, T) or (N, T, E)} -> {index: mean segmental edit score}, for the dictionaries
+    `evaluate_f1_at_k_multi` takes: -1 targets ignored, the labels read in place (no transposition), one launch and one
+    copy per index."""
+    K = get_kernels()
+    results = {}
+    for index, target in sorted(targets.items()):
+        target, output = _entity_minor(target, outputs[index])
+        packed = K.segment_edit(target, output, -1, bg_label, entity_minor=True)[5]
+        score, _, _, _, valid = unpack_segment_edit(packed.cpu(), target.shape[0] * target.shape[2])
+        results[index] = _sequential_mean(score.numpy(), valid.numpy())
+    return results
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -386,9 +442,12 @@ class EvaluationAccumulator:
     overlap on transposed copies of the labels (fp32 per-sequence values); 'workgroup' runs twog_segment_f1 once for all
     overlaps on the labels as eval_update wrote them and twog_segment_f1_accumulate (fp64 throughout), and falls back to
     'thread' for a batch it cannot take (an overlap <= 0, more steps than its limit). `last_f1_route` names what the last
-    update ran."""
+    update ran. edit: also keep, per name, the sum of the per-sequence segmental edit scores (twog_segment_edit on the same
+    labels, `bg_label` as in `edit_score_per_example`) and of its valid sequences; `result()[name]['edit']` is their
+    ratio. That metric has one route: a batch with more steps than `segment_edit_limits()` is a ValueError."""
 
-    def __init__(self, names, num_classes, downsampling: int = 1, overlaps=(0.1, 0.25, 0.5), f1_route: str = 'thread'):
+    def __init__(self, names, num_classes, downsampling: int = 1, overlaps=(0.1, 0.25, 0.5), f1_route: str = 'thread',
+                 edit: bool = False, bg_label=None):
         if f1_route not in ('thread', 'workgroup'):
             raise ValueError(f"f1_route must be 'thread' or 'workgroup', not {f1_route!r}")
         self.f1_route = f1_route
@@ -399,12 +458,18 @@ class EvaluationAccumulator:
             raise ValueError('num_classes must be one int or one per name')
         self.downsampling = max(1, int(downsampling))
         self.overlaps = tuple(float(o) for o in overlaps)
-        self._state = None   # 8-byte words: per name [C * C counts, 2 flags] as int64, then per name [f1 sums, valid sums] as fp64
+        self.edit = bool(edit)
+        self.bg_label = bg_label
+        # 8-byte words: per name [C * C counts, 2 flags] as int64, then per name [f1 sums, valid sums] as fp64, then with
+        # `edit` per name [edit sum, valid sum] as fp64
+        self._state = None
 
     def _allocate(self, device):
         n_int = sum(c * c + 2 for c in self.num_classes)
         n_ov = len(self.overlaps)
-        self._state = get_kernels().zeros(n_int + 2 * n_ov * len(self.names), dtype=torch.int64, device=device)
+        n_f1 = 2 * n_ov * len(self.names)
+        n_edit = 2 * len(self.names) if self.edit else 0
+        self._state = get_kernels().zeros(n_int + n_f1 + n_edit, dtype=torch.int64, device=device)
         self._ints = self._state[:n_int]
         self._floats = self._state[n_int:].view(torch.float64)
         self._counts, self._flags, self._f1, self._valid = [], [], [], []
@@ -415,6 +480,9 @@ class EvaluationAccumulator:
             at += c * c + 2
             self._f1.append(self._floats[2 * n_ov * i:2 * n_ov * i + n_ov])
             self._valid.append(self._floats[2 * n_ov * i + n_ov:2 * n_ov * (i + 1)])
+        if self.edit:
+            self._edit = [self._floats[n_f1 + 2 * i:n_f1 + 2 * i + 1] for i in range(len(self.names))]
+            self._edit_valid = [self._floats[n_f1 + 2 * i + 1:n_f1 + 2 * i + 2] for i in range(len(self.names))]
 
     def update(self, outputs, targets, step_index=None):
         """One batch: outputs / targets are the model's lists (the last len(names) are used), output (bs, C, T, E)
@@ -426,6 +494,12 @@ class EvaluationAccumulator:
         outputs, targets = list(outputs)[-n:], list(targets)[-n:]
         if len(outputs) != n or len(targets) != n:
             raise ValueError(f'{n} outputs and targets expected')
+        if self.edit:   # before anything is added to the state
+            max_steps = K.segment_edit_limits()
+            for name, tgt in zip(self.names, targets):
+                steps = step_index.shape[1] if step_index is not None else tgt.shape[1]
+                if steps > max_steps:
+                    raise ValueError(f'output {name!r}: the edit score takes up to {max_steps} steps per batch, not {steps}')
         for i, (out, tgt) in enumerate(zip(outputs, targets)):
             if out.ndim != 4:
                 raise RuntimeError(f'Number of dimensions for output is {out.ndim}')  # predict.py:66-67
@@ -437,6 +511,9 @@ class EvaluationAccumulator:
                 step_index = step_index.to(device=out.device, dtype=torch.int32)
             labels, kept = K.eval_update(out, self.downsampling, tgt.to(torch.int64), step_index, self._counts[i],
                                          self._flags[i], want_labels=True)
+            if self.edit:
+                score, _, _, _, edit_valid, _ = K.segment_edit(kept, labels, -1, self.bg_label, entity_minor=True)
+                K.segment_f1_accumulate(score.view(-1, 1), edit_valid, self._edit[i], self._edit_valid[i])
             if self.f1_route == 'workgroup' and self.overlaps and self._update_f1_workgroup(K, i, kept, labels):
                 continue
             self.last_f1_route = 'thread'
@@ -473,7 +550,8 @@ class EvaluationAccumulator:
     def result(self) -> dict:
         """{name: {'micro': {...}, 'macro': {...}, 'report': {...}, 'f1@k': {overlap: value}, 'confusion': ndarray}}.
         Raises ValueError if a target was outside [-1, C) or a step_index entry pointed beyond the targets. F1@k is
-        NaN when no sequence had a counted step (the reference divides by zero there)."""
+        NaN when no sequence had a counted step (the reference divides by zero there). With `edit` every name has
+        'edit' too: the mean segmental edit score, NaN when no sequence was valid."""
         if self._state is None:
             raise RuntimeError('result before the first update')
         host = self._state.cpu().numpy()   # the one device-to-host copy
@@ -491,4 +569,7 @@ class EvaluationAccumulator:
                          'f1@k': {ov: (float(f1[j] / valid[j]) if valid[j] > 0 else float('nan'))
                                   for j, ov in enumerate(self.overlaps)},
                          'confusion': counts}
+            if self.edit:
+                total, n_valid = floats[2 * n_ov * len(self.names) + 2 * i:2 * n_ov * len(self.names) + 2 * i + 2]
+                res[name]['edit'] = float(total / n_valid) if n_valid > 0 else float('nan')
         return res

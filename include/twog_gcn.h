@@ -950,6 +950,19 @@ int twog_mtl_weight_bwd(const twog_mtl_t* spec, const float* losses, const float
  * twog_segment_f1_accumulate: one workgroup; f1_sums[k] += sum_s f1[s][k] and valid_sums[k] += sum_s valid[s] (device
  *   fp64, k < n_overlaps), in a fixed order.
  * twog_segment_f1_limits: the longest sequence the LDS layout of twog_segment_f1 holds, and its largest n_overlaps.
+ * twog_segment_edit: the segmental edit score, one workgroup per sequence, labels read in place in the two layouts of
+ *   twog_segment_f1 (int64, compared as int64). Per sequence: steps with y_true == ignore_value are dropped from both
+ *   sequences (use_ignore) BEFORE the run-length encoding, so two runs of one label that an ignored stretch separated are
+ *   one segment; with use_bg the segments labelled bg_label are then removed from both segment lists WITHOUT merging the
+ *   neighbours this brings together (A bg A gives [A, A]); distance int32 [n_seq] is the Levenshtein distance between the
+ *   two lists of n_true = m and n_pred = n segment labels (unit insertion, deletion and substitution), and score fp64
+ *   [n_seq] = (1.0 - (double)distance / (double)max(m, n)) * 100.0, each of the three operations rounded once. valid
+ *   int32 [n_seq] is 0, and the other four outputs are zero, for a sequence with no kept step or with max(m, n) == 0; the
+ *   batch metric is sum(score) / sum(valid) (twog_segment_f1_accumulate with n_overlaps == 1 adds both). Integer
+ *   arithmetic in LDS only, no atomics: bit-identical from run to run. Returns -1 for a negative size or n_seq not a
+ *   multiple of entities; -2 for n_steps > max_steps; 0 without a launch for n_seq == 0. n_steps == 0 writes the
+ *   all-zero rows, as twog_segment_f1 does.
+ * twog_segment_edit_limits: the longest sequence twog_segment_edit takes: the max_steps of twog_segment_f1_limits.
  * =============================================================================================================== */
 int twog_predict_labels(const float* logp, int bs, int n_classes, int T, int E, int downsampling, int T_out,
                         int64_t* labels, void* stream);
@@ -967,6 +980,10 @@ int twog_segment_f1(const int64_t* y_true, const int64_t* y_pred, int n_seq, int
 int twog_segment_f1_accumulate(const double* f1, const int32_t* valid, int n_seq, int n_overlaps, double* f1_sums,
                                double* valid_sums, void* stream);
 int twog_segment_f1_limits(int* max_steps, int* max_overlaps);
+int twog_segment_edit(const int64_t* y_true, const int64_t* y_pred, int n_seq, int n_steps, int entities,
+                      int64_t ignore_value, int use_ignore, int64_t bg_label, int use_bg, double* score, int32_t* distance,
+                      int32_t* n_true, int32_t* n_pred, int32_t* valid, void* stream);
+int twog_segment_edit_limits(int* max_steps);
 
 #ifdef __cplusplus
 }
