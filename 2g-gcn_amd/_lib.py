@@ -127,6 +127,12 @@ class Loss(C.Structure):  # twog_loss_t
                 ('ignore_value', C.c_float)]
 
 
+class SmoothLoss(C.Structure):  # twog_smooth_loss_t
+    _fields_ = [('n_classes', C.c_int32), ('pad0_', C.c_int32), ('outer', C.c_int64), ('steps', C.c_int64),
+                ('entities', C.c_int64), ('input', C.c_void_p), ('target', C.c_void_p), ('dinput', C.c_void_p),
+                ('weight', C.c_float), ('tau', C.c_float), ('ignore_value', C.c_float), ('accumulate', C.c_int32)]
+
+
 class Relation(C.Structure):  # twog_relation_t
     _fields_ = [('q', Rows), ('k', Rows), ('msg', Rows), ('p_r', Rows), ('p_s', Rows), ('out', Rows),
                 ('a_r', C.c_void_p), ('c_s', C.c_void_p), ('dist', C.c_void_p), ('dist_ld_inst', C.c_int64),
@@ -289,6 +295,8 @@ SIGNATURES = {
     'twog_stream_grid': [_I, _L, _L],
     'twog_multitask_loss_fwd': [C.POINTER(Loss), _I, _P, _P, _P, _P],
     'twog_multitask_loss_bwd': [C.POINTER(Loss), _I, _P, _P, _P],
+    'twog_smooth_loss_fwd': [C.POINTER(SmoothLoss), _I, _P, _P, _P, _P],
+    'twog_smooth_loss_bwd': [C.POINTER(SmoothLoss), _I, _P, _P, _P],
     'twog_grad_norm': [_P, C.POINTER(Ranges), _F, _F, _P, _P, _P],
     'twog_adam_step_coef': [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P, _P],
     'twog_mtl_weight_fwd': [C.POINTER(Mtl), _P, _P, _P, _P],

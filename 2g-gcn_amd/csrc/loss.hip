@@ -6,6 +6,7 @@
 // (mask.sum().item()); here every term is a column of a (blocks, terms) grid: lane-contiguous reads, fp64 partial
 // sums reduced in a fixed order (bit-reproducible), the per-term {sum, count} kept on the device for the backward
 // launch, which writes d(input) of every term in one pass (for NLL: -w/count at the target class, 0 elsewhere).
+// Second half of the file: the temporal smoothing terms (truncated MSE between adjacent steps), one more launch per direction.
 #include "twog_common.h"
 
 namespace {
@@ -16,6 +17,21 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+
+// {sum, count} of a 256-thread block -> partials[term = blockIdx.y][block = blockIdx.x], in a fixed order
+__device__ __forceinline__ void block_partial(double sum, double cnt, double* partials) {
+    __shared__ double red[2][4];
+    sum = wave_sum_f64(sum);
+    cnt = wave_sum_f64(cnt);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) { red[0][w] = sum; red[1][w] = cnt; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double* p = partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
+        p[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        p[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    }
 }
 
 __global__ __launch_bounds__(256) void loss_partial_kernel(const Terms T, double* partials) {
@@ -40,17 +56,7 @@ __global__ __launch_bounds__(256) void loss_partial_kernel(const Terms T, double
             }
         }
     }
-    __shared__ double red[2][4];
-    sum = wave_sum_f64(sum);
-    cnt = wave_sum_f64(cnt);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { red[0][w] = sum; red[1][w] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double* p = partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
-        p[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        p[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    }
+    block_partial(sum, cnt, partials);
 }
 
 __global__ void loss_final_kernel(const Terms T, int n_terms, int n_blocks, const double* partials, double* stats,
@@ -109,7 +115,113 @@ inline bool terms_ok(const twog_loss_t* t, int n) {
     return true;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Temporal smoothing loss (truncated MSE between the log-probabilities of adjacent steps; the definition is at
+// twog_smooth_loss_t in include/twog_gcn.h). One thread per (o, t, e) along the contiguous t * E + e axis, a loop over
+// the classes: the predecessor is E floats back, mostly in the same cache lines.
+// The definition fixes every fp32 rounding (the difference, g, the product g * 2 D, the addition into the buffer), so from
+// here to the end of the file no multiplication is fused with an addition.
+#pragma clang fp contract(off)
+
+struct SmoothTerms { twog_smooth_loss_t t[TWOG_LOSS_MAX_TERMS]; };
+
+__device__ __forceinline__ bool smooth_step_kept(const twog_smooth_loss_t& L, int64_t y) {
+    return y != (int64_t)L.ignore_value && y >= 0 && y < L.n_classes;
+}
+
+__global__ __launch_bounds__(256) void smooth_partial_kernel(const SmoothTerms T, double* partials) {
+    const twog_smooth_loss_t& L = T.t[blockIdx.y];
+    const int64_t inner = L.steps * L.entities, n = L.outer * inner;
+    const double tau2 = (double)L.tau * (double)L.tau;
+    double sum = 0.0, cnt = 0.0;
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (int64_t)gridDim.x * 256) {
+        const int64_t o = p / inner, r = p - o * inner;
+        if (r < L.entities) continue;   // step 0 has no predecessor
+        if (!smooth_step_kept(L, L.target[p]) || !smooth_step_kept(L, L.target[p - L.entities])) continue;
+        const float* x = L.input + o * L.n_classes * inner + r;
+        for (int c = 0; c < L.n_classes; ++c) {
+            const float d = x[(int64_t)c * inner] - x[(int64_t)c * inner - L.entities];
+            sum += fmin((double)d * (double)d, tau2);
+        }
+        cnt += (double)L.n_classes;
+    }
+    block_partial(sum, cnt, partials);
+}
+
+__global__ void smooth_final_kernel(const SmoothTerms T, int n_terms, int n_blocks, const double* partials, double* stats,
+                                    float* losses) {
+    const int term = blockIdx.x * blockDim.x + threadIdx.x;
+    if (term >= n_terms) return;
+    double sum = 0.0, cnt = 0.0;
+    for (int b = 0; b < n_blocks; ++b) {
+        sum += partials[((int64_t)term * n_blocks + b) * 2];
+        cnt += partials[((int64_t)term * n_blocks + b) * 2 + 1];
+    }
+    stats[term * 2] = sum;
+    stats[term * 2 + 1] = cnt;
+    losses[term] = T.t[term].weight * (float)(cnt > 0.0 ? sum / cnt : 0.0);
+}
+
+__global__ __launch_bounds__(256) void smooth_bwd_kernel(const SmoothTerms T, const double* stats, const float* dlosses) {
+    const twog_smooth_loss_t& L = T.t[blockIdx.y];
+    if (!L.dinput) return;
+    const int64_t inner = L.steps * L.entities, n = L.outer * inner;
+    const double tau2 = (double)L.tau * (double)L.tau;
+    const double cnt = stats[blockIdx.y * 2 + 1];
+    const float g = cnt > 0.0 ? L.weight * dlosses[blockIdx.y] / (float)cnt : 0.f;
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (int64_t)gridDim.x * 256) {
+        const int64_t o = p / inner, r = p - o * inner;
+        const bool kept = r >= L.entities && smooth_step_kept(L, L.target[p]) &&
+                          smooth_step_kept(L, L.target[p - L.entities]);
+        if (!kept && L.accumulate) continue;
+        const float* x = L.input + o * L.n_classes * inner + r;
+        float* dx = L.dinput + o * L.n_classes * inner + r;
+        for (int c = 0; c < L.n_classes; ++c) {
+            float v = 0.f;
+            if (kept) {
+                const float d = x[(int64_t)c * inner] - x[(int64_t)c * inner - L.entities];
+                if ((double)d * (double)d <= tau2) v = g * (2.f * d);
+            }
+            if (!L.accumulate) dx[(int64_t)c * inner] = v;
+            else if (v != 0.f) dx[(int64_t)c * inner] += v;
+        }
+    }
+}
+
+inline bool smooth_terms_ok(const twog_smooth_loss_t* t, int n) {
+    if (n < 0 || n > TWOG_LOSS_MAX_TERMS) return false;
+    for (int i = 0; i < n; ++i)
+        if (!(t[i].tau > 0.f) || t[i].outer < 0 || t[i].steps < 0 || t[i].entities < 0 || t[i].n_classes < 1) return false;
+    return true;
+}
+
 }  // namespace
+
+extern "C" int twog_smooth_loss_fwd(const twog_smooth_loss_t* terms, int n_terms, double* partials, double* stats,
+                                    float* losses, void* stream) {
+    if (!smooth_terms_ok(terms, n_terms)) return -1;
+    if (n_terms == 0) return 0;
+    SmoothTerms T;
+    for (int i = 0; i < n_terms; ++i) T.t[i] = terms[i];
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(smooth_partial_kernel, dim3(TWOG_LOSS_BLOCKS, n_terms), dim3(256), 0, st, T, partials);
+    TWOG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(smooth_final_kernel, dim3(1), dim3(64), 0, st, T, n_terms, TWOG_LOSS_BLOCKS, partials, stats, losses);
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int twog_smooth_loss_bwd(const twog_smooth_loss_t* terms, int n_terms, const double* stats, const float* dlosses,
+                                    void* stream) {
+    if (!smooth_terms_ok(terms, n_terms)) return -1;
+    if (n_terms == 0) return 0;
+    SmoothTerms T;
+    for (int i = 0; i < n_terms; ++i) T.t[i] = terms[i];
+    hipLaunchKernelGGL(smooth_bwd_kernel, dim3(TWOG_LOSS_BLOCKS * 4, n_terms), dim3(256), 0, (hipStream_t)stream, T, stats,
+                       dlosses);
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" int twog_multitask_loss_fwd(const twog_loss_t* terms, int n_terms, double* partials, double* stats,
                                        float* losses, void* stream) {

@@ -170,7 +170,8 @@ class DataParallel:
         """sync_bn: the geometric-level BatchNorm uses the statistics of the GLOBAL batch (one all-reduce of 2*4N fp64
         sums per step). count_weighted_loss: every term of the criterion (losses.multi_task_loss) is
         normalised by the GLOBAL number of valid (non-ignored) targets instead of the rank's own (one all-reduce of the
-        6-12 per-term counts per step; 8e (b)) -- with ragged clips (-1 targets) the averaged rank gradients are then the
+        6-12 per-term counts per step, 8-16 with the temporal smoothing terms, whose pair counts ride in the same tensor;
+        8e (b)) -- with ragged clips (-1 targets) the averaged rank gradients are then the
         gradient of the global mean, not a mean of per-rank means. global_noise_seed: every rank draws the Gumbel noise of
         the global batch from a generator seeded with this value and keeps its shard (8e (c)); device_noise_seed gives the
         same equivalence without the W-fold host draw: the noise is drawn on the device (model.use_device_noise(seed)) as a

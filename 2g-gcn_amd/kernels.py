@@ -1397,13 +1397,15 @@ class HipKernels:
             a.weight, a.ignore_value = float(t['weight']), float(t['ignore'])
         return arr
 
-    def multitask_loss_fwd(self, terms):
-        """All loss terms in one launch. Returns (losses [n] fp32, stats [n][2] fp64 = sum, count)."""
+    def multitask_loss_fwd(self, terms, room=0):
+        """All loss terms in one launch. Returns (losses [n + room] fp32, stats [n + room][2] fp64 = sum, count): the first n
+        rows are written here, the `room` rows behind them are left to smooth_loss_fwd, so the criterion's losses stay ONE
+        tensor (multi_task._loss_tensor reads it in place) without a copy."""
         n, dev = len(terms), terms[0]['input'].device
         if n > L.LOSS_MAX_TERMS:
             raise ValueError(f'at most {L.LOSS_MAX_TERMS} loss terms per call')
-        losses = torch.empty(n, dtype=torch.float32, device=dev)
-        stats = torch.empty(n, 2, dtype=torch.float64, device=dev)
+        losses = torch.empty(n + room, dtype=torch.float32, device=dev)
+        stats = torch.empty(n + room, 2, dtype=torch.float64, device=dev)
         partials = self.workspace(n * L.LOSS_BLOCKS * 2 * 8, dev, 'loss')
         self._check(self.lib.twog_multitask_loss_fwd(self._loss_terms(terms), n, partials.data_ptr(), stats.data_ptr(),
                                                      losses.data_ptr(), self._stream()), 'twog_multitask_loss_fwd')
@@ -1416,6 +1418,47 @@ class HipKernels:
                                                      dlosses.contiguous().data_ptr(), self._stream()),
                     'twog_multitask_loss_bwd')
         return dins
+
+    def _smooth_terms(self, terms, dinputs=None, accumulate=None):
+        """terms: list of dict(input (outer, C, T, E) log-probabilities, target int64 (outer, T, E), weight, tau, ignore)."""
+        if len(terms) > L.LOSS_MAX_TERMS:
+            raise ValueError(f'at most {L.LOSS_MAX_TERMS} smoothing terms per call')
+        arr = (L.SmoothLoss * len(terms))()
+        for i, (t, a) in enumerate(zip(terms, arr)):
+            x, y = t['input'], t['target']
+            assert x.is_contiguous() and y.is_contiguous() and x.dtype == torch.float32 and y.dtype == torch.int64
+            assert x.dim() == 4 and y.shape == (x.shape[0], x.shape[2], x.shape[3]), (tuple(x.shape), tuple(y.shape))
+            a.outer, a.n_classes, a.steps, a.entities = x.shape
+            a.input, a.target = x.data_ptr(), y.data_ptr()
+            a.dinput = None
+            if dinputs is not None and dinputs[i] is not None:
+                d = dinputs[i]
+                assert d.is_contiguous() and d.dtype == torch.float32 and d.shape == x.shape and d.device == x.device
+                a.dinput, a.accumulate = d.data_ptr(), int(bool(accumulate[i]))
+            a.weight, a.tau, a.ignore_value = float(t['weight']), float(t['tau']), float(t['ignore'])
+        return arr
+
+    def smooth_loss_fwd(self, terms, losses_out, stats_out):
+        """The temporal smoothing terms (twog_smooth_loss_t) in one launch pair, written into the given views: losses_out
+        [m] fp32 and stats_out [m][2] fp64, the tail of the tensors multitask_loss_fwd(..., room=m) returned."""
+        m, dev = len(terms), terms[0]['input'].device
+        assert losses_out.shape == (m,) and losses_out.dtype == torch.float32 and losses_out.is_contiguous()
+        assert stats_out.shape == (m, 2) and stats_out.dtype == torch.float64 and stats_out.is_contiguous()
+        assert losses_out.device == dev and stats_out.device == dev
+        partials = self.workspace(m * L.LOSS_BLOCKS * 2 * 8, dev, 'smooth_loss')
+        self._check(self.lib.twog_smooth_loss_fwd(self._smooth_terms(terms), m, partials.data_ptr(), stats_out.data_ptr(),
+                                                  losses_out.data_ptr(), self._stream()), 'twog_smooth_loss_fwd')
+
+    def smooth_loss_bwd(self, terms, stats, dlosses, dins, accumulate):
+        """d(input) of every smoothing term with a buffer in dins (None: skipped), scaled by dlosses [m]: stored into dins[i]
+        (every element), or with accumulate[i] added where it is not zero. No two terms may share a buffer."""
+        m = len(terms)
+        assert stats.shape == (m, 2) and stats.dtype == torch.float64 and stats.is_contiguous()
+        assert dlosses.shape == (m,) and dlosses.dtype == torch.float32 and dlosses.is_contiguous()
+        ptrs = [d.data_ptr() for d in dins if d is not None]
+        assert len(set(ptrs)) == len(ptrs), 'two smoothing terms of one launch share a gradient buffer'
+        self._check(self.lib.twog_smooth_loss_bwd(self._smooth_terms(terms, dins, accumulate), m, stats.data_ptr(),
+                                                  dlosses.data_ptr(), self._stream()), 'twog_smooth_loss_bwd')
 
 
     # ---------------------------------------------------------------- inference post-processing

@@ -6,6 +6,11 @@ values (a list of weighted scalar losses, one per output of the model), so `trai
 `criterion(output, target)` / `sum(losses).backward()`. All terms run in ONE forward and ONE backward kernel launch
 (`twog_multitask_loss_fwd/bwd`), with no host synchronisation (the reference calls `mask.sum().item()` per term).
 Terms whose weight is 0 (stage-1: budget, BCE and the frame-level NLL terms) get no backward work at all.
+
+Beyond the reference: the temporal smoothing loss (`temporal_smoothing_loss`, `multi_task_loss(..., smoothing=...)`,
+`misc.smoothing_loss` of `select_loss`), MS-TCN's truncated MSE between the log-probabilities of adjacent steps -- the
+training-side companion of the segmental metrics. Its terms follow the reference's in the same loss tensor, written by
+ONE more launch per direction (`twog_smooth_loss_fwd/bwd`; definition in include/twog_gcn.h); off by default.
 """
 from functools import partial
 
@@ -14,7 +19,15 @@ import torch.nn.functional as F
 
 from .kernels import get_kernels
 
-_NLL, _BCE, _BUDGET = 0, 1, 2
+_NLL, _BCE, _BUDGET = 0, 1, 2   # twog_loss_t::kind
+
+
+def _misc(cfg):
+    """cfg's `misc` section: an OmegaConf-style `.get('misc', default_value={})` or a plain dict."""
+    try:
+        return cfg.get('misc', default_value={})
+    except TypeError:  # plain dict
+        return cfg.get('misc', {})
 
 
 def nll_loss(input, target, ignore_index=-1, reduction='mean'):
@@ -32,6 +45,14 @@ def binary_cross_entropy_loss(input, target, positive_class_weight=1, ignore_val
 def budget_loss(input, target, ignore_value=-1, reduction='mean'):
     """pyrutils/torch/losses.py:24-36."""
     return _run([input], [target], [_BUDGET], [1.0], ignore_value, 'mean')[0]
+
+
+def temporal_smoothing_loss(input, target, tau=4.0, ignore_index=-1):
+    """Truncated MSE between the log-probabilities of adjacent steps (T-MSE of MS-TCN): input (bs, C, T, E) log-probabilities,
+    target (bs, T, E) labels; the mean over the pairs of adjacent kept steps and the classes of min((x_t - x_{t-1})^2, tau^2)
+    with x_{t-1} held constant; 0 when no pair is kept. (The input rides on an NLL term of weight 0, whose value is dropped
+    and which gets no backward work.)"""
+    return _run([input], [target], [_NLL], [0.0], ignore_index, 'mean', [(0, 1.0, tau)])[1]
 
 
 _KIND = {nll_loss: _NLL, F.nll_loss: _NLL, binary_cross_entropy_loss: _BCE, budget_loss: _BUDGET}
@@ -75,14 +96,22 @@ def get_count_reducer():
 class _MultiTaskLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec, *inputs):
-        kinds, targets, weights, ignore, reducer = spec
+        kinds, targets, weights, ignore, reducer, smoothing = spec
         K = get_kernels()
         terms = []
         for x, y, k, w in zip(inputs, targets, kinds, weights):
             x = x.detach().contiguous()
             y = (y.to(torch.int64) if k == _NLL else y.to(torch.float32)).contiguous()
             terms.append(dict(kind=k, input=x, target=y, weight=w, ignore=ignore))
-        losses, stats = K.multitask_loss_fwd(terms)
+        smooth = [dict(input=terms[i]['input'], target=terms[i]['target'], weight=w, tau=tau, ignore=ignore)
+                  for i, w, tau in smoothing]
+        if smooth:
+            # the smoothing terms follow the n zipped ones in the same tensors: one more launch writes the tail in place
+            n = len(terms)
+            losses, stats = K.multitask_loss_fwd(terms, room=len(smooth))
+            K.smooth_loss_fwd(smooth, losses[n:], stats[n:])
+        else:
+            losses, stats = K.multitask_loss_fwd(terms)
         if reducer is not None:
             # six to twelve scalars: sum_rank / (count_global / W) per term, 0 / 0 -> NaN for NLL like torch's mean over an
             # empty selection, 0 for the BCE / budget terms (pyrutils/torch/losses.py:15-16, :32-33). Same arithmetic as
@@ -90,35 +119,64 @@ class _MultiTaskLoss(torch.autograd.Function):
             # -- with a reducer that returns the counts unchanged (one rank) the losses are bit-identical to the plain path.
             eff = reducer(stats[:, 1].clone())
             val = stats[:, 0] / eff
-            soft = torch.tensor([k != _NLL for k in kinds], device=val.device)
+            soft = torch.tensor([k != _NLL for k in kinds] + [True] * len(smooth), device=val.device)
             val = torch.where(soft & (eff <= 0), torch.zeros_like(val), val)
-            w = torch.tensor([float(x) for x in weights], dtype=torch.float32, device=val.device)
+            w = torch.tensor([float(x) for x in weights] + [t['weight'] for t in smooth], dtype=torch.float32,
+                             device=val.device)
             losses = w * val.to(torch.float32)
             stats = torch.stack([stats[:, 0], eff], 1).contiguous()
         ctx.terms, ctx.stats = terms, stats
+        ctx.smooth, ctx.smooth_index = smooth, [i for i, _, _ in smoothing]
         return losses
 
     @staticmethod
     def backward(ctx, dlosses):
         need = [ctx.needs_input_grad[i + 1] and t['weight'] != 0 for i, t in enumerate(ctx.terms)]
-        if not any(need):
+        need_smooth = [ctx.needs_input_grad[i + 1] and t['weight'] != 0 for i, t in zip(ctx.smooth_index, ctx.smooth)]
+        if not any(need) and not any(need_smooth):
             return (None,) + tuple(None for _ in ctx.terms)
-        dins = get_kernels().multitask_loss_bwd(ctx.terms, ctx.stats, dlosses, need)
+        K, n = get_kernels(), len(ctx.terms)
+        dins = K.multitask_loss_bwd(ctx.terms, ctx.stats, dlosses, need) if any(need) else [None] * n
+        if any(need_smooth):
+            # one gradient per input: the smoothing launch adds into the buffer the NLL launch just wrote on this stream, or
+            # stores into a buffer of its own where the NLL term of that input has no backward work
+            dins, sdins, acc = list(dins), [None] * len(ctx.smooth), [False] * len(ctx.smooth)
+            for j, (i, nd) in enumerate(zip(ctx.smooth_index, need_smooth)):
+                if nd:
+                    acc[j] = dins[i] is not None
+                    if not acc[j]:
+                        dins[i] = torch.empty_like(ctx.terms[i]['input'])
+                    sdins[j] = dins[i]
+            K.smooth_loss_bwd(ctx.smooth, ctx.stats[n:], dlosses.contiguous()[n:], sdins, acc)
         return (None,) + tuple(dins)
 
 
-def _run(inputs, targets, kinds, weights, ignore_value, reduction):
+def _run(inputs, targets, kinds, weights, ignore_value, reduction, smoothing=()):
     if reduction != 'mean':
         raise NotImplementedError("only reduction='mean' (the reference's setting) is implemented")
+    smoothing = [(int(i), float(w), float(tau)) for i, w, tau in smoothing]
+    for i, _, tau in smoothing:
+        if not 0 <= i < len(kinds) or kinds[i] != _NLL:
+            raise ValueError(f'smoothing term on input {i}: not one of the NLL terms of this call')
+        if not tau > 0:
+            raise ValueError(f'smoothing term on input {i}: tau must be positive, got {tau}')
+    if len({i for i, _, _ in smoothing}) != len(smoothing):
+        # (both would write the gradient buffer of that input in the same launch)
+        raise ValueError('more than one smoothing term on the same input')
     # the scope's reducer, and only while autograd records (read here: grad mode is off inside Function.forward)
     reducer = _count_reducer if torch.is_grad_enabled() else None
-    losses = _MultiTaskLoss.apply((list(kinds), list(targets), [float(w) for w in weights], ignore_value, reducer), *inputs)
+    losses = _MultiTaskLoss.apply((list(kinds), list(targets), [float(w) for w in weights], ignore_value, reducer,
+                                   smoothing), *inputs)
     return list(losses.unbind(0))
 
 
 def multi_task_loss(input: list, target: list, loss_functions: list, weight: list = None, ignore_value=-1,
-                    reduction: str = 'mean'):
-    """pyrutils/torch/losses.py:39-51: the list of weighted losses, one per (input, target, loss function)."""
+                    reduction: str = 'mean', smoothing: list = None):
+    """pyrutils/torch/losses.py:39-51: the list of weighted losses, one per (input, target, loss function).
+
+    smoothing: a list of (index, weight, tau); term j is weight * temporal_smoothing_loss(input[index], target[index], tau),
+    appended after the zipped terms in list order (input[index] must be an NLL term's (bs, C, T, E) log-probabilities). Each
+    input still receives ONE gradient: the smoothing terms take the inputs by index."""
     if weight is None:
         weight = [1.0] * len(input)
     n = min(len(input), len(target), len(loss_functions), len(weight))  # zip semantics
@@ -127,17 +185,14 @@ def multi_task_loss(input: list, target: list, loss_functions: list, weight: lis
         if fn not in _KIND:
             raise NotImplementedError(f'loss function {fn} is not part of the 2G-GCN criterion')
         kinds.append(_KIND[fn])
-    return _run(list(input[:n]), list(target[:n]), kinds, list(weight[:n]), ignore_value, reduction)
+    return _run(list(input[:n]), list(target[:n]), kinds, list(weight[:n]), ignore_value, reduction, smoothing or ())
 
 
 def select_loss(model_name: str, model_input_type: str, dataset_name: str, cfg):
     """vhoi/losses.py:8-70 for model '2G-GCN': (criterion, loss_names). cfg needs `.get('misc', default_value={})`."""
     if model_name != '2G-GCN':
         raise NotImplementedError(f'{model_name}: only the 2G-GCN hot path is built (SURVEY section 8)')
-    try:
-        misc = cfg.get('misc', default_value={})
-    except TypeError:  # plain dict
-        misc = cfg.get('misc', {})
+    misc = _misc(cfg)
     hb_weight = ob_weight = 0.0
     if misc.get('budget_loss', {}).get('add', False):
         hb_weight = misc.get('budget_loss', {}).get('human_weight', 1.0)
@@ -164,18 +219,36 @@ def select_loss(model_name: str, model_input_type: str, dataset_name: str, cfg):
         weight += [fl_weight] * 2 + [weight_val, ant_weight]
         fns = (budget_loss, binary_cross_entropy_loss) + (nll_loss,) * 4
         names = ['B_HS', 'BCE_HS', 'NLL_SAR_F', 'NLL_SAP_F', 'NLL_SAR', 'NLL_SAP']
-    return partial(multi_task_loss, loss_functions=fns, weight=weight), names
+    smooth = misc.get('smoothing_loss', {})
+    if not smooth.get('add', False):
+        return partial(multi_task_loss, loss_functions=fns, weight=weight), names
+    # one smoothing term per final-level NLL term (the last 2 or 4 of the list; not the frame-level _F ones), weighted
+    # relative to it: the stage-1 pretraining zeros and the anticipation weight carry over
+    first = len(fns) - (4 if cad else 2)
+    s_weight, tau = smooth.get('weight', 0.15), smooth.get('tau', 4.0)
+    smoothing = [(i, s_weight * weight[i], tau) for i in range(first, len(fns))]
+    names = names + ['TMSE_' + names[i][len('NLL_'):] for i in range(first, len(fns))]
+    return partial(multi_task_loss, loss_functions=fns, weight=weight, smoothing=smoothing), names
+
+
+def _n_smoothing_terms(dataset_name, cfg):
+    """The smoothing terms select_loss appends for this configuration (misc.smoothing_loss.add)."""
+    if not _misc(cfg).get('smoothing_loss', {}).get('add', False):
+        return 0
+    return 4 if dataset_name == 'cad120' else 2
 
 
 def select_loss_types(model_name: str, dataset_name: str, cfg):
     """vhoi/losses.py:72-80."""
     if model_name != '2G-GCN':
         raise ValueError(f'Multi-task learning option not implemented for {model_name}')
-    return ['budget'] * 2 + ['bce'] * 2 + ['softmax'] * 8 if dataset_name == 'cad120' else ['budget', 'bce'] + ['softmax'] * 4
+    types = ['budget'] * 2 + ['bce'] * 2 + ['softmax'] * 8 if dataset_name == 'cad120' else ['budget', 'bce'] + ['softmax'] * 4
+    return types + ['mse'] * _n_smoothing_terms(dataset_name, cfg)
 
 
 def select_loss_learning_mask(model_name: str, dataset_name: str, cfg):
     """vhoi/losses.py:83-91."""
     if model_name != '2G-GCN':
         raise ValueError(f'Multi-task learning option not implemented for {model_name}')
-    return [False] * 4 + [True] * 8 if dataset_name == 'cad120' else [False] * 2 + [True] * 4
+    mask = [False] * 4 + [True] * 8 if dataset_name == 'cad120' else [False] * 2 + [True] * 4
+    return mask + [False] * _n_smoothing_terms(dataset_name, cfg)

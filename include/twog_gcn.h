@@ -870,6 +870,49 @@ int twog_multitask_loss_bwd(const twog_loss_t* terms, int n_terms, const double*
                             void* stream);
 
 /* ===============================================================================================================
+ * Temporal smoothing loss: the truncated mean-squared error between the log-probabilities of adjacent steps (T-MSE,
+ * Farha & Gall, MS-TCN, CVPR 2019), the training-side companion of the segmental metrics (F1@k, edit score): it acts on
+ * predictions that flicker between labels for a few steps. Not part of the reference; csrc/loss.hip.
+ * Per term:
+ *   input x    fp32 log-probabilities [outer][C][T][E] (steps are E elements apart, classes T*E), outputs of a log-softmax
+ *   target y   int64 [outer][T][E];  tau > 0 (MS-TCN: 4);  w the weight;  ignore the ignored target value
+ *   a step is kept under the NLL term's rule: y != ignore && 0 <= y < C;
+ *   a pair (o, t, e), t >= 1, is kept when steps t and t-1 of (o, e) are both kept;
+ *   D = x[o][c][t][e] - x[o][c][t-1][e] in fp32 (one rounding);  v = min((double)D * (double)D, (double)tau * (double)tau)
+ *   sum   = sum of v over the kept pairs and all C classes, added in fp64 in a fixed order (TWOG_LOSS_BLOCKS partial sums
+ *           per term, then one sequential pass);  count = (kept pairs) * C
+ *   stats = {sum, count};  loss = w * (float)(sum / count), 0 when count == 0 (a clip of one step, or every target ignored,
+ *           has nothing to smooth: 0 like the BCE and budget terms, not NaN)
+ *   the predecessor is a constant (MS-TCN's .detach()): only step t of a pair receives a gradient. With
+ *   g = w * dloss / (float)count in fp32 (0 when count == 0):
+ *     d x[o][c][t][e] = fl(g * (2 D))  where the pair is kept and D*D <= tau*tau (boundary included, as torch.clamp), else 0.
+ *   The product is rounded to fp32 before it is stored or added (no fused multiply-add into the buffer), so both store
+ *   modes are reproducible bit for bit. NaN / infinite inputs: whatever IEEE arithmetic gives; not specified.
+ * twog_smooth_loss_fwd: up to TWOG_LOSS_MAX_TERMS terms in one launch pair, a (TWOG_LOSS_BLOCKS, terms) grid; partials is a
+ *   workspace of n_terms * TWOG_LOSS_BLOCKS * 2 doubles; stats [n_terms][2] and losses [n_terms] are plain pointers (the
+ *   tail of the criterion's own tensors). twog_smooth_loss_bwd: one launch; per term, accumulate == 0 stores every element
+ *   of dinput (zeros included), accumulate != 0 adds the non-zero contributions into dinput and leaves every other element
+ *   untouched (the buffer an earlier launch on the same stream filled); a NULL dinput skips the term. No two terms of one
+ *   call may share a dinput. Both return -1 on a malformed term (tau <= 0, a negative size, n_classes < 1).
+ * =============================================================================================================== */
+typedef struct {
+    int32_t n_classes;
+    int32_t pad0_;
+    int64_t outer, steps, entities;
+    const float* input;
+    const int64_t* target;
+    float* dinput;
+    float weight;
+    float tau;
+    float ignore_value;
+    int32_t accumulate;
+} twog_smooth_loss_t;
+int twog_smooth_loss_fwd(const twog_smooth_loss_t* terms, int n_terms, double* partials, double* stats, float* losses,
+                         void* stream);
+int twog_smooth_loss_bwd(const twog_smooth_loss_t* terms, int n_terms, const double* stats, const float* dlosses,
+                         void* stream);
+
+/* ===============================================================================================================
  * Training-step options of the reference's trainer on the fused step (pyrutils/torch/train_utils.py:149-153,
  * train.py:42-46; csrc/train_opts.hip).
  *
