@@ -127,6 +127,10 @@ class Loss(C.Structure):  # twog_loss_t
                 ('ignore_value', C.c_float)]
 
 
+class WLoss(C.Structure):  # twog_wloss_t
+    _fields_ = Loss._fields_ + [('class_weight', C.c_void_p), ('positive_class_weight', C.c_float), ('pad0_', C.c_int32)]
+
+
 class SmoothLoss(C.Structure):  # twog_smooth_loss_t
     _fields_ = [('n_classes', C.c_int32), ('pad0_', C.c_int32), ('outer', C.c_int64), ('steps', C.c_int64),
                 ('entities', C.c_int64), ('input', C.c_void_p), ('target', C.c_void_p), ('dinput', C.c_void_p),
@@ -297,6 +301,8 @@ SIGNATURES = {
     'twog_multitask_loss_bwd': [C.POINTER(Loss), _I, _P, _P, _P],
     'twog_smooth_loss_fwd': [C.POINTER(SmoothLoss), _I, _P, _P, _P, _P],
     'twog_smooth_loss_bwd': [C.POINTER(SmoothLoss), _I, _P, _P, _P],
+    'twog_weighted_loss_fwd': [C.POINTER(WLoss), _I, _P, _P, _P, _P],
+    'twog_weighted_loss_bwd': [C.POINTER(WLoss), _I, _P, _P, _P],
     'twog_grad_norm': [_P, C.POINTER(Ranges), _F, _F, _P, _P, _P],
     'twog_adam_step_coef': [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P, _P],
     'twog_mtl_weight_fwd': [C.POINTER(Mtl), _P, _P, _P, _P],
@@ -305,6 +311,7 @@ SIGNATURES = {
     'twog_f1_at_k': [_P, _P, _I, _I, _I, C.c_double, _L, _I, _P, _P, _P, _P],
     'twog_eval_update': [_P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P],
     'twog_confusion_counts': [_P, _P, _L, _I, _P, _P, _P],
+    'twog_class_counts': [_P, _L, _I, _L, _P, _P],
     'twog_eval_limits': [C.POINTER(C.c_int), C.POINTER(C.c_int)],
     'twog_segment_f1': [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_double), _I, _L, _I, _P, _P, _P, _P, _P, _P],
     'twog_segment_f1_accumulate': [_P, _P, _I, _I, _P, _P, _P],

@@ -6,7 +6,8 @@
 // (mask.sum().item()); here every term is a column of a (blocks, terms) grid: lane-contiguous reads, fp64 partial
 // sums reduced in a fixed order (bit-reproducible), the per-term {sum, count} kept on the device for the backward
 // launch, which writes d(input) of every term in one pass (for NLL: -w/count at the target class, 0 elsewhere).
-// Second half of the file: the temporal smoothing terms (truncated MSE between adjacent steps), one more launch per direction.
+// Second half of the file: the temporal smoothing terms (truncated MSE between adjacent steps), one more launch per direction;
+// then the same criterion with class weights (NLL) and the positive-class weight (BCE), twog_weighted_loss_fwd / _bwd.
 #include "twog_common.h"
 
 namespace {
@@ -195,7 +196,133 @@ inline bool smooth_terms_ok(const twog_smooth_loss_t* t, int n) {
     return true;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The criterion with class weights (NLL) and the positive-class weight (BCE): twog_wloss_t in include/twog_gcn.h states
+// every operation. The kernels above are left as they are (their multiply-adds may be fused; these are not), so the
+// per-element arithmetic is written out again here; the launch shape and the block reduction are shared. With cw == 1 and
+// p <= 1 every partial sum below is the one loss_partial_kernel forms: sum + 1.0 * (-x) == sum - x.
+struct WTerms { twog_wloss_t t[TWOG_LOSS_MAX_TERMS]; };
+
+__device__ __forceinline__ bool wloss_positive(const twog_wloss_t& L, float t) {
+    return t == 1.0f && L.positive_class_weight > 1.f;
+}
+
+__global__ __launch_bounds__(256) void wloss_partial_kernel(const WTerms T, double* partials) {
+    const twog_wloss_t& L = T.t[blockIdx.y];
+    const int64_t n = L.outer * L.inner;
+    double sum = 0.0, den = 0.0;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        if (L.kind == 0) {
+            const int64_t tgt = reinterpret_cast<const int64_t*>(L.target)[e];
+            if (tgt != (int64_t)L.ignore_value && tgt >= 0 && tgt < L.n_classes) {
+                const int64_t o = e / L.inner, i = e - o * L.inner;
+                const double cw = L.class_weight ? (double)L.class_weight[tgt] : 1.0;
+                sum += cw * (double)(-L.input[(o * L.n_classes + tgt) * L.inner + i]);
+                den += cw;
+            }
+        } else {
+            const float t = reinterpret_cast<const float*>(L.target)[e];
+            if (t != L.ignore_value) {
+                const float x = L.input[e];
+                float v;
+                if (L.kind == 2) v = x;
+                else if (wloss_positive(L, t)) v = -fmaxf(L.positive_class_weight * logf(x), -100.f);
+                else v = -(t * fmaxf(logf(x), -100.f) + (1.f - t) * fmaxf(logf(1.f - x), -100.f));
+                sum += (double)v;
+                den += 1.0;
+            }
+        }
+    }
+    block_partial(sum, den, partials);
+}
+
+__global__ void wloss_final_kernel(const WTerms T, int n_terms, int n_blocks, const double* partials, double* stats,
+                                   float* losses) {
+    const int term = blockIdx.x * blockDim.x + threadIdx.x;
+    if (term >= n_terms) return;
+    double sum = 0.0, den = 0.0;
+    for (int b = 0; b < n_blocks; ++b) {
+        sum += partials[((int64_t)term * n_blocks + b) * 2];
+        den += partials[((int64_t)term * n_blocks + b) * 2 + 1];
+    }
+    stats[term * 2] = sum;
+    stats[term * 2 + 1] = den;
+    const twog_wloss_t& L = T.t[term];
+    double v;
+    if (L.kind == 0) v = sum / den;  // 0 / 0 -> NaN, as F.nll_loss(weight=) with no kept weight
+    else v = den > 0.0 ? sum / den : 0.0;
+    losses[term] = L.weight * (float)v;
+}
+
+__global__ __launch_bounds__(256) void wloss_bwd_kernel(const WTerms T, const double* stats, const float* dlosses) {
+    const twog_wloss_t& L = T.t[blockIdx.y];
+    if (!L.dinput) return;
+    const int64_t n = L.outer * L.inner;
+    const double den = stats[blockIdx.y * 2 + 1];
+    const float g = den > 0.0 ? L.weight * dlosses[blockIdx.y] / (float)den : 0.f;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        if (L.kind == 0) {
+            const int64_t tgt = reinterpret_cast<const int64_t*>(L.target)[e];
+            const bool valid = tgt != (int64_t)L.ignore_value && tgt >= 0 && tgt < L.n_classes;
+            const int64_t o = e / L.inner, i = e - o * L.inner;
+            float v = 0.f;
+            if (valid) v = L.class_weight ? -(g * L.class_weight[tgt]) : -g;
+            float* d = L.dinput + o * L.n_classes * L.inner + i;
+            for (int c = 0; c < L.n_classes; ++c) d[(int64_t)c * L.inner] = (valid && c == tgt) ? v : 0.f;
+        } else {
+            const float t = reinterpret_cast<const float*>(L.target)[e];
+            float d = 0.f;
+            if (t != L.ignore_value) {
+                if (L.kind == 1) {
+                    const float x = L.input[e];
+                    d = g * (x - t) / fmaxf((1.f - x) * x, 1e-12f);  // torch's binary_cross_entropy backward
+                    if (wloss_positive(L, t)) d = d * L.positive_class_weight;
+                } else {
+                    d = g;
+                }
+            }
+            L.dinput[e] = d;
+        }
+    }
+}
+
+inline bool wterms_ok(const twog_wloss_t* t, int n) {
+    if (n < 0 || n > TWOG_LOSS_MAX_TERMS) return false;
+    for (int i = 0; i < n; ++i) {
+        if (t[i].kind < 0 || t[i].kind > 2 || t[i].outer < 0 || t[i].inner < 0) return false;
+        if (t[i].kind == 0 && t[i].n_classes < 1) return false;
+        if (!(t[i].positive_class_weight >= 0.f) || !(t[i].positive_class_weight <= 3.402823466e38f)) return false;
+    }
+    return true;
+}
+
 }  // namespace
+
+extern "C" int twog_weighted_loss_fwd(const twog_wloss_t* terms, int n_terms, double* partials, double* stats,
+                                      float* losses, void* stream) {
+    if (!wterms_ok(terms, n_terms)) return -1;
+    if (n_terms == 0) return 0;
+    WTerms T;
+    for (int i = 0; i < n_terms; ++i) T.t[i] = terms[i];
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(wloss_partial_kernel, dim3(TWOG_LOSS_BLOCKS, n_terms), dim3(256), 0, st, T, partials);
+    TWOG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(wloss_final_kernel, dim3(1), dim3(64), 0, st, T, n_terms, TWOG_LOSS_BLOCKS, partials, stats, losses);
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int twog_weighted_loss_bwd(const twog_wloss_t* terms, int n_terms, const double* stats, const float* dlosses,
+                                      void* stream) {
+    if (!wterms_ok(terms, n_terms)) return -1;
+    if (n_terms == 0) return 0;
+    WTerms T;
+    for (int i = 0; i < n_terms; ++i) T.t[i] = terms[i];
+    hipLaunchKernelGGL(wloss_bwd_kernel, dim3(TWOG_LOSS_BLOCKS * 4, n_terms), dim3(256), 0, (hipStream_t)stream, T, stats,
+                       dlosses);
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" int twog_smooth_loss_fwd(const twog_smooth_loss_t* terms, int n_terms, double* partials, double* stats,
                                     float* losses, void* stream) {

@@ -100,6 +100,24 @@ __global__ __launch_bounds__(256) void confusion_counts_kernel(const long long* 
     flush_hist(hist, C, counts, flags);
 }
 
+// Class counts of a label tensor under the NLL term's rule (label != ignore && 0 <= label < C), for losses.class_counts:
+// hist[C] 32-bit counters per workgroup (a workgroup sees far fewer than 2^32 positions), flushed like the cells above.
+__global__ __launch_bounds__(256) void class_counts_kernel(const long long* targets, int64_t n, int C, long long ignore,
+                                                           long long* counts) {
+    extern __shared__ unsigned hist[];
+    for (int k = threadIdx.x; k < C; k += 256) hist[k] = 0u;
+    __syncthreads();
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const long long y = targets[i];
+        if (y != ignore && y >= 0 && y < C) atomicAdd(&hist[(int)y], 1u);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < C; k += 256) {
+        const unsigned v = hist[k];
+        if (v != 0u) atomicAdd(reinterpret_cast<unsigned long long*>(counts + k), (unsigned long long)v);
+    }
+}
+
 inline int eval_grid(int64_t n) { return (int)((n + 255) / 256 < EVAL_GRID_CAP ? (n + 255) / 256 : EVAL_GRID_CAP); }
 
 // One thread per sequence. Steps whose target equals the ignore value are dropped from BOTH sequences before the
@@ -571,6 +589,18 @@ extern "C" int twog_confusion_counts(const int64_t* y_true, const int64_t* y_pre
     hipLaunchKernelGGL(confusion_counts_kernel, dim3(eval_grid(n)), dim3(256), lds, (hipStream_t)stream,
                        reinterpret_cast<const long long*>(y_true), reinterpret_cast<const long long*>(y_pred), n,
                        n_classes, reinterpret_cast<long long*>(counts), reinterpret_cast<long long*>(flags));
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int twog_class_counts(const int64_t* targets, int64_t n, int n_classes, int64_t ignore_index, int64_t* counts,
+                                 void* stream) {
+    if (n < 0 || n_classes < 1) return -1;
+    if (n_classes > TWOG_CLASS_COUNTS_MAX) return -2;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(class_counts_kernel, dim3(eval_grid(n)), dim3(256), (size_t)n_classes * sizeof(unsigned),
+                       (hipStream_t)stream, reinterpret_cast<const long long*>(targets), n, n_classes,
+                       (long long)ignore_index, reinterpret_cast<long long*>(counts));
     TWOG_CHECK_LAUNCH();
     return 0;
 }

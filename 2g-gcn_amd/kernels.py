@@ -1378,10 +1378,21 @@ class HipKernels:
 
 
     # ---------------------------------------------------------------- multi-task loss
-    def _loss_terms(self, terms, dinputs=None):
-        """terms: list of dict(kind 0 NLL / 1 BCE / 2 budget, input, target, weight, ignore). input/target contiguous."""
-        arr = (L.Loss * len(terms))()
+    def _loss_terms(self, terms, dinputs=None, struct=L.Loss):
+        """terms: list of dict(kind 0 NLL / 1 BCE / 2 budget, input, target, weight, ignore). input/target contiguous.
+        struct=L.WLoss reads two more keys: class_weight (contiguous fp32 [n_classes] on the input's device, or None; NLL
+        terms only) and positive_class_weight (a number; BCE terms only)."""
+        arr = (struct * len(terms))()
         for i, (t, a) in enumerate(zip(terms, arr)):
+            if struct is L.WLoss:
+                cw, p = t.get('class_weight'), float(t.get('positive_class_weight', 1.0))
+                assert cw is None or t['kind'] == 0, 'class_weight on a term that is not NLL'
+                assert p == 1.0 or t['kind'] == 1, 'positive_class_weight on a term that is not BCE'
+                if cw is not None:
+                    x = t['input']
+                    assert cw.dtype == torch.float32 and cw.is_contiguous() and cw.device == x.device
+                    assert cw.dim() == 1 and cw.numel() == x.shape[1], (tuple(cw.shape), tuple(x.shape))
+                a.class_weight, a.positive_class_weight = _ptr(cw), p
             x, y = t['input'], t['target']
             assert x.is_contiguous() and y.is_contiguous() and x.dtype == torch.float32
             a.kind = t['kind']
@@ -1417,6 +1428,28 @@ class HipKernels:
         self._check(self.lib.twog_multitask_loss_bwd(self._loss_terms(terms, dins), len(terms), stats.data_ptr(),
                                                      dlosses.contiguous().data_ptr(), self._stream()),
                     'twog_multitask_loss_bwd')
+        return dins
+
+    def weighted_loss_fwd(self, terms, room=0):
+        """multitask_loss_fwd for terms that may carry `class_weight` (NLL) and `positive_class_weight` (BCE), through
+        twog_weighted_loss_fwd: same returns, stats = (sum, den) with den the sum of the kept class weights of an NLL term."""
+        n, dev = len(terms), terms[0]['input'].device
+        if n > L.LOSS_MAX_TERMS:
+            raise ValueError(f'at most {L.LOSS_MAX_TERMS} loss terms per call')
+        losses = torch.empty(n + room, dtype=torch.float32, device=dev)
+        stats = torch.empty(n + room, 2, dtype=torch.float64, device=dev)
+        partials = self.workspace(n * L.LOSS_BLOCKS * 2 * 8, dev, 'loss')
+        self._check(self.lib.twog_weighted_loss_fwd(self._loss_terms(terms, struct=L.WLoss), n, partials.data_ptr(),
+                                                    stats.data_ptr(), losses.data_ptr(), self._stream()),
+                    'twog_weighted_loss_fwd')
+        return losses, stats
+
+    def weighted_loss_bwd(self, terms, stats, dlosses, need):
+        """multitask_loss_bwd for the terms of weighted_loss_fwd."""
+        dins = [torch.empty_like(t['input']) if nd else None for t, nd in zip(terms, need)]
+        self._check(self.lib.twog_weighted_loss_bwd(self._loss_terms(terms, dins, struct=L.WLoss), len(terms),
+                                                    stats.data_ptr(), dlosses.contiguous().data_ptr(), self._stream()),
+                    'twog_weighted_loss_bwd')
         return dins
 
     def _smooth_terms(self, terms, dinputs=None, accumulate=None):
@@ -1528,6 +1561,16 @@ class HipKernels:
         self._check(self.lib.twog_confusion_counts(y_true.data_ptr(), y_pred.data_ptr(), y_true.numel(), int(num_classes),
                                                    counts.data_ptr(), flags.data_ptr(), self._stream()),
                     'twog_confusion_counts')
+        return counts
+
+    def class_counts(self, targets, num_classes, ignore_index, counts):
+        """ADDS the number of labels of each class in an int64 tensor to counts int64 (C,), in place, under the NLL term's
+        rule: a label equal to ignore_index or outside [0, C) is skipped."""
+        assert targets.dtype == torch.int64 and targets.is_contiguous()
+        assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == num_classes
+        assert counts.device == targets.device
+        self._check(self.lib.twog_class_counts(targets.data_ptr(), targets.numel(), int(num_classes), int(ignore_index),
+                                               counts.data_ptr(), self._stream()), 'twog_class_counts')
         return counts
 
     def segment_f1_limits(self):

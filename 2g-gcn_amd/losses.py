@@ -11,6 +11,12 @@ Beyond the reference: the temporal smoothing loss (`temporal_smoothing_loss`, `m
 `misc.smoothing_loss` of `select_loss`), MS-TCN's truncated MSE between the log-probabilities of adjacent steps -- the
 training-side companion of the segmental metrics. Its terms follow the reference's in the same loss tensor, written by
 ONE more launch per direction (`twog_smooth_loss_fwd/bwd`; definition in include/twog_gcn.h); off by default.
+
+Against label imbalance: per-class weights on the NLL terms (`nll_loss(weight=)`, `multi_task_loss(class_weights=)`,
+`misc.class_weights`) and the reference's `positive_class_weight` of the BCE terms (`multi_task_loss(positive_class_weights=)`,
+`misc.segmentation_loss.positive_class_weight`). A call in which any term carries one runs ALL its terms through
+`twog_weighted_loss_fwd/bwd` (twog_wloss_t in include/twog_gcn.h), still one launch per direction; a call without them makes
+the launches it always made. `class_counts` (on the device) and `class_weights` ('balanced', 'effective') give the weights.
 """
 from functools import partial
 
@@ -30,16 +36,18 @@ def _misc(cfg):
         return cfg.get('misc', {})
 
 
-def nll_loss(input, target, ignore_index=-1, reduction='mean'):
-    """F.nll_loss(input, target, ignore_index, reduction='mean') on the HIP path."""
-    return _run([input], [target], [_NLL], [1.0], ignore_index, reduction)[0]
+def nll_loss(input, target, ignore_index=-1, reduction='mean', *, weight=None):
+    """F.nll_loss(input, target, weight, ignore_index=ignore_index, reduction='mean') on the HIP path. weight: per-class
+    weights, a [C] tensor or a sequence of floats: the weighted mean sum(w[y] * -x[y]) / sum(w[y]) over the kept targets."""
+    return _run([input], [target], [_NLL], [1.0], ignore_index, reduction, class_weights=[weight])[0]
 
 
 def binary_cross_entropy_loss(input, target, positive_class_weight=1, ignore_value=-1, reduction='mean'):
-    """pyrutils/torch/losses.py:7-21."""
-    if positive_class_weight != 1:
-        raise NotImplementedError('positive_class_weight != 1 is not used by any reference configuration')
-    return _run([input], [target], [_BCE], [1.0], ignore_value, reduction)[0]
+    """pyrutils/torch/losses.py:7-21. positive_class_weight p > 1 weighs the elements whose target is exactly 1.0 by p
+    (the reference raises their input to the power p; here p * log x, see twog_wloss_t in include/twog_gcn.h); p <= 1
+    changes nothing, as in the reference."""
+    return _run([input], [target], [_BCE], [1.0], ignore_value, reduction,
+                positive_class_weights=[positive_class_weight])[0]
 
 
 def budget_loss(input, target, ignore_value=-1, reduction='mean'):
@@ -96,27 +104,35 @@ def get_count_reducer():
 class _MultiTaskLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec, *inputs):
-        kinds, targets, weights, ignore, reducer, smoothing = spec
+        kinds, targets, weights, ignore, reducer, smoothing, options = spec
         K = get_kernels()
         terms = []
         for x, y, k, w in zip(inputs, targets, kinds, weights):
             x = x.detach().contiguous()
             y = (y.to(torch.int64) if k == _NLL else y.to(torch.float32)).contiguous()
             terms.append(dict(kind=k, input=x, target=y, weight=w, ignore=ignore))
+        # class weights / a positive-class weight on ANY term: all terms of the call go through twog_weighted_loss_*, still
+        # one launch per direction; none: the plain entry points, exactly as before (same launches, same bits)
+        ctx.weighted = options is not None
+        if ctx.weighted:
+            for t, cw, p in zip(terms, *options):
+                t['class_weight'], t['positive_class_weight'] = cw, p
+        fwd = K.weighted_loss_fwd if ctx.weighted else K.multitask_loss_fwd
         smooth = [dict(input=terms[i]['input'], target=terms[i]['target'], weight=w, tau=tau, ignore=ignore)
                   for i, w, tau in smoothing]
         if smooth:
             # the smoothing terms follow the n zipped ones in the same tensors: one more launch writes the tail in place
             n = len(terms)
-            losses, stats = K.multitask_loss_fwd(terms, room=len(smooth))
+            losses, stats = fwd(terms, room=len(smooth))
             K.smooth_loss_fwd(smooth, losses[n:], stats[n:])
         else:
-            losses, stats = K.multitask_loss_fwd(terms)
+            losses, stats = fwd(terms)
         if reducer is not None:
             # six to twelve scalars: sum_rank / (count_global / W) per term, 0 / 0 -> NaN for NLL like torch's mean over an
             # empty selection, 0 for the BCE / budget terms (pyrutils/torch/losses.py:15-16, :32-33). Same arithmetic as
             # loss_final_kernel (csrc/loss.hip): the fp64 quotient rounded to fp32, then the fp32 product with the weight
             # -- with a reducer that returns the counts unchanged (one rank) the losses are bit-identical to the plain path.
+            # With class weights the column handed over is den, the sum of the kept weights: the global WEIGHTED mean.
             eff = reducer(stats[:, 1].clone())
             val = stats[:, 0] / eff
             soft = torch.tensor([k != _NLL for k in kinds] + [True] * len(smooth), device=val.device)
@@ -136,7 +152,8 @@ class _MultiTaskLoss(torch.autograd.Function):
         if not any(need) and not any(need_smooth):
             return (None,) + tuple(None for _ in ctx.terms)
         K, n = get_kernels(), len(ctx.terms)
-        dins = K.multitask_loss_bwd(ctx.terms, ctx.stats, dlosses, need) if any(need) else [None] * n
+        bwd = K.weighted_loss_bwd if ctx.weighted else K.multitask_loss_bwd
+        dins = bwd(ctx.terms, ctx.stats, dlosses, need) if any(need) else [None] * n
         if any(need_smooth):
             # one gradient per input: the smoothing launch adds into the buffer the NLL launch just wrote on this stream, or
             # stores into a buffer of its own where the NLL term of that input has no backward work
@@ -151,9 +168,60 @@ class _MultiTaskLoss(torch.autograd.Function):
         return (None,) + tuple(dins)
 
 
-def _run(inputs, targets, kinds, weights, ignore_value, reduction, smoothing=()):
+_uploaded_weights = {}   # (values, device) -> fp32 tensor: a host sequence of class weights is uploaded once per device
+
+
+def _class_weight(cw, i, kind, x):
+    """Entry i of class_weights -> a contiguous fp32 [C] tensor on x's device, or None. A host sequence is checked and
+    uploaded once; a tensor is taken as it is and never read back (no host synchronisation)."""
+    if cw is None:
+        return None
+    if kind != _NLL:
+        raise ValueError(f'class weights on term {i}, which is not an NLL term')
+    C = x.shape[1] if x.dim() >= 2 else -1
+    if not torch.is_tensor(cw):
+        values = tuple(float(v) for v in cw)
+        if any(v < 0 or v != v or v in (float('inf'), float('-inf')) for v in values):
+            raise ValueError(f'class weights of term {i}: negative or non-finite value in {values}')
+        key = (values, x.device)
+        if key not in _uploaded_weights:
+            _uploaded_weights[key] = torch.tensor(values, dtype=torch.float32).to(x.device)
+        cw = _uploaded_weights[key]
+    if cw.dim() != 1 or cw.numel() != C:
+        raise ValueError(f'class weights of term {i}: shape {tuple(cw.shape)} for an input of {C} classes')
+    return cw.detach().to(device=x.device, dtype=torch.float32).contiguous()
+
+
+def _positive_weight(p, i, kind):
+    if p is None:
+        return 1.0
+    if kind != _BCE:
+        raise ValueError(f'positive-class weight on term {i}, which is not a BCE term')
+    p = float(p)
+    if p < 0 or p != p or p == float('inf'):
+        raise ValueError(f'positive-class weight of term {i}: {p} is negative or not finite')
+    return p
+
+
+def _options(inputs, kinds, class_weights, positive_class_weights):
+    """None when no term carries an option (the plain launches), else ([class weight tensor or None], [p]) per term."""
+    n = len(kinds)
+    cws = list(class_weights) if class_weights is not None else [None] * n
+    pws = list(positive_class_weights) if positive_class_weights is not None else [None] * n
+    if len(cws) != n or len(pws) != n:
+        raise ValueError(f'class_weights / positive_class_weights: {len(cws)} / {len(pws)} entries for {n} terms')
+    cws = [_class_weight(cw, i, k, x) for i, (cw, k, x) in enumerate(zip(cws, kinds, inputs))]
+    pws = [_positive_weight(p, i, k) for i, (p, k) in enumerate(zip(pws, kinds))]
+    if all(cw is None for cw in cws) and all(p == 1.0 for p in pws):
+        return None
+    return cws, pws
+
+
+def _run(inputs, targets, kinds, weights, ignore_value, reduction, smoothing=(), class_weights=None,
+         positive_class_weights=None):
     if reduction != 'mean':
         raise NotImplementedError("only reduction='mean' (the reference's setting) is implemented")
+    options = _options(inputs, kinds, class_weights, positive_class_weights)
     smoothing = [(int(i), float(w), float(tau)) for i, w, tau in smoothing]
     for i, _, tau in smoothing:
         if not 0 <= i < len(kinds) or kinds[i] != _NLL:
@@ -166,13 +234,20 @@ def _run(inputs, targets, kinds, weights, ignore_value, reduction, smoothing=())
     # the scope's reducer, and only while autograd records (read here: grad mode is off inside Function.forward)
     reducer = _count_reducer if torch.is_grad_enabled() else None
     losses = _MultiTaskLoss.apply((list(kinds), list(targets), [float(w) for w in weights], ignore_value, reducer,
-                                   smoothing), *inputs)
+                                   smoothing, options), *inputs)
     return list(losses.unbind(0))
 
 
 def multi_task_loss(input: list, target: list, loss_functions: list, weight: list = None, ignore_value=-1,
-                    reduction: str = 'mean', smoothing: list = None):
+                    reduction: str = 'mean', smoothing: list = None, class_weights: list = None,
+                    positive_class_weights: list = None):
     """pyrutils/torch/losses.py:39-51: the list of weighted losses, one per (input, target, loss function).
+
+    class_weights / positive_class_weights: lists aligned with the terms. class_weights[i] is None, a [C] tensor (taken as
+    it is, never read back) or a sequence of floats (checked, uploaded once per device): F.nll_loss's weight= for NLL term i.
+    positive_class_weights[i] is None or a number: the positive_class_weight of BCE term i. An entry on a term of another
+    kind, a wrong length, or a negative / non-finite host value raises ValueError before any launch. When any term carries
+    one, all terms of the call run through twog_weighted_loss_* (one launch per direction, as without).
 
     smoothing: a list of (index, weight, tau); term j is weight * temporal_smoothing_loss(input[index], target[index], tau),
     appended after the zipped terms in list order (input[index] must be an NLL term's (bs, C, T, E) log-probabilities). Each
@@ -185,7 +260,9 @@ def multi_task_loss(input: list, target: list, loss_functions: list, weight: lis
         if fn not in _KIND:
             raise NotImplementedError(f'loss function {fn} is not part of the 2G-GCN criterion')
         kinds.append(_KIND[fn])
-    return _run(list(input[:n]), list(target[:n]), kinds, list(weight[:n]), ignore_value, reduction, smoothing or ())
+    return _run(list(input[:n]), list(target[:n]), kinds, list(weight[:n]), ignore_value, reduction, smoothing or (),
+                None if class_weights is None else list(class_weights)[:n],
+                None if positive_class_weights is None else list(positive_class_weights)[:n])
 
 
 def select_loss(model_name: str, model_input_type: str, dataset_name: str, cfg):
@@ -219,16 +296,29 @@ def select_loss(model_name: str, model_input_type: str, dataset_name: str, cfg):
         weight += [fl_weight] * 2 + [weight_val, ant_weight]
         fns = (budget_loss, binary_cross_entropy_loss) + (nll_loss,) * 4
         names = ['B_HS', 'BCE_HS', 'NLL_SAR_F', 'NLL_SAP_F', 'NLL_SAR', 'NLL_SAP']
+    # Beyond the reference, against label imbalance. misc.class_weights = {add, subactivity: [...], affordance: [...]}: the
+    # per-class weights of the human NLL terms (NLL_SAR(_F), NLL_SAP(_F)) and of the object ones (NLL_OA*); and
+    # misc.segmentation_loss.positive_class_weight on the BCE terms. The keywords appear only with the keys.
+    options = {}
+    cw_cfg = misc.get('class_weights', {})
+    if cw_cfg.get('add', False):
+        by_prefix = {'NLL_SA': cw_cfg.get('subactivity', None), 'NLL_OA': cw_cfg.get('affordance', None)}
+        cws = [by_prefix.get(name[:6]) for name in names]
+        if any(cw is not None for cw in cws):
+            options['class_weights'] = [None if cw is None else [float(v) for v in cw] for cw in cws]
+    p = seg.get('positive_class_weight', 1)
+    if p != 1:
+        options['positive_class_weights'] = [float(p) if fn is binary_cross_entropy_loss else None for fn in fns]
     smooth = misc.get('smoothing_loss', {})
     if not smooth.get('add', False):
-        return partial(multi_task_loss, loss_functions=fns, weight=weight), names
+        return partial(multi_task_loss, loss_functions=fns, weight=weight, **options), names
     # one smoothing term per final-level NLL term (the last 2 or 4 of the list; not the frame-level _F ones), weighted
     # relative to it: the stage-1 pretraining zeros and the anticipation weight carry over
     first = len(fns) - (4 if cad else 2)
     s_weight, tau = smooth.get('weight', 0.15), smooth.get('tau', 4.0)
     smoothing = [(i, s_weight * weight[i], tau) for i in range(first, len(fns))]
     names = names + ['TMSE_' + names[i][len('NLL_'):] for i in range(first, len(fns))]
-    return partial(multi_task_loss, loss_functions=fns, weight=weight, smoothing=smoothing), names
+    return partial(multi_task_loss, loss_functions=fns, weight=weight, smoothing=smoothing, **options), names
 
 
 def _n_smoothing_terms(dataset_name, cfg):
@@ -252,3 +342,38 @@ def select_loss_learning_mask(model_name: str, dataset_name: str, cfg):
         raise ValueError(f'Multi-task learning option not implemented for {model_name}')
     mask = [False] * 4 + [True] * 8 if dataset_name == 'cad120' else [False] * 2 + [True] * 4
     return mask + [False] * _n_smoothing_terms(dataset_name, cfg)
+
+
+def class_counts(targets, num_classes, ignore_index=-1, out=None):
+    """Labels per class of a target tensor, on its device, under the NLL terms' rule (a label equal to ignore_index or outside
+    [0, num_classes) is skipped): int64 [num_classes]. With `out` (such a tensor) the counts are ADDED to it and it is
+    returned, so a pass over a loader's targets accumulates without a host synchronisation."""
+    targets = targets.to(torch.int64).contiguous()
+    if out is None:
+        out = torch.zeros(int(num_classes), dtype=torch.int64, device=targets.device)
+    return get_kernels().class_counts(targets, int(num_classes), int(ignore_index), out)
+
+
+def class_weights(counts, scheme='balanced', beta=0.999):
+    """Per-class weights from class counts, computed once on the host in fp64: fp32 [C] on the counts' device.
+    'balanced': N / (K * n_c), N the number of labels and K the number of classes present (sklearn's
+    compute_class_weight('balanced') over the classes present). 'effective': (1 - beta) / (1 - beta^n_c), the inverse
+    effective number of samples (Cui et al., CVPR 2019), scaled to sum to K. A class without labels gets 0."""
+    import numpy as np
+    device = counts.device if torch.is_tensor(counts) else 'cpu'
+    n = np.asarray(counts.cpu() if torch.is_tensor(counts) else counts).astype(np.float64)
+    if n.ndim != 1 or (n < 0).any():
+        raise ValueError('class counts: a 1-D array of non-negative numbers is expected')
+    present = n > 0
+    K = int(present.sum())
+    w = np.zeros_like(n)
+    if scheme == 'balanced':
+        w[present] = n.sum() / (K * n[present])
+    elif scheme == 'effective':
+        if not 0 <= beta < 1:
+            raise ValueError(f'beta must lie in [0, 1), got {beta}')
+        w[present] = (1.0 - beta) / (1.0 - np.power(np.float64(beta), n[present]))
+        w *= K / w.sum() if K else 0.0
+    else:
+        raise ValueError(f"scheme must be 'balanced' or 'effective', got {scheme!r}")
+    return torch.from_numpy(w.astype(np.float32)).to(device)

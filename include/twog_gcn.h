@@ -870,6 +870,59 @@ int twog_multitask_loss_bwd(const twog_loss_t* terms, int n_terms, const double*
                             void* stream);
 
 /* ===============================================================================================================
+ * The same criterion with the two imbalance options: per-class weights on the NLL terms (F.nll_loss(weight=)) and the
+ * positive-class weight of the BCE terms (pyrutils/torch/losses.py:17-18). A second pair of entry points with a struct of
+ * its own; twog_loss_t and twog_multitask_loss_* above are unchanged. Same launch shape: a (TWOG_LOSS_BLOCKS, terms) grid,
+ * TWOG_LOSS_BLOCKS fp64 partial sums per term added in a fixed order, then one sequential pass; stats[term] = {sum, den}
+ * stays on the device for the backward call. Up to TWOG_LOSS_MAX_TERMS terms of all three kinds in one launch per direction.
+ * No multiplication below is fused with an addition; (double) and (float) are conversions, fl() is one fp32 rounding.
+ *
+ * kind 0, NLL, class_weight cw ([n_classes] device floats; NULL: every cw = 1):
+ *   an element (o, i) with target y is kept when y != ignore && 0 <= y < C (the rule of twog_loss_t)
+ *   sum  = sum over kept of (double)cw[y] * (double)(-x[o][y][i])     (the product of two fp32 values is exact in fp64)
+ *   den  = sum over kept of (double)cw[y]                            (NULL: the count of kept elements)
+ *   loss = w * (float)(sum / den); 0 / 0 gives NaN, as torch gives for weight= with no kept weight
+ *   g = w * dloss / (float)den in fp32, 0 when den <= 0
+ *   d x[o][y][i] = -fl(g * cw[y]) at kept elements (NULL: -g); every other element of dinput is stored as 0
+ *   Negative, infinite or NaN class weights: whatever IEEE arithmetic gives; not specified.
+ * kind 1, BCE, positive_class_weight p; an element is kept when t != ignore; den = the count of kept elements:
+ *   where t == 1.0f && p > 1:   term = -fmaxf(fl(p * logf(x)), -100.f)
+ *   everywhere else:            term = -fl(fl(t * fmaxf(logf(x), -100.f)) + fl(fl(1.f - t) * fmaxf(logf(fl(1.f - x)), -100.f)))
+ *   sum = sum over kept of (double)term;  loss = w * (float)(sum / den), 0 when den == 0
+ *   g as above;  d0 = fl(fl(g * fl(x - t)) / fmaxf(fl(fl(1.f - x) * x), 1e-12f))   (torch's binary_cross_entropy backward)
+ *   d x = fl(d0 * p) where t == 1.0f && p > 1, d0 at every other kept element, 0 at ignored ones
+ *   p <= 1 changes nothing, and neither does a target other than exactly 1.0 (a smoothed 0.5, say), as in the reference.
+ *   The reference raises the input to the power p (x' = x ** p) and hands x' to F.binary_cross_entropy. log(x ** p) and
+ *   p * log x are clamped at -100 on the same inputs and differ by the fp32 rounding of x ** p only: on x in
+ *   [1e-3, 1 - 1e-3], p in {1.5, 2, 2.5, 3} the fp64 form of this definition is within 1.5e-7 relative of the reference's
+ *   loss and 2.4e-7 of its input gradient, the reference's own fp32 rounding. Outside that domain -- where x ** p leaves
+ *   fp32's range (underflows to 0 or to a subnormal) or (1 - x') x' < 1e-12 -- THIS definition holds, not torch's
+ *   composition: x = 0 at t = 1 gives term 100 and d x = fl(-g * 1e12 * p); x = 1 gives 0 and 0.
+ * kind 2, budget: no option; as in twog_loss_t.
+ * With class_weight NULL (or all ones) and p <= 1 the results equal twog_multitask_loss_* bit for bit whenever the BCE
+ * targets are 0, 1 or ignored (with those, a fused and a separate multiply-add cannot differ).
+ * Both return -1 on what twog_multitask_loss_* rejects and on a positive_class_weight that is negative or not finite.
+ * =============================================================================================================== */
+typedef struct {
+    int32_t kind;
+    int32_t n_classes;
+    int64_t outer, inner;
+    const float* input;
+    const void* target;
+    float* dinput;
+    float weight;
+    float ignore_value;
+    const float* class_weight;
+    float positive_class_weight;
+    int32_t pad0_;
+} twog_wloss_t;
+/* partials: workspace of n_terms * TWOG_LOSS_BLOCKS * 2 doubles; stats: [n_terms][2] doubles; losses: [n_terms] floats. */
+int twog_weighted_loss_fwd(const twog_wloss_t* terms, int n_terms, double* partials, double* stats, float* losses,
+                           void* stream);
+int twog_weighted_loss_bwd(const twog_wloss_t* terms, int n_terms, const double* stats, const float* dlosses,
+                           void* stream);
+
+/* ===============================================================================================================
  * Temporal smoothing loss: the truncated mean-squared error between the log-probabilities of adjacent steps (T-MSE,
  * Farha & Gall, MS-TCN, CVPR 2019), the training-side companion of the segmental metrics (F1@k, edit score): it acts on
  * predictions that flicker between labels for a few steps. Not part of the reference; csrc/loss.hip.
@@ -1027,6 +1080,13 @@ int twog_segment_edit(const int64_t* y_true, const int64_t* y_pred, int n_seq, i
                       int64_t ignore_value, int use_ignore, int64_t bg_label, int use_bg, double* score, int32_t* distance,
                       int32_t* n_true, int32_t* n_pred, int32_t* valid, void* stream);
 int twog_segment_edit_limits(int* max_steps);
+/* twog_class_counts: ADDS, per class c, the number of targets[i] == c among n int64 labels to counts[c] (int64 [n_classes]),
+ * under the rule of the NLL term: a label is counted when it is != ignore_index and 0 <= label < n_classes; every other
+ * label is skipped (twog_confusion_counts ignores -1 only and reports the rest as errors, so it cannot stand in). An LDS
+ * histogram per workgroup and one integer atomic per non-empty class per workgroup: the totals do not depend on the order.
+ * Returns -1 on n < 0 or n_classes < 1, -2 on more than TWOG_CLASS_COUNTS_MAX classes. */
+#define TWOG_CLASS_COUNTS_MAX 4096
+int twog_class_counts(const int64_t* targets, int64_t n, int n_classes, int64_t ignore_index, int64_t* counts, void* stream);
 
 #ifdef __cplusplus
 }
