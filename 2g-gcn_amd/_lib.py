@@ -194,6 +194,23 @@ class Ranges(C.Structure):  # twog_ranges_t
                 ('pad_', C.c_int32)]
 
 
+BIGRU_PLAN_HEAD, BIGRU_PLAN_MAX_COMBOS = 8, 32   # TWOG_BIGRU_PLAN_HEAD, TWOG_BIGRU_PLAN_MAX_COMBOS
+BIGRU_PLAN_INTS = BIGRU_PLAN_HEAD + 4 * BIGRU_PLAN_MAX_COMBOS   # TWOG_BIGRU_PLAN_INTS
+
+
+def bigru_persistent_plan(lib, Es, bs, h, n_cus=0):
+    """twog_bigru_persistent_plan of the loaded library `lib` as a dict (include/twog_gcn.h states every field); with n_cus > 0
+    no device is touched. served False: the shape is refused, the other fields but n_cus are 0 / empty."""
+    out = (C.c_int32 * BIGRU_PLAN_INTS)()
+    rc = lib.twog_bigru_persistent_plan((C.c_int32 * max(1, len(Es)))(*Es), len(Es), bs, h, n_cus, out)
+    if rc != 0:
+        raise RuntimeError(f'twog_bigru_persistent_plan failed with code {rc}')
+    n = max(0, out[0])
+    combos = [tuple(out[BIGRU_PLAN_HEAD + 4 * i:BIGRU_PLAN_HEAD + 4 * i + 4]) for i in range(n)]
+    return dict(served=out[0] > 0, n_combos=out[0], nkb=out[1], twc=out[2], grid=out[3], lds_fwd=out[4], lds_bwd=out[5],
+                bwd_served=bool(out[6]), n_cus=out[7], combos=combos)
+
+
 MTL_PASS, MTL_SOFTMAX, MTL_MSE, MTL_MAE = 0, 1, 2, 3   # TWOG_MTL_*
 MTL_MAX_TERMS = 16   # TWOG_MTL_MAX_TERMS
 
@@ -245,6 +262,7 @@ SIGNATURES = {
     'twog_bigru_fwd_persistent': [C.POINTER(BiGru), _I, _I, _I, _I, _P, _P],
     'twog_bigru_bwd_persistent_supported': [C.POINTER(BiGruBwd), _I, _I, _I],
     'twog_bigru_bwd_persistent': [C.POINTER(BiGruBwd), _I, _I, _I, _I, _P, _P],
+    'twog_bigru_persistent_plan': [C.POINTER(C.c_int32), _I, _I, _I, _I, C.POINTER(C.c_int32)],
     'twog_bigru_bwd': [C.POINTER(BiGruBwd), _I, _I, _I, _I, _P, C.c_size_t, _P],
     'twog_gru_seq_fwd': [C.POINTER(BiGru), _I, _I, _I, _I, _P, C.c_size_t, _P],
     'twog_gru_seq_bwd': [C.POINTER(BiGruBwd), _I, _I, _I, _I, _P, C.c_size_t, _P],

@@ -481,23 +481,83 @@ static int plan(const int* E_of_type, int n_types, int bs, int hidden, int n_cus
     return n;
 }
 
+// Everything the two launches take from the partition: what they launch with, what the two *_supported functions rate, and
+// what twog_bigru_persistent_plan reports. One place: there is no second copy of this arithmetic.
+struct PLaunch {
+    int n_combos;   // (group, chunk) combinations, > 0
+    int nkb, twc;   // the forward instance bigru_persist_fwd_kernel<nkb, twc>: hidden / 32, and the largest tiles-per-wave of
+                    // any combination rounded up to an instance that exists (1, 2, 4)
+    int grid;       // workgroups of either launch: n_combos x hidden / 16
+    int lds_fwd;    // dynamic LDS bytes, forward: the slice's B fragments [hidden / 32][3 gates][3 planes] x 1 KB + the waves' scratch
+    int lds_bwd;    // backward: [3 hidden / 32][3 planes] x 1 KB + the waves' scratch
+    int bwd_served; // 1 when no wave owns more than one tile: the backward kernel has no other form
+};
+constexpr int SCRATCH_BYTES = 4 * 16 * 20 * 4;   // a [16][20] float transposition scratch per wave
+static_assert(TWOG_BIGRU_PLAN_MAX_COMBOS == MAXC, "the report of include/twog_gcn.h holds every combination");
+
+// plan() and what follows from it. Returns the number of combinations, or -1 (L and combos undefined) when the shape is not served.
+static int launch_plan(const int* E_of_type, int n_types, int bs, int hidden, int n_cus, PCombo* combos, PLaunch& L) {
+    if (n_types <= 0 || n_types > MAXG / 2) return -1;
+    const int n = plan(E_of_type, n_types, bs, hidden, n_cus, combos);
+    if (n <= 0) return -1;
+    int tw = 1;
+    for (int i = 0; i < n; ++i)
+        if (combos[i].tw > tw) tw = combos[i].tw;
+    L.n_combos = n;
+    L.nkb = hidden / 32;
+    L.twc = tw > 2 ? 4 : tw;
+    L.grid = n * (hidden / 16);
+    L.lds_fwd = (hidden / 32) * 9 * 1024 + SCRATCH_BYTES;
+    L.lds_bwd = (3 * hidden / 32) * 3 * 1024 + SCRATCH_BYTES;
+    L.bwd_served = tw == 1;
+    return n;
+}
+
+static hipError_t device_cus(int* n_cus) {
+    int dev = 0;
+    const hipError_t e = hipGetDevice(&dev);
+    return e != hipSuccess ? e : hipDeviceGetAttribute(n_cus, hipDeviceAttributeMultiprocessorCount, dev);
+}
+
+// The partition and the launch numbers of (E_of_type[n_types], bs, hidden) on n_cus compute units (<= 0: those of the current
+// device), without a launch; with n_cus > 0 without any device call. Layout of `out`: include/twog_gcn.h.
+extern "C" int twog_bigru_persistent_plan(const int32_t* E_of_type, int n_types, int bs, int hidden, int n_cus, int32_t* out) {
+    if (!out || (n_types > 0 && !E_of_type)) return -2;
+    if (n_cus <= 0) {
+        const hipError_t e = device_cus(&n_cus);
+        if (e != hipSuccess) return -(int)e;
+    }
+    for (int i = 0; i < TWOG_BIGRU_PLAN_INTS; ++i) out[i] = 0;
+    out[0] = -1;
+    out[7] = n_cus;
+    PCombo combos[MAXC];
+    PLaunch L;
+    int Es[MAXG / 2];
+    for (int k = 0; k < n_types && k < MAXG / 2; ++k) Es[k] = E_of_type[k];
+    if (launch_plan(Es, n_types, bs, hidden, n_cus, combos, L) < 0) return 0;
+    out[0] = L.n_combos; out[1] = L.nkb; out[2] = L.twc; out[3] = L.grid;
+    out[4] = L.lds_fwd; out[5] = L.lds_bwd; out[6] = L.bwd_served;
+    for (int i = 0; i < L.n_combos; ++i) {
+        int32_t* c = out + TWOG_BIGRU_PLAN_HEAD + 4 * i;
+        c[0] = combos[i].group; c[1] = combos[i].rt0; c[2] = combos[i].rt1; c[3] = combos[i].tw;
+    }
+    return 0;
+}
+
 // 2 if twog_bigru_fwd_persistent serves this shape on the current device AND is the faster path (every wave owns at
 // most one row tile: the small-batch regime, where a step is a latency chain -- 9.2 us per step against 17.4 at 8
 // clips; with more tiles per wave the launch-per-step path wins: 48 against 31 us at 64 clips, see profiles/HISTORY.md);
 // 1 if it is served but slower; 0 if it is not served.
 extern "C" int twog_bigru_persistent_supported(const twog_bigru_t* types, int n_types, int bs, int hidden) {
-    int dev = 0, n_cus = 0;
+    int n_cus = 0;
     if (n_types <= 0 || n_types > MAXG / 2) return 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    if (device_cus(&n_cus) != hipSuccess) return 0;
     PCombo combos[MAXC];
+    PLaunch L;
     int Es[MAXG / 2];
     for (int k = 0; k < n_types; ++k) Es[k] = types[k].E;
-    const int n = plan(Es, n_types, bs, hidden, n_cus, combos);
-    if (n <= 0) return 0;
-    for (int i = 0; i < n; ++i)
-        if (combos[i].tw > 1) return 1;
-    return 2;
+    if (launch_plan(Es, n_types, bs, hidden, n_cus, combos, L) < 0) return 0;
+    return L.twc > 1 ? 1 : 2;
 }
 
 // Same contract as twog_bigru_fwd (tmp_gh and zeros unused). sync: device memory, >= 1024 uint32, ZERO at launch
@@ -508,15 +568,14 @@ extern "C" int twog_bigru_fwd_persistent(const twog_bigru_t* types, int n_types,
                                          void* stream) {
     if (n_types <= 0 || T <= 0) return 0;
     if (n_types > MAXG / 2) return -2;
-    int dev = 0, n_cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return -(int)e;
-    e = hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev);
+    int n_cus = 0;
+    const hipError_t e = device_cus(&n_cus);
     if (e != hipSuccess) return -(int)e;
     PArgs P;
+    PLaunch L;
     int Es[MAXG / 2];
     for (int k = 0; k < n_types; ++k) Es[k] = types[k].E;
-    const int n_combos = plan(Es, n_types, bs, hidden, n_cus, P.c);
+    const int n_combos = launch_plan(Es, n_types, bs, hidden, n_cus, P.c, L);
     if (n_combos <= 0 || !sync) return -2;
     for (int k = 0; k < n_types; ++k)
         for (int dir = 0; dir < 2; ++dir) {
@@ -530,12 +589,8 @@ extern "C" int twog_bigru_fwd_persistent(const twog_bigru_t* types, int n_types,
     P.n_combos = n_combos; P.bs = bs; P.T = T;
     P.spin_limit = twog_persist_spin_limit();
     twog_jitter_configure();   // (no-op in the shipped library)
-    const int grid = n_combos * (hidden / 16);
-    const size_t lds = (size_t)(hidden / 32) * 9 * 1024 + 4 * 16 * 20 * 4;
-    int twc = 1;
-    for (int i = 0; i < n_combos; ++i)
-        if (P.c[i].tw > twc) twc = P.c[i].tw;
-    twc = twc > 2 ? 4 : twc;
+    const int grid = L.grid, twc = L.twc;
+    const size_t lds = (size_t)L.lds_fwd;
     hipStream_t st = (hipStream_t)stream;
 #define TWOG_GP_LAUNCH(NKB_, TWC_)                                                                              \
     do {                                                                                                        \
@@ -551,10 +606,10 @@ extern "C" int twog_bigru_fwd_persistent(const twog_bigru_t* types, int n_types,
         else if (twc == 2) TWOG_GP_LAUNCH(NKB_, 2);                                                             \
         else TWOG_GP_LAUNCH(NKB_, 4);                                                                           \
     } while (0)
-    switch (hidden) {
-        case 64: TWOG_GP_LAUNCH_H(2); break;
-        case 128: TWOG_GP_LAUNCH_H(4); break;
-        case 256: TWOG_GP_LAUNCH_H(8); break;
+    switch (L.nkb) {
+        case 2: TWOG_GP_LAUNCH_H(2); break;
+        case 4: TWOG_GP_LAUNCH_H(4); break;
+        case 8: TWOG_GP_LAUNCH_H(8); break;
         default: TWOG_GP_LAUNCH_H(16); break;
     }
 #undef TWOG_GP_LAUNCH_H
@@ -565,36 +620,30 @@ extern "C" int twog_bigru_fwd_persistent(const twog_bigru_t* types, int n_types,
 
 // 2 if twog_bigru_bwd_persistent serves this shape (at most one row tile per wave), else 0.
 extern "C" int twog_bigru_bwd_persistent_supported(const twog_bigru_bwd_t* types, int n_types, int bs, int hidden) {
-    int dev = 0, n_cus = 0;
+    int n_cus = 0;
     if (n_types <= 0 || n_types > MAXG / 2) return 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    if (device_cus(&n_cus) != hipSuccess) return 0;
     PCombo combos[MAXC];
+    PLaunch L;
     int Es[MAXG / 2];
     for (int k = 0; k < n_types; ++k) Es[k] = types[k].E;
-    const int n = plan(Es, n_types, bs, hidden, n_cus, combos);
-    if (n <= 0) return 0;
-    for (int i = 0; i < n; ++i)
-        if (combos[i].tw > 1) return 0;
-    return 2;
+    if (launch_plan(Es, n_types, bs, hidden, n_cus, combos, L) < 0) return 0;
+    return L.bwd_served ? 2 : 0;
 }
 
 extern "C" int twog_bigru_bwd_persistent(const twog_bigru_bwd_t* types, int n_types, int bs, int T, int hidden, void* sync,
                                          void* stream) {
     if (n_types <= 0 || T <= 0) return 0;
     if (n_types > MAXG / 2) return -2;
-    int dev = 0, n_cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return -(int)e;
-    e = hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev);
+    int n_cus = 0;
+    const hipError_t e = device_cus(&n_cus);
     if (e != hipSuccess) return -(int)e;
     BArgs P;
+    PLaunch L;
     int Es[MAXG / 2];
     for (int k = 0; k < n_types; ++k) Es[k] = types[k].E;
-    const int n_combos = plan(Es, n_types, bs, hidden, n_cus, P.c);
-    if (n_combos <= 0 || !sync) return -2;
-    for (int i = 0; i < n_combos; ++i)
-        if (P.c[i].tw > 1) return -2;
+    const int n_combos = launch_plan(Es, n_types, bs, hidden, n_cus, P.c, L);
+    if (n_combos <= 0 || !sync || !L.bwd_served) return -2;
     for (int k = 0; k < n_types; ++k)
         for (int dir = 0; dir < 2; ++dir) {
             BGroup& G = P.g[2 * k + dir];
@@ -607,8 +656,8 @@ extern "C" int twog_bigru_bwd_persistent(const twog_bigru_bwd_t* types, int n_ty
     P.n_combos = n_combos; P.bs = bs; P.T = T;
     P.spin_limit = twog_persist_spin_limit();
     twog_jitter_configure();   // (no-op in the shipped library)
-    const int grid = n_combos * (hidden / 16);
-    const size_t lds = (size_t)(3 * hidden / 32) * 3 * 1024 + 4 * 16 * 20 * 4;
+    const int grid = L.grid;
+    const size_t lds = (size_t)L.lds_bwd;
     hipStream_t st = (hipStream_t)stream;
 #define TWOG_GPB_LAUNCH(NKH_)                                                                       \
     do {                                                                                            \
@@ -618,10 +667,10 @@ extern "C" int twog_bigru_bwd_persistent(const twog_bigru_bwd_t* types, int n_ty
             return TWOG_PERSIST_NOT_RESIDENT;                                                       \
         hipLaunchKernelGGL(bigru_persist_bwd_kernel<NKH_>, dim3(grid), dim3(256), lds, st, P);      \
     } while (0)
-    switch (hidden) {
-        case 64: TWOG_GPB_LAUNCH(2); break;
-        case 128: TWOG_GPB_LAUNCH(4); break;
-        case 256: TWOG_GPB_LAUNCH(8); break;
+    switch (L.nkb) {
+        case 2: TWOG_GPB_LAUNCH(2); break;
+        case 4: TWOG_GPB_LAUNCH(4); break;
+        case 8: TWOG_GPB_LAUNCH(8); break;
         default: TWOG_GPB_LAUNCH(16); break;
     }
 #undef TWOG_GPB_LAUNCH

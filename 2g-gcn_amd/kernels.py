@@ -652,6 +652,12 @@ class HipKernels:
         self._check(self.lib.twog_guard_outputs(C.byref(g), self._stream()), 'twog_guard_outputs')
         return True
 
+    def bigru_persistent_plan(self, Es, bs, h, n_cus=0):
+        """What bigru_fwd / bigru_bwd would launch persistently for entity counts Es at this batch and width on n_cus compute
+        units (0: the current device's): forward instance (nkb, twc), grid, LDS bytes, whether the backward is served, and
+        the combinations (group, rt0, rt1, tw). Host arithmetic of the library (twog_bigru_persistent_plan), nothing launched."""
+        return L.bigru_persistent_plan(self.lib, Es, bs, h, n_cus)
+
     def bigru_persistent(self, arr, n, bs, h, dev=None):
         """True when the frame-level recurrence runs as the persistent launch: where the library serves the shape and
         rates it the faster path (small batches: at most one 16-row tile per wave). TWOG_BIGRU_PERSIST=1: wherever it is

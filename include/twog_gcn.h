@@ -338,6 +338,29 @@ int twog_bigru_bwd(const twog_bigru_bwd_t* types, int n_types, int bs, int T, in
  * twog_bigru_bwd (carry unused). sync: device memory, >= 1024 uint32, ZERO when the launch starts. */
 int twog_bigru_bwd_persistent_supported(const twog_bigru_bwd_t* types, int n_types, int bs, int hidden);
 int twog_bigru_bwd_persistent(const twog_bigru_bwd_t* types, int n_types, int bs, int T, int hidden, void* sync, void* stream);
+/* What the two persistent launches would launch with for entity counts E_of_type[n_types] at this batch and width on n_cus
+ * compute units (n_cus <= 0: those of the current device): host arithmetic only, nothing is launched, and with n_cus > 0 no
+ * device is touched. The launchers and the two *_supported functions take their numbers from the same code. out: int32
+ * [TWOG_BIGRU_PLAN_INTS], written whole:
+ *   out[0]  number of (group, chunk) combinations, or -1: the shape is not served (n_types not 1 .. 4, hidden not 64 / 128 /
+ *           256 / 512, a type without rows, more workgroups than compute units, a chunk of more than 16 row tiles); every
+ *           field below except out[7] is then 0
+ *   out[1]  NKB, out[2] TWC: the forward launch runs bigru_persist_fwd_kernel<NKB, TWC>; NKB = hidden / 32, TWC = the most row
+ *           tiles any wave owns, rounded up to 1, 2 or 4. twog_bigru_persistent_supported = 2 iff TWC == 1, 1 iff TWC > 1
+ *   out[3]  grid of either launch: combinations x hidden / 16 workgroups of 256 threads
+ *   out[4]  dynamic LDS bytes of the forward launch, out[5] of the backward launch
+ *   out[6]  1 when the backward launch serves the shape (no wave owns more than one tile: twog_bigru_bwd_persistent_supported
+ *           = 2), else 0
+ *   out[7]  the compute-unit count the plan was made for
+ *   out[TWOG_BIGRU_PLAN_HEAD + 4 i ...], i < out[0]: {group, rt0, rt1, tw} of combination i -- group = 2 x type + direction
+ *           (0 forward, 1 reverse), the combination's 16-row tiles [rt0, rt1) of that group's bs x E rows, tw = ceil((rt1 - rt0)
+ *           / 4) tiles per wave: wave w of each of its hidden / 16 workgroups owns tiles rt0 + w tw ... and leaves at once
+ *           when that is not below rt1. Workgroup b works combination b % out[0], unit slice b / out[0].
+ * Returns 0 (also for a shape that is not served), -2 for a NULL argument, or the negative HIP error of the device query. */
+#define TWOG_BIGRU_PLAN_HEAD 8
+#define TWOG_BIGRU_PLAN_MAX_COMBOS 32
+#define TWOG_BIGRU_PLAN_INTS (TWOG_BIGRU_PLAN_HEAD + 4 * TWOG_BIGRU_PLAN_MAX_COMBOS)
+int twog_bigru_persistent_plan(const int32_t* E_of_type, int n_types, int bs, int hidden, int n_cus, int32_t* out);
 
 /* Single-direction frame recurrence: nn.GRU(bidirectional=False) applied per entity slice by the baseline models'
  * _process_frame_level_rnn (vhoi/models.py:70-87, :157-175; modules :25-28, :102-105). The same descriptors and the
