@@ -218,6 +218,20 @@ MTL_MAX_TERMS = 16   # TWOG_MTL_MAX_TERMS
 class Mtl(C.Structure):  # twog_mtl_t
     _fields_ = [('kind', C.c_int32 * MTL_MAX_TERMS), ('n', C.c_int32), ('pad_', C.c_int32)]
 
+
+OPTIM_CLIP, OPTIM_DECOUPLED, OPTIM_SKIP_NONFINITE = 1, 2, 4   # TWOG_OPTIM_*
+
+
+class OptimState(C.Structure):  # twog_optim_state_t: the 64-byte step state of the device-side Adam
+    _fields_ = [('step', C.c_int64), ('skipped', C.c_int64), ('beta1_pow', C.c_double), ('beta2_pow', C.c_double),
+                ('lr', C.c_float), ('step_size', C.c_float), ('bc2s', C.c_float), ('clip_k', C.c_float),
+                ('decay_mul', C.c_float), ('apply', C.c_int32), ('reserved_', C.c_int64)]
+
+
+class OptimHyper(C.Structure):  # twog_optim_hyper_t
+    _fields_ = [('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float), ('weight_decay', C.c_float),
+                ('grad_scale', C.c_float), ('ema_decay', C.c_float)]
+
 # name -> (argtypes) ; every function returns int except twog_version
 _I, _L, _F, _P = C.c_int, C.c_int64, C.c_float, C.c_void_p
 SIGNATURES = {
@@ -325,6 +339,8 @@ SIGNATURES = {
     'twog_adam_step_coef': [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P, _P],
     'twog_mtl_weight_fwd': [C.POINTER(Mtl), _P, _P, _P, _P],
     'twog_mtl_weight_bwd': [C.POINTER(Mtl), _P, _P, _P, _P, _P, _I, _P],
+    'twog_optim_prepare': [_P, C.POINTER(OptimHyper), _F, _P, C.POINTER(C.c_void_p), _I, _P, _I, _P],
+    'twog_optim_apply': [_P, _P, _P, _P, _P, _L, C.POINTER(OptimHyper), _I, _P, _P],
     'twog_predict_labels': [_P, _I, _I, _I, _I, _I, _I, _P, _P],
     'twog_f1_at_k': [_P, _P, _I, _I, _I, C.c_double, _L, _I, _P, _P, _P, _P],
     'twog_eval_update': [_P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P],

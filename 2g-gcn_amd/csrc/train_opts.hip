@@ -1,6 +1,7 @@
 // Training-step options of the reference's trainer on the fused step (include/twog_gcn.h, "Training-step options"):
 // the global gradient norm of clip_grad_norm_ (pyrutils/torch/train_utils.py:149-153), Adam reading the clip coefficient
-// from device memory, and the multi-task loss learner's weighting (pyrutils/torch/multi_task.py:10-75).
+// from device memory, and the multi-task loss learner's weighting (pyrutils/torch/multi_task.py:10-75). Further down: Adam
+// with its step state on the device (twog_optim_prepare / twog_optim_apply: checkpoints, NaN skip, AdamW, EMA).
 //
 // The norm is the only one with a cost: one read of the model's flat gradient buffer (45.5 M floats = 182 MB for the
 // headline model). Each workgroup of the first launch sums fp64 squares of a fixed set of float4 groups (four loads in flight
@@ -180,6 +181,110 @@ bool mtl_spec_ok(const twog_mtl_t* spec) {
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Adam with its step state on the device (include/twog_gcn.h states the arithmetic; tests/optim_state_ref.py is its numpy form).
+// One rounding per operation is the contract. hipcc contracts a * b + c into a fused multiply-add by default, the __f*_rn
+// functions of its headers included (they are the plain operators), so the functions below switch contraction off for their own
+// statements; fp32 division and square root are correctly rounded by default.
+__global__ __launch_bounds__(64) void optim_prepare_kernel(twog_optim_state_t* st, const twog_optim_hyper_t h, float lr,
+                                                           const float* lr_ptr, const float* norm0, const float* norm1,
+                                                           const float* coef, int flags) {
+#pragma clang fp contract(off)
+    if (threadIdx.x != 0) return;
+    bool finite = true;
+    if (norm0) finite = finite && isfinite(norm0[0]);
+    if (norm1) finite = finite && isfinite(norm1[0]);
+    if ((flags & TWOG_OPTIM_SKIP_NONFINITE) && !finite) {
+        st->skipped += 1;
+        st->apply = 0;
+        return;
+    }
+    const double b1p = st->beta1_pow * (double)h.beta1, b2p = st->beta2_pow * (double)h.beta2;
+    if (lr_ptr) lr = lr_ptr[0];
+    const float bc1 = (float)(1.0 - b1p);
+    float k = 1.f;
+    if (coef) {
+        const float c = coef[0];
+        if (c < 1.f) k = c;
+    }
+    st->step += 1;
+    st->beta1_pow = b1p;
+    st->beta2_pow = b2p;
+    st->lr = lr;
+    st->step_size = lr / bc1;
+    st->bc2s = (float)__builtin_sqrt(1.0 - b2p);
+    st->clip_k = k;
+    st->decay_mul = 1.f - lr * h.weight_decay;
+    st->apply = 1;
+}
+
+struct OptimStep {
+    float b1, b2, omb1, omb2, eps, wd, gscale, d, omd, step_size, bc2s, clip_k, decay_mul;
+    int flags;
+};
+
+template <bool EMA>
+__device__ __forceinline__ void optim_elem(float& p, float g, float& m, float& v, float& ema, const OptimStep& s) {
+#pragma clang fp contract(off)
+    g = g * s.gscale;
+    if (s.flags & TWOG_OPTIM_CLIP) g = g * s.clip_k;
+    float p0 = p;
+    if (s.flags & TWOG_OPTIM_DECOUPLED) {
+        p0 = p * s.decay_mul;
+    } else if (s.wd != 0.f) {
+        const float wp = s.wd * p;
+        g = g + wp;
+    }
+    const float m0 = s.b1 * m, m1 = s.omb1 * g;
+    m = m0 + m1;
+    const float gg = g * g, v0 = s.b2 * v, v1 = s.omb2 * gg;
+    v = v0 + v1;
+    const float num = s.step_size * m, den = __builtin_sqrtf(v) / s.bc2s + s.eps;   // (the sum's operand is a quotient)
+    p = p0 - num / den;
+    if (EMA) {
+        const float e0 = s.d * ema, e1 = s.omd * p;
+        ema = e0 + e1;
+    }
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(TWOG_STREAM_THREADS) void optim_apply_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                          float* __restrict__ m, float* __restrict__ v,
+                                                                          float* __restrict__ ema, int64_t n, int head,
+                                                                          const twog_optim_hyper_t h, int flags,
+                                                                          const twog_optim_state_t* __restrict__ st) {
+    if (st->apply == 0) return;   // a skipped step: nothing is written
+    OptimStep s;
+    {
+#pragma clang fp contract(off)
+        s.b1 = h.beta1, s.b2 = h.beta2, s.omb1 = 1.f - h.beta1, s.omb2 = 1.f - h.beta2;
+        s.eps = h.eps, s.wd = h.weight_decay, s.gscale = h.grad_scale, s.d = h.ema_decay, s.omd = 1.f - h.ema_decay;
+    }
+    s.step_size = st->step_size, s.bc2s = st->bc2s, s.clip_k = st->clip_k, s.decay_mul = st->decay_mul, s.flags = flags;
+    const int64_t tid = (int64_t)blockIdx.x * TWOG_STREAM_THREADS + threadIdx.x;
+    const int64_t nthr = (int64_t)gridDim.x * TWOG_STREAM_THREADS;
+    // [0, head) in front of the first 16-byte boundary (head <= 3, head <= n), n4 groups of four, then [a1, n) (at most 3)
+    const int64_t n4 = (n - head) >> 2, a1 = head + n4 * 4;
+    float4* p4 = reinterpret_cast<float4*>(p + head);
+    const float4* g4 = reinterpret_cast<const float4*>(g + head);
+    float4* m4 = reinterpret_cast<float4*>(m + head);
+    float4* v4 = reinterpret_cast<float4*>(v + head);
+    float4* e4 = EMA ? reinterpret_cast<float4*>(ema + head) : nullptr;
+    for (int64_t i = tid; i < n4; i += nthr) {
+        float4 P = p4[i], M = m4[i], V = v4[i], E = EMA ? e4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 G = g4[i];
+        optim_elem<EMA>(P.x, G.x, M.x, V.x, E.x, s);
+        optim_elem<EMA>(P.y, G.y, M.y, V.y, E.y, s);
+        optim_elem<EMA>(P.z, G.z, M.z, V.z, E.z, s);
+        optim_elem<EMA>(P.w, G.w, M.w, V.w, E.w, s);
+        p4[i] = P, m4[i] = M, v4[i] = V;
+        if (EMA) e4[i] = E;
+    }
+    float dummy = 0.f;
+    if (tid < head) optim_elem<EMA>(p[tid], g[tid], m[tid], v[tid], EMA ? ema[tid] : dummy, s);
+    if (tid < n - a1) optim_elem<EMA>(p[a1 + tid], g[a1 + tid], m[a1 + tid], v[a1 + tid], EMA ? ema[a1 + tid] : dummy, s);
+}
+
 }  // namespace
 
 extern "C" int twog_grad_norm(const float* buf, const twog_ranges_t* ranges, float scale, float max_norm, double* partials,
@@ -231,6 +336,39 @@ extern "C" int twog_mtl_weight_bwd(const twog_mtl_t* spec, const float* losses, 
     if (!losses || !log_sds || !dout || !dlog_sds) return -2;
     hipLaunchKernelGGL(mtl_bwd_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *spec, losses, log_sds, dout, dlosses,
                        dlog_sds, accumulate);
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int twog_optim_prepare(twog_optim_state_t* state, const twog_optim_hyper_t* hyper, float lr, const float* lr_ptr,
+                                  const float* const* norms, int n_norms, const float* coef, int flags, void* stream) {
+    if (!state || !hyper || n_norms < 0 || n_norms > 2 || (n_norms > 0 && !norms)) return -2;
+    for (int j = 0; j < n_norms; ++j)
+        if (!norms[j]) return -2;
+    hipLaunchKernelGGL(optim_prepare_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, *hyper, lr, lr_ptr,
+                       n_norms > 0 ? norms[0] : nullptr, n_norms > 1 ? norms[1] : nullptr, coef, flags);
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int twog_optim_apply(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                const twog_optim_hyper_t* hyper, int flags, const twog_optim_state_t* state, void* stream) {
+    if (!state || !hyper || !param || !grad || !exp_avg || !exp_avg_sq || n < 0) return -2;
+    if (ema && !(hyper->ema_decay > 0.f && hyper->ema_decay < 1.f)) return -2;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(param) & 15;
+    if ((a & 3) != 0) return -2;
+    for (const void* q : {(const void*)grad, (const void*)exp_avg, (const void*)exp_avg_sq, (const void*)(ema ? ema : param)})
+        if ((reinterpret_cast<uintptr_t>(q) & 15) != a) return -2;
+    if (n == 0) return 0;
+    int64_t head = ((16 - (int64_t)a) & 15) >> 2;
+    if (head > n) head = n;
+    const int grid = twog_stream_blocks(TWOG_STREAM_OPTIM, n);
+    if (ema)
+        hipLaunchKernelGGL(optim_apply_kernel<true>, dim3(grid), dim3(TWOG_STREAM_THREADS), 0, (hipStream_t)stream, param, grad,
+                           exp_avg, exp_avg_sq, ema, n, (int)head, *hyper, flags, state);
+    else
+        hipLaunchKernelGGL(optim_apply_kernel<false>, dim3(grid), dim3(TWOG_STREAM_THREADS), 0, (hipStream_t)stream, param, grad,
+                           exp_avg, exp_avg_sq, ema, n, (int)head, *hyper, flags, state);
     TWOG_CHECK_LAUNCH();
     return 0;
 }

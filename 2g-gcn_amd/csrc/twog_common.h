@@ -63,6 +63,7 @@ inline int twog_stream_blocks(int kernel, int64_t work) {
         case TWOG_STREAM_SCALE_ROWS: cap = 8192; break;
         case TWOG_STREAM_COPY_BLOCKS: items = (work + 3) / 4; cap = 512; break;
         case TWOG_STREAM_FILL_ZERO: items = work / 16; cap = 4096; break;
+        case TWOG_STREAM_OPTIM: items = work / 4; cap = 2048; break;   // 8 workgroups per CU, one float4 of each buffer per thread and trip
         default: return -2;
     }
     int64_t g = (items + TWOG_STREAM_THREADS - 1) / TWOG_STREAM_THREADS;

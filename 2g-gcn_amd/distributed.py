@@ -12,6 +12,7 @@ per rank. Dead parameters (constructed by the reference but never used, SURVEY.m
 The three cross-sample couplings of SURVEY 8e have an exact-equivalence switch each: sync_bn (a), count_weighted_loss
 (b), global_noise_seed or device_noise_seed (c).
 """
+import contextlib
 import os
 import weakref
 
@@ -54,6 +55,9 @@ class FlatParameters:
         their own after the model's last one. `module_ranges[0]` is the model's (begin, end) slice, `module_ranges[1 + j]`
         that of extra_modules[j]."""
         named = list(module.named_parameters())
+        # (name, parameter) in named_parameters() order, the model first, then each extra module: the layout below sorts by
+        # stage, an optimizer checkpoint (FusedAdam.state_dict) is in this order
+        self.named_groups = [list(named)] + [list(m.named_parameters()) for m in extra_modules]
         if stage_of is not None:
             named.sort(key=lambda kv: stage_of(kv[0]))
         groups = [named] + [list(m.named_parameters()) for m in extra_modules]
@@ -115,18 +119,52 @@ class FusedAdam:
     all-reduced) gradient buffer, measured on the averaged gradient g * grad_scale, then Adam reading the clip coefficient
     from the device. The slices of extra modules (FlatParameters(extra_modules=...): the loss learner) are stepped without
     it. step() then returns the pre-clip norm as a 0-d device tensor (what clip_grad_norm_ returns); nothing is read on
-    the host."""
+    the host.
 
-    def __init__(self, flat: FlatParameters, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0):
+    The device path. Any of decoupled_weight_decay, skip_nonfinite, ema_decay, device_state, or a one-element fp32 device
+    tensor as `lr` (read by the step's own launch: a schedule writes it, no host value is needed) moves the step's scalar state
+    -- step number, bias corrections, clip coefficient, the decision to apply or skip -- into a 64-byte block on the device
+    (twog_optim_state_t) that one small launch advances (twog_optim_prepare) in front of the element-wise update
+    (twog_optim_apply); without them the launches are exactly the ones above. The arithmetic is stated in include/twog_gcn.h:
+    one fp32 rounding per operation, the bias corrections from fp64 running products of the betas (tests/optim_state_ref.py
+    reproduces it bit for bit); it differs from the path above by contraction and the form of the bias corrections only.
+      decoupled_weight_decay: AdamW, p <- p (1 - lr weight_decay) in front of the update instead of L2 added to the gradient.
+      skip_nonfinite: the norm of the model's gradients and, with extra modules, a second norm over theirs are taken; if either
+        is not finite the step is SKIPPED on the device: parameters, moments, averaged weights, step number and powers stay
+        as they are and skipped_steps() counts it. The norm is an fp32 number: one that is not representable in fp32 (beyond
+        3.4e38, from finite gradients) counts as non-finite. Under DataParallel every rank sees the same all-reduced gradient
+        and therefore takes the same decision.
+      ema_decay: averaged weights ema <- d ema + (1 - d) p' inside the update (they start as a copy of the parameters);
+        ema_state_dict() / swap_ema() give them to an evaluation.
+    step() returns the pre-clip norm of the model's gradients whenever one was computed and reads nothing on the host.
+    Out of scope: learning rates or decay per group, amsgrad, capture of the step into a hipGraph."""
+
+    def __init__(self, flat: FlatParameters, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0,
+                 decoupled_weight_decay=False, skip_nonfinite=False, ema_decay=None, device_state=False):
         if not max_grad_norm >= 0.0:
             raise ValueError(f'max_grad_norm must be >= 0, got {max_grad_norm}')
+        if ema_decay is not None and not 0.0 < ema_decay < 1.0:
+            raise ValueError(f'ema_decay must lie in (0, 1), got {ema_decay}')
+        if torch.is_tensor(lr) and not (lr.dtype == torch.float32 and lr.numel() == 1 and lr.device == flat.flat.device):
+            raise ValueError('a tensor lr must be one fp32 element on the device of the parameters')
         self.flat, self.lr, self.betas, self.eps, self.wd = flat, lr, betas, eps, weight_decay
         self.max_grad_norm = float(max_grad_norm)
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
-        self.step_count = 0
+        self.step_count = 0   # the path without device state; step_number() answers on both
+        self.decoupled, self.skip_nonfinite = bool(decoupled_weight_decay), bool(skip_nonfinite)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.on_device = bool(self.decoupled or self.skip_nonfinite or ema_decay is not None or device_state
+                              or torch.is_tensor(lr))
+        self.ema = flat.flat.detach().clone() if ema_decay is not None else None
+        self.state = get_kernels().new_optim_state(0, 0, betas[0], betas[1], flat.flat.device) if self.on_device else None
+        self._skipped, self._swapped = 0, False
 
     def step(self, grad_scale=1.0):
+        if self._swapped:
+            raise RuntimeError('step() inside swap_ema(): the parameter buffer holds the averaged weights')
+        if self.on_device:
+            return self._device_step(grad_scale)
         self.step_count += 1
         K, f = get_kernels(), self.flat
         args = (self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, grad_scale)
@@ -139,6 +177,156 @@ class FusedAdam:
         if e < f.numel:   # the extra modules: never clipped
             K.adam_step(f.flat[e:], f.grad[e:], self.exp_avg[e:], self.exp_avg_sq[e:], *args)
         return out[0]
+
+    def _hyper(self, grad_scale=1.0):
+        return dict(beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.wd, grad_scale=grad_scale,
+                    ema_decay=self.ema_decay)
+
+    def _device_step(self, grad_scale):
+        """Norm(s), one prepare launch, one update launch per range; nothing is read on the host."""
+        K, f = get_kernels(), self.flat
+        b, e = f.module_ranges[0]
+        hyper, clip = self._hyper(grad_scale), self.max_grad_norm > 0
+        norms, out = [], None
+        if clip or self.skip_nonfinite:
+            out = K.grad_norm(f.grad, [(b, e)], grad_scale, self.max_grad_norm)
+            norms.append(out[0:1])
+            if self.skip_nonfinite and e < f.numel:
+                norms.append(K.grad_norm(f.grad, [(e, f.numel)], grad_scale, 0.0)[0:1])
+        flags = (K.OPTIM_DECOUPLED if self.decoupled else 0) | (K.OPTIM_SKIP_NONFINITE if self.skip_nonfinite else 0)
+        K.optim_prepare(self.state, hyper, self.lr, norms=norms, coef=out[1:2] if clip else None, flags=flags)
+        ema = self.ema
+        K.optim_apply(f.flat[b:e], f.grad[b:e], self.exp_avg[b:e], self.exp_avg_sq[b:e], None if ema is None else ema[b:e],
+                      hyper, flags | (K.OPTIM_CLIP if clip else 0), self.state)
+        if e < f.numel:   # the extra modules: never clipped
+            K.optim_apply(f.flat[e:], f.grad[e:], self.exp_avg[e:], self.exp_avg_sq[e:], None if ema is None else ema[e:],
+                          hyper, flags, self.state)
+        return None if out is None else out[0]
+
+    # ---------------------------------------------------------------- step state and checkpoints
+    def _read_state(self):
+        """(step, skipped, beta1^step, beta2^step): one device-to-host copy on the device path, host values otherwise (the
+        powers then by `step` fp64 multiplications, the form the device keeps)."""
+        from .kernels import optim_state_block, read_optim_state
+        if self.on_device:
+            s = read_optim_state(self.state)
+        else:
+            s = read_optim_state(optim_state_block(self.step_count, self._skipped, *self.betas))
+        return s['step'], s['skipped'], s['beta1_pow'], s['beta2_pow']
+
+    def step_number(self):
+        """Applied steps so far (one device-to-host copy on the device path)."""
+        return self._read_state()[0]
+
+    def skipped_steps(self):
+        """Steps skipped for a non-finite gradient norm so far (one device-to-host copy on the device path)."""
+        return self._read_state()[1]
+
+    def _view(self, buf, p):
+        off = p.data.storage_offset()   # the parameter is a view into flat.flat; every buffer here has its layout
+        return buf[off:off + p.numel()].view_as(p)
+
+    def state_dict(self):
+        """torch.optim.Adam's layout: group 0 = the model's parameters in model.parameters() order, one further group per extra
+        module (how the reference adds the loss learner, train.py:46); per parameter `step`, `exp_avg`, `exp_avg_sq` (copies).
+        torch.optim.Adam(model.parameters(), ...) [+ add_param_group per extra module] loads it and this class loads Adam's.
+        Our own extras sit under the top-level key 'twog' (torch ignores it): the exact step, the skipped steps, the two fp64
+        powers and, with ema_decay, the averaged weights per parameter."""
+        step, skipped, p1, p2 = self._read_state()
+        lr = float(self.lr.detach().cpu()) if torch.is_tensor(self.lr) else self.lr
+        state, groups, ema, i = {}, [], {}, 0
+        for g in self.flat.named_groups:
+            ids = []
+            for _name, p in g:
+                state[i] = dict(step=torch.tensor(float(step)), exp_avg=self._view(self.exp_avg, p).detach().clone(),
+                                exp_avg_sq=self._view(self.exp_avg_sq, p).detach().clone())
+                if self.ema is not None:
+                    ema[i] = self._view(self.ema, p).detach().clone()
+                ids.append(i)
+                i += 1
+            groups.append(dict(lr=lr, betas=tuple(self.betas), eps=self.eps, weight_decay=self.wd, amsgrad=False, maximize=False,
+                               foreach=None, capturable=False, differentiable=False, fused=None,
+                               decoupled_weight_decay=self.decoupled, params=ids))
+        twog = dict(step=int(step), skipped=int(skipped), beta1_pow=p1, beta2_pow=p2)
+        if self.ema is not None:
+            twog['ema'] = ema
+        return dict(state=state, param_groups=groups, twog=twog)
+
+    def load_state_dict(self, sd):
+        """Loads state_dict()'s result or a torch.optim.Adam state of the same parameters in the same groups. lr, betas, eps and
+        weight_decay come from the checkpoint (equal in every group: per-group values are out of scope). A state without 'twog'
+        (torch's own) gives skipped = 0 and powers rebuilt by `step` fp64 multiplications; parameters torch kept no state for
+        (never given a gradient) get zero moments. Averaged weights are taken when both sides have them; otherwise they stay."""
+        groups, named = sd['param_groups'], self.flat.named_groups
+        if [len(g['params']) for g in groups] != [len(g) for g in named]:
+            raise ValueError(f'the checkpoint has parameter groups of {[len(g["params"]) for g in groups]} parameters, this '
+                             f'optimizer {[len(g) for g in named]}')
+        keys = ('lr', 'betas', 'eps', 'weight_decay')
+        if any(tuple(g[k]) != tuple(groups[0][k]) if k == 'betas' else g[k] != groups[0][k] for g in groups for k in keys):
+            raise ValueError('learning rate, betas, eps or weight decay differ between the groups: out of scope here')
+        if any(g.get('amsgrad') or g.get('maximize') for g in groups):
+            raise ValueError('amsgrad / maximize are out of scope here')
+        if bool(groups[0].get('decoupled_weight_decay', False)) != self.decoupled:
+            raise ValueError('decoupled_weight_decay of the checkpoint and of this optimizer differ')
+        twog, steps = sd.get('twog'), set()
+        with torch.no_grad():
+            for g_sd, g in zip(groups, named):
+                for i, (_name, p) in zip(g_sd['params'], g):
+                    st = sd['state'].get(i)
+                    for key, buf in (('exp_avg', self.exp_avg), ('exp_avg_sq', self.exp_avg_sq)):
+                        if st is None:
+                            self._view(buf, p).zero_()
+                        else:
+                            self._view(buf, p).copy_(st[key])
+                    if st is not None:
+                        steps.add(int(st['step']))
+                    if self.ema is not None and twog is not None and 'ema' in twog:
+                        self._view(self.ema, p).copy_(twog['ema'][i])
+            lr = float(groups[0]['lr'])
+            if torch.is_tensor(self.lr):
+                self.lr.fill_(lr)
+            else:
+                self.lr = lr
+        if len(steps) > 1:
+            raise ValueError(f'the parameters of the checkpoint are at different steps {sorted(steps)}: out of scope here')
+        self.betas, self.eps, self.wd = tuple(groups[0]['betas']), groups[0]['eps'], groups[0]['weight_decay']
+        step = twog['step'] if twog is not None else (steps.pop() if steps else 0)
+        powers = (twog['beta1_pow'], twog['beta2_pow']) if twog is not None else None
+        self.step_count, self._skipped = int(step), int(twog['skipped']) if twog is not None else 0
+        if self.on_device:
+            self.state = get_kernels().new_optim_state(self.step_count, self._skipped, self.betas[0], self.betas[1],
+                                                       self.flat.flat.device, powers=powers)
+
+    # ---------------------------------------------------------------- averaged weights
+    def ema_state_dict(self):
+        """name -> averaged weights (copies) of the model's parameters, for model.load_state_dict(..., strict=False). BatchNorm
+        statistics are buffers, not parameters: they are not averaged."""
+        if self.ema is None:
+            raise RuntimeError('no averaged weights: construct with ema_decay')
+        return {name: self._view(self.ema, p).detach().clone() for name, p in self.flat.named_groups[0]}
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """Inside the context the parameter buffer holds the averaged weights and the EMA buffer the parameters (exchanged with
+        the library's copy launches through a temporary), so that an evaluation runs on the averaged weights in place; leaving
+        it exchanges them back, bit for bit. step() inside raises."""
+        if self.ema is None:
+            raise RuntimeError('no averaged weights: construct with ema_decay')
+        if self._swapped:
+            raise RuntimeError('swap_ema() is already active')
+        self._exchange()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._exchange()
+            self._swapped = False
+
+    def _exchange(self):
+        K, a, b = get_kernels(), self.flat.flat, self.ema
+        tmp = torch.empty_like(a)
+        for src, dst in ((a, tmp), (b, a), (tmp, b)):   # three launches: each reads what the one before wrote
+            K.copy_blocks([(src, dst)])
 
 
 def _ranks_share_a_device(group, world):

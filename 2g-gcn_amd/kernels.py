@@ -73,6 +73,40 @@ def _as_int64(v):
     return v - 2 ** 64 if v >= 2 ** 63 else v
 
 
+def _f32(v):
+    return C.c_float(float(v)).value   # the value the C ABI (float) receives
+
+
+def optim_state_block(step, skipped, beta1, beta2, powers=None):
+    """twog_optim_state_t (include/twog_gcn.h) at step `step` as a uint8 [64] CPU tensor. powers = (beta1^step, beta2^step) as
+    stored by a checkpoint; None rebuilds them the way the device keeps them: `step` fp64 multiplications by the fp32 beta."""
+    s = L.OptimState()
+    s.step, s.skipped = int(step), int(skipped)
+    if powers is None:
+        b1, b2, p1, p2 = _f32(beta1), _f32(beta2), 1.0, 1.0
+        for _ in range(int(step)):
+            p1, p2 = p1 * b1, p2 * b2
+        powers = (p1, p2)
+    s.beta1_pow, s.beta2_pow = float(powers[0]), float(powers[1])
+    s.clip_k, s.decay_mul, s.apply = 1.0, 1.0, 1
+    return torch.frombuffer(bytearray(bytes(s)), dtype=torch.uint8).clone()
+
+
+def read_optim_state(state):
+    """The fields of a state block as a dict (ONE device-to-host copy of 64 bytes)."""
+    s = L.OptimState.from_buffer_copy(state.cpu().numpy().tobytes())
+    return {name: getattr(s, name) for name, _ in L.OptimState._fields_ if name != 'reserved_'}
+
+
+def optim_hyper(h):
+    return L.OptimHyper(h['beta1'], h['beta2'], h['eps'], h['weight_decay'], h.get('grad_scale', 1.0), h.get('ema_decay') or 0.0)
+
+
+def _check_optim_state(state):
+    assert state.dtype == torch.uint8 and state.numel() == C.sizeof(L.OptimState) and state.is_contiguous()
+    assert state.data_ptr() % 8 == 0
+
+
 class _DeferredWord:
     """The error word of a persistent launch on its way to pinned host memory behind the launch: an entry of PERSIST.pending.
     Host slot and event come from a ring per device, so that a training step allocates nothing."""
@@ -1353,6 +1387,39 @@ class HipKernels:
         self._check(self.lib.twog_adam_step_coef(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(),
                                                  exp_avg_sq.data_ptr(), n, lr, beta1, beta2, eps, weight_decay, step,
                                                  grad_scale, coef.data_ptr(), self._stream()), 'twog_adam_step_coef')
+
+    # ---------------------------------------------------------------- Adam with its step state on the device
+    STREAM_OPTIM = 13   # TWOG_STREAM_OPTIM (twog_stream_grid; 12 is not assigned)
+    OPTIM_CLIP, OPTIM_DECOUPLED, OPTIM_SKIP_NONFINITE = L.OPTIM_CLIP, L.OPTIM_DECOUPLED, L.OPTIM_SKIP_NONFINITE
+
+    def new_optim_state(self, step, skipped, beta1, beta2, device, powers=None):
+        """The 64-byte twog_optim_state_t as a uint8 [64] tensor on `device` (optim_state_block: the powers by `step` fp64
+        multiplications on the host unless given)."""
+        return optim_state_block(step, skipped, beta1, beta2, powers).to(device)
+
+    def optim_prepare(self, state, hyper, lr, norms=(), coef=None, flags=0):
+        """twog_optim_prepare: advances the state block by one step, or counts a skipped one. hyper: dict(beta1, beta2, eps,
+        weight_decay, grad_scale, ema_decay); lr: a float or a one-element fp32 device tensor (read by the launch); norms: up to two
+        one-element fp32 device tensors (twog_grad_norm's out[0:1]); coef: the clip coefficient (out[1:2]) or None."""
+        _check_optim_state(state)
+        lr_t = lr if torch.is_tensor(lr) else None
+        for t in list(norms) + [coef, lr_t]:
+            assert t is None or (t.dtype == torch.float32 and t.numel() >= 1 and t.device == state.device)
+        arr = (C.c_void_p * 2)(*[t.data_ptr() for t in norms]) if len(norms) <= 2 else None
+        self._check(self.lib.twog_optim_prepare(state.data_ptr(), C.byref(optim_hyper(hyper)), 0.0 if lr_t is not None else float(lr),
+                                                _ptr(lr_t), arr, len(norms), _ptr(coef), int(flags), self._stream()),
+                    'twog_optim_prepare')
+
+    def optim_apply(self, param, grad, exp_avg, exp_avg_sq, ema, hyper, flags, state):
+        """twog_optim_apply over param.numel() elements (contiguous fp32 views at the same offset of equally aligned buffers);
+        ema: the averaged weights or None. Writes nothing when the prepared step is a skipped one."""
+        _check_optim_state(state)
+        n = param.numel()
+        for t in (param, grad, exp_avg, exp_avg_sq, ema):
+            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n and t.device == state.device)
+        self._check(self.lib.twog_optim_apply(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                                              _ptr(ema), n, C.byref(optim_hyper(hyper)), int(flags), state.data_ptr(),
+                                              self._stream()), 'twog_optim_apply')
 
     @staticmethod
     def _mtl_spec(kinds):

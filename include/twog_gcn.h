@@ -847,6 +847,10 @@ int twog_adam_step(float* param, const float* grad, float* exp_avg, float* exp_a
 #define TWOG_STREAM_COPY_BLOCKS 9   /* twog_copy_blocks */
 #define TWOG_STREAM_FILL_ZERO 10    /* twog_fill_zero */
 #define TWOG_STREAM_REORDER 11      /* twog_reorder_fwd / twog_reorder_bwd: column chunks */
+/* (12 is not assigned: the launch-free plan's test keeps it as its example of an unknown id)
+ * twog_optim_apply: a _VEC kernel over the 16-byte aligned body of the range. The body starts up to 3 elements into the range,
+ * so with pointers that are not 16-byte aligned the slack is 6 instead of 3. */
+#define TWOG_STREAM_OPTIM 13
 int twog_stream_grid(int kernel, int64_t work, int64_t cols);
 
 /* Adjacency attention of Geo_gcn (compute_similarity + s.matmul(x), pyrutils/torch/models_gcn.py:86-100, :30-34) on the
@@ -1033,6 +1037,55 @@ typedef struct {
 int twog_mtl_weight_fwd(const twog_mtl_t* spec, const float* losses, const float* log_sds, float* out, void* stream);
 int twog_mtl_weight_bwd(const twog_mtl_t* spec, const float* losses, const float* log_sds, const float* dout, float* dlosses,
                         float* dlog_sds, int accumulate, void* stream);
+
+/* ===============================================================================================================
+ * Adam with its step state on the device (csrc/train_opts.hip): the step number, the bias corrections, the clip coefficient
+ * and the decision to apply or skip the step live in one 64-byte block and are advanced by a launch, so that a checkpointable,
+ * NaN-skipping, decoupled-decay (AdamW), weight-averaging (EMA) step reads nothing on the host. fl() = one fp32 rounding;
+ * nothing is contracted into a fused multiply-add, so tests/optim_state_ref.py reproduces both launches bit for bit in numpy.
+ *
+ * twog_optim_prepare: one workgroup, one active lane, plain stores. norms: HOST array of n_norms (0, 1 or 2) DEVICE pointers,
+ *   each to an fp32 norm written by twog_grad_norm; lr_ptr / coef: device fp32 scalars or NULL.
+ *     finite = every *norms[j] is finite;   apply = !((flags & SKIP_NONFINITE) && !finite)
+ *     not apply:  skipped += 1, apply = 0, nothing else changes
+ *     apply:      step += 1;  beta1_pow *= (double)beta1;  beta2_pow *= (double)beta2       (fp64 running products, no pow)
+ *                 lr = lr_ptr ? *lr_ptr : lr
+ *                 step_size = fl(lr / fl32(1.0 - beta1_pow))           (fp64 subtraction, rounded to fp32, fp32 division)
+ *                 bc2s      = fl32(sqrt(1.0 - beta2_pow))              (fp64 subtraction and square root, rounded to fp32)
+ *                 clip_k    = (coef && *coef < 1) ? *coef : 1          (a NaN coefficient does not clip: twog_adam_step_coef's rule)
+ *                 decay_mul = fl(1 - fl(lr * weight_decay))
+ * twog_optim_apply: the element-wise update of n elements; every thread reads the block first and returns when apply == 0
+ *   (then no buffer is written). Per element, with b1 / b2 / eps / wd / d = beta1 / beta2 / eps / weight_decay / ema_decay:
+ *     g  = fl(grad * grad_scale);            if (flags & CLIP) g = fl(g * clip_k)
+ *     p0 = p
+ *     if (flags & DECOUPLED)  p0 = fl(p * decay_mul)
+ *     else if (wd != 0)       g  = fl(g + fl(wd * p))
+ *     m' = fl(fl(b1 * m) + fl(fl(1 - b1) * g))
+ *     v' = fl(fl(b2 * v) + fl(fl(1 - b2) * fl(g * g)))
+ *     p' = fl(p0 - fl(fl(step_size * m') / fl(fl(sqrt(v') / bc2s) + eps)))               (adam_kernel's order of divisions)
+ *     if (ema) ema' = fl(fl(d * ema) + fl(fl(1 - d) * p'))
+ *   ema may be NULL. The pointers must be 4-byte aligned and congruent modulo 16 (the same sub-range of equally aligned buffers:
+ *   a sub-range is stepped by offsetting all of them): up to 3 elements in front of the first 16-byte boundary and up to 3
+ *   behind the last are taken one by one, the body in 16-byte loads and stores on the capped grid of TWOG_STREAM_OPTIM.
+ * Both return -2 before any launch for NULL state / hyper / param / grad / exp_avg / exp_avg_sq, n < 0, n_norms outside 0..2
+ * or a NULL among norms, an ema_decay outside (0, 1) when ema is given, and pointers that are not congruent; n == 0 launches
+ * nothing.
+ * =============================================================================================================== */
+typedef struct {
+    int64_t step, skipped;         /* applied steps so far, skipped steps so far */
+    double beta1_pow, beta2_pow;   /* beta^step (1.0 at step 0) */
+    float lr, step_size, bc2s, clip_k, decay_mul;   /* the scalars of the CURRENT step, written by twog_optim_prepare */
+    int32_t apply;
+    int64_t reserved_;             /* 64 bytes */
+} twog_optim_state_t;
+typedef struct {
+    float beta1, beta2, eps, weight_decay, grad_scale, ema_decay;
+} twog_optim_hyper_t;
+enum { TWOG_OPTIM_CLIP = 1, TWOG_OPTIM_DECOUPLED = 2, TWOG_OPTIM_SKIP_NONFINITE = 4 };
+int twog_optim_prepare(twog_optim_state_t* state, const twog_optim_hyper_t* hyper, float lr, const float* lr_ptr,
+                       const float* const* norms, int n_norms, const float* coef, int flags, void* stream);
+int twog_optim_apply(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                     const twog_optim_hyper_t* hyper, int flags, const twog_optim_state_t* state, void* stream);
 
 /* ===============================================================================================================
  * Inference post-processing on the device.
