@@ -232,6 +232,18 @@ class OptimHyper(C.Structure):  # twog_optim_hyper_t
     _fields_ = [('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float), ('weight_decay', C.c_float),
                 ('grad_scale', C.c_float), ('ema_decay', C.c_float)]
 
+AUGMENT_TAG_GEOMETRY, AUGMENT_TAG_HUMAN, AUGMENT_TAG_OBJECT = 0x47454F4D, 0x48554D4E, 0x4F424A53   # TWOG_AUGMENT_TAG_*
+
+
+class Augment(C.Structure):  # twog_augment_t
+    _fields_ = [('x_human', C.c_void_p), ('x_objects', C.c_void_p), ('clip_ids', C.c_void_p), ('steps', C.c_void_p),
+                ('objects_mask', C.c_void_p), ('state', C.c_void_p), ('params_out', C.c_void_p),
+                ('bs', C.c_int32), ('T', C.c_int32), ('H', C.c_int32), ('O', C.c_int32), ('F_h', C.c_int32),
+                ('F_o', C.c_int32), ('N', C.c_int32), ('geo_offset', C.c_int32),
+                ('tan_half_max', C.c_float), ('scale_max', C.c_float), ('shift_max', C.c_float), ('cx', C.c_float),
+                ('cy', C.c_float), ('amp', C.c_float), ('keep_scale', C.c_float), ('drop_threshold', C.c_uint32)]
+
+
 # name -> (argtypes) ; every function returns int except twog_version
 _I, _L, _F, _P = C.c_int, C.c_int64, C.c_float, C.c_void_p
 SIGNATURES = {
@@ -311,6 +323,8 @@ SIGNATURES = {
     'twog_gate_fwd': [C.POINTER(Gate), _P],
     'twog_gate_bwd': [C.POINTER(Gate), _P, _P, _P, _P, _P],
     'twog_gumbel_noise_fill': [_P, _I, _I, _I, C.c_uint32, _P, _P, _P],
+    'twog_augment_inputs': [C.POINTER(Augment), _P],
+    'twog_augment_grid': [_L],
     'twog_rank1_update': [Rows, _P, _P, _I, _I, _P],
     'twog_colsum': [Rows, _P, _I, _I, _P, _I, _P, _I, _P],
     'twog_colsum_n_partial_floats': [C.POINTER(ColSum), _I],

@@ -539,11 +539,20 @@ class DevicePrefetcher:
     of HBM3E) and batches become device-side index selections: no per-step PCIe traffic at all.
 
     Iterating yields exactly what ``fetch(batch, device=...)`` yields for every batch of ``loader``, in loader order.
-    On a CPU device it degenerates to that plain loop (used by the CPU tests of the host logic)."""
+    On a CPU device it degenerates to that plain loop (used by the CPU tests of the host logic).
 
-    def __init__(self, loader, fetch, device, resident: bool = False, **fetch_kwargs):
+    ``augment``: an ``augment.InputAugmentation``. Every batch handed over has then been augmented in place on the consumer's
+    stream (the batches of both routes are fresh copies), with the batch's data-set indices as clip ids, and a full pass ends
+    with ``augment.next_epoch()``. It needs a route that knows those indices: the resident one, or a ``TensorDataset`` under a
+    batch sampler without the trimming collate; anything else raises ``TypeError`` here. ``None`` changes nothing."""
+
+    def __init__(self, loader, fetch, device, resident: bool = False, augment=None, **fetch_kwargs):
         self.loader, self.fetch, self.device, self.kw = loader, fetch, torch.device(device), fetch_kwargs
         self.on_gpu = self.device.type == 'cuda'
+        self.augment = augment
+        if augment is not None and not resident and not self._indexed():
+            raise TypeError('augment needs the clips\' data-set indices: resident=True, or a TensorDataset under a batch '
+                            'sampler without the length-trimming collate')
         self.copy_stream = torch.cuda.Stream(self.device) if self.on_gpu else None
         self._slots = [{}, {}]  # pinned staging buffers of the two in-flight batches, keyed by tuple position
         self._slot_events = [None, None]
@@ -570,16 +579,25 @@ class DevicePrefetcher:
     def _host_batches(self):
         """Host-side batches. For a TensorDataset the rows of a batch are gathered straight into the pinned staging
         slot (one host copy; DataLoader's collate + pin would make two); otherwise the loader's own batches are
-        copied into the slot."""
+        copied into the slot. With an augmenter the batch's data-set indices ride along as one more (int64) entry at the
+        end of the list, staged like the others; `_stage` takes it off again."""
         ds = self.loader.dataset
-        if self.on_gpu and isinstance(ds, TensorDataset) and self.loader.batch_sampler is not None and \
-                self.loader.collate_fn is not _trim_collate:
+        if self.on_gpu and self._indexed():
             for k, idx in enumerate(self._batch_indices()):
                 slot = k & 1
                 self._wait_slot_free(slot)
                 idx = torch.as_tensor(idx, dtype=torch.int64)
-                yield [torch.index_select(t, 0, idx, out=self._slot_view(slot, i, (len(idx),) + tuple(t.shape[1:]), t.dtype))
-                       for i, t in enumerate(ds.tensors)]
+                batch = [torch.index_select(t, 0, idx, out=self._slot_view(slot, i, (len(idx),) + tuple(t.shape[1:]), t.dtype))
+                         for i, t in enumerate(ds.tensors)]
+                if self.augment is not None:
+                    ids = self._slot_view(slot, 'clip_ids', (len(idx),), torch.int64)
+                    ids.copy_(idx)
+                    batch.append(ids)
+                yield batch
+        elif self.augment is not None:   # (a CPU device: the same gather without the staging slots)
+            for idx in self._batch_indices():
+                idx = torch.as_tensor(idx, dtype=torch.int64)
+                yield [t.index_select(0, idx) for t in ds.tensors] + [idx]
         else:
             for k, batch in enumerate(self.loader):
                 if self.on_gpu:
@@ -608,11 +626,19 @@ class DevicePrefetcher:
         if ev is not None:
             ev.synchronize()
 
+    def _indexed(self):
+        """The staged route that gathers a TensorDataset's rows itself and so knows every batch's data-set indices."""
+        return isinstance(self.loader.dataset, TensorDataset) and self.loader.batch_sampler is not None and \
+            self.loader.collate_fn is not _trim_collate
+
     def _stage(self, batch, k):
+        ids = batch.pop() if self.augment is not None else None   # (see _host_batches)
         if not self.on_gpu:
-            return self.fetch(batch, device=self.device, **self.kw), None
+            return self.fetch(batch, device=self.device, **self.kw), None, ids
         with torch.cuda.stream(self.copy_stream):
             out = self.fetch(batch, device=self.device, non_blocking=True, **self.kw)
+            if ids is not None:
+                ids = ids.to(self.device, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
         self._slot_events[k & 1] = ev
@@ -623,10 +649,10 @@ class DevicePrefetcher:
         out = type(out)(type(group)(t.clone() if (isinstance(t, torch.Tensor) and not t.is_cuda and
                                                    t.untyped_storage().data_ptr() in slots) else t for t in group)
                         if isinstance(group, (list, tuple)) else group for group in out)
-        return out, ev
+        return out, ev, ids
 
     def _hand_over(self, staged):
-        out, ev = staged
+        out, ev, ids = staged
         if ev is not None:
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(ev)
@@ -634,6 +660,10 @@ class DevicePrefetcher:
                 for t in group:
                     if isinstance(t, torch.Tensor) and t.is_cuda:
                         t.record_stream(cur)
+            if ids is not None:
+                ids.record_stream(cur)
+        if self.augment is not None:
+            self.augment(out[0], ids)   # behind the copy, on the consumer's stream
         return out
 
     def _resident_batches(self):
@@ -643,9 +673,17 @@ class DevicePrefetcher:
             batch = [t.index_select(0, idx) for t in ds.tensors]
             if self.loader.collate_fn is _trim_collate:   # length-bucketed loader: trim to the batch's longest clip
                 batch = trim_to_batch_length(batch)
-            yield self.fetch(batch, device=self.device, **self.kw)
+            out = self.fetch(batch, device=self.device, **self.kw)
+            if self.augment is not None:
+                self.augment(out[0], idx)
+            yield out
 
     def __iter__(self):
+        yield from self._batches()
+        if self.augment is not None:
+            self.augment.next_epoch()   # once per full pass, behind its last batch
+
+    def _batches(self):
         if self._resident is not None:
             yield from self._resident_batches()
             return

@@ -1057,6 +1057,49 @@ class HipKernels:
                                                     state.data_ptr(), _ptr(words), self._stream()), 'twog_gumbel_noise_fill')
         return noise
 
+    def augment_grid(self, work):
+        """Workgroups of the capped launches of augment_inputs for `work` workgroup-sized items: rows of the feature pass, groups
+        of 256 nodes of the geometry pass (twog_augment_grid: host arithmetic of the library, no GPU call)."""
+        g = self.lib.twog_augment_grid(int(work))
+        if g < 0:
+            raise RuntimeError(f'twog_augment_grid failed with code {g}')
+        return g
+
+    def augment_inputs(self, x_human, x_objects, clip_ids, state, opts, steps=None, objects_mask=None, params_out=None):
+        """In-place augmentation of a batch (twog_augment_inputs, where the arithmetic is stated): x_human (bs, T, H, F_h) whose
+        last 4 * opts['gcn_node'] channels are (x, y, vx, vy) nodes, x_objects (bs, T, O, F_o) or None, clip_ids int64 [bs],
+        state int64 [seed, epoch] on the device. opts: tan_half_max, scale_max, shift_max, cx, cy, amp, keep_scale,
+        drop_threshold, gcn_node (augment.InputAugmentation makes them). Nothing is read or written on the host; neutral options
+        launch nothing. Tensors that are not contiguous raise: the write is in place, a silent copy would lose it."""
+        dev = x_human.device
+        for name, t, dtype in (('x_human', x_human, torch.float32), ('x_objects', x_objects, torch.float32),
+                               ('clip_ids', clip_ids, torch.int64), ('state', state, torch.int64), ('steps', steps, torch.float32),
+                               ('objects_mask', objects_mask, torch.float32), ('params_out', params_out, torch.float32)):
+            if t is None:
+                continue
+            if t.dtype != dtype or t.device != dev:
+                raise TypeError(f'{name}: {t.dtype} on {t.device}, expected {dtype} on {dev}')
+            if not t.is_contiguous():
+                raise ValueError(f'{name} is not contiguous: augment_inputs writes in place and does not copy')
+        if x_human.dim() != 4 or (x_objects is not None and (x_objects.dim() != 4 or x_objects.shape[:2] != x_human.shape[:2])):
+            raise ValueError(f'x_human {tuple(x_human.shape)} / x_objects {None if x_objects is None else tuple(x_objects.shape)}')
+        bs, T, H, F_h = x_human.shape
+        O, F_o = (x_objects.shape[2], x_objects.shape[3]) if x_objects is not None else (0, 0)
+        assert clip_ids.numel() == bs and state.numel() == 2
+        assert steps is None or steps.numel() == bs
+        assert objects_mask is None or objects_mask.numel() == bs * O
+        assert params_out is None or params_out.numel() == 4 * bs
+        a = L.Augment()
+        a.x_human, a.x_objects, a.clip_ids, a.steps = x_human.data_ptr(), _ptr(x_objects), clip_ids.data_ptr(), _ptr(steps)
+        a.objects_mask, a.state, a.params_out = _ptr(objects_mask), state.data_ptr(), _ptr(params_out)
+        a.bs, a.T, a.H, a.O, a.F_h, a.F_o = bs, T, H, O, F_h, F_o
+        a.N, a.geo_offset = int(opts['gcn_node']), F_h - 4 * int(opts['gcn_node'])
+        a.tan_half_max, a.scale_max, a.shift_max = opts['tan_half_max'], opts['scale_max'], opts['shift_max']
+        a.cx, a.cy, a.amp, a.keep_scale, a.drop_threshold = opts['cx'], opts['cy'], opts['amp'], opts['keep_scale'], \
+            int(opts['drop_threshold'])
+        self._check(self.lib.twog_augment_inputs(C.byref(a), self._stream()), 'twog_augment_inputs')
+        return x_human, x_objects
+
     def rank1_update(self, dst, s, v):
         """dst[r][c] += s[r] * v[c] on a row-strided view."""
         self._check(self.lib.twog_rank1_update(rows_of(dst), s.data_ptr(), v.data_ptr(), n_rows(dst), dst.shape[-1],

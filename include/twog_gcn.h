@@ -703,6 +703,67 @@ int twog_gate_bwd(const twog_gate_t* g, const float* d_hard, const float* d_soft
  * T * noise_entities * bs >= 2^31. */
 int twog_gumbel_noise_fill(float* noise, int T, int noise_entities, int bs, uint32_t clip_offset, int64_t* state,
                            uint32_t* words_or_null, void* stream);
+/* twog_augment_inputs: random augmentation of a batch's inputs, in place, on the device. No counterpart in the reference
+ * trainer (its loaders hand the stored features over unchanged); SGN, the model Geo_gcn is taken from, rotates its skeletons
+ * at random in its loader. Two parts, each skipped when its options are neutral:
+ *   geometry  one similarity transform per clip of the (x, y, vx, vy) nodes in the last 4 * N floats of every x_human row
+ *             (the layout data_loading._pos_vel writes for all three data sets);
+ *   features  uniform jitter and dropout of the first geo_offset channels of the human rows and of all F_o channels of the
+ *             object rows.
+ * A clip's draw is a pure function of (seed, epoch, clip id, element) and of nothing else -- not of the batch's composition or
+ * size, the rank that holds the clip or the launch geometry -- through Philox4x32-10 (constants and round: see
+ * twog_gumbel_noise_fill) keyed apart from the Gumbel noise and per part:
+ *   key     = (seed low, seed high ^ TAG),  TAG = TWOG_AUGMENT_TAG_GEOMETRY / _HUMAN / _OBJECT      -- seed  = state[0]
+ *   counter = (epoch low, epoch high, clip id, index)                                                -- epoch = state[1]
+ *   a word w becomes r = 2u - 1 with u = ((w >> 9) + 0.5f) * 2^-23: exact in fp32 (an odd numerator below 2^23), |r| < 1.
+ * Every operation below is one fp32 operation rounded once (no contraction, correctly rounded division, no transcendentals),
+ * so that a numpy restatement (tests/augment_ref.py) gives the same bits.
+ * Geometry: index 0, words -> r0..r3; the rotation is drawn through the tangent of the half angle:
+ *   t = tan_half_max * r0;  q = t * t;  c = (1 - q) / (1 + q);  s = (t + t) / (1 + q);  g = 1 + scale_max * r1;
+ *   a = g * c;  b = g * s;  tx = shift_max * r2;  ty = shift_max * r3;
+ * for every human row, every frame t < steps[b] and every node with x != 0 or y != 0 (a node at exactly (0, 0) is a missing
+ * object or a padded frame and stays zero), with dx = x - cx, dy = y - cy:
+ *   x' = ((a * dx - b * dy) + cx) + tx;   y' = ((b * dx + a * dy) + cy) + ty;   vx' = a * vx - b * vy;   vy' = b * vx + a * vy
+ * (velocities take the linear part only, so v = (p_next - p_cur) * 100 stays true; all H human rows carry the same context
+ * block and get the same transform). The distance tensors of the batch are NOT touched: they are normalised by the image size
+ * per axis, so no similarity transform maps onto them.
+ * Features: frames t < steps[b] only, objects with objects_mask > 0 only. Element e = (t * E + entity) * F + channel is numbered
+ * over the whole row block of the clip (E = H, F = F_h, the geometry tail included / E = O, F = F_o), whatever the access
+ * width; it uses index = e >> 1 and the words 2 * (e & 1) (dropout) and 2 * (e & 1) + 1 (jitter):
+ *   keep = (w_drop >> 8) >= drop_threshold;   x' = keep ? (x + amp * r) * keep_scale : 0
+ * with drop_threshold = round(p * 2^24) < 2^24, amp = noise_std * sqrt(3) (uniform jitter of the variance the option names)
+ * and keep_scale = 1 / (1 - p) made by the caller in fp64 and passed as fp32.
+ * Neutral options issue nothing: tan_half_max = scale_max = shift_max = 0 -> no geometry launch; amp = 0 and
+ * drop_threshold = 0 -> no feature launch. At most three launches: the parameters (only with params_out), geometry, features.
+ * state: two DEVICE int64 words [seed, epoch], read by the kernels and never by the host (a captured launch draws anew after the
+ * epoch has moved on); clip_ids: DEVICE int64 [bs], 0 <= id < 2^32 (the low 32 bits are the counter word).
+ * Returns -1 for a NULL descriptor, a negative size, geo_offset + 4 * N != F_h, drop_threshold >= 2^24, a pointer that is not
+ * aligned to its element (4 bytes; 8 for clip_ids and state), a missing clip_ids / state / x_human or 2^62 elements and more;
+ * -2 for a clip whose row block T * H * F_h or T * O * F_o exceeds 2^33 elements (e >> 1 is a 32-bit counter word).
+ * The 16-byte form of the feature pass serves a tensor whose base is 16-byte aligned and whose F (and geo_offset) is a multiple
+ * of 4, the scalar form any other. */
+#define TWOG_AUGMENT_TAG_GEOMETRY 0x47454F4Du   /* 'GEOM' */
+#define TWOG_AUGMENT_TAG_HUMAN    0x48554D4Eu   /* 'HUMN' */
+#define TWOG_AUGMENT_TAG_OBJECT   0x4F424A53u   /* 'OBJS' */
+typedef struct {
+    float* x_human;              /* [bs][T][H][F_h], contiguous, written in place */
+    float* x_objects;            /* [bs][T][O][F_o], contiguous, written in place; NULL = no objects */
+    const int64_t* clip_ids;     /* [bs] */
+    const float* steps;          /* [bs] frames per clip (the loader's steps_per_example) or NULL = T */
+    const float* objects_mask;   /* [bs][O] or NULL = all present */
+    const int64_t* state;        /* [2] = (seed, epoch) */
+    float* params_out;           /* [bs][4] = (a, b, tx, ty) per clip or NULL: a test hook */
+    int32_t bs, T, H, O, F_h, F_o;
+    int32_t N, geo_offset;       /* nodes; F_h - 4 * N */
+    float tan_half_max, scale_max, shift_max, cx, cy;
+    float amp, keep_scale;
+    uint32_t drop_threshold;
+} twog_augment_t;
+int twog_augment_inputs(const twog_augment_t* a, void* stream);
+/* The grid of the two capped launches of twog_augment_inputs, host arithmetic only: workgroups for `work` workgroup-sized
+ * items = (clip, frame, entity) rows of the feature pass, which takes one row per workgroup and trip, or groups of 256 nodes of
+ * the geometry pass. A workgroup makes a second trip exactly when work exceeds the answer. -2 for negative work. */
+int twog_augment_grid(int64_t work);
 /* dst[r][c] += s[r] * v[c]  (gate input gradient, one call per column block) */
 int twog_rank1_update(twog_rows_t dst, const float* s, const float* v, int rows, int cols, void* stream);
 /* out[c] (+)= sum_r rowscale[r] * x[r][c] (rowscale NULL => 1): bias gradients and gate weight gradients.
