@@ -876,7 +876,7 @@ extern "C" int twog_attn_fwd(const twog_attn_t* a, int n, void* stream) {
     if (lds > LDS_LIMIT) return -3;
     g.staged = staged ? 1 : 0;
     // throughput regime with at most ten entities per instance: column-parallel Gram, no feature rows in LDS
-    static const int cols_on = getenv("TWOG_ATTN_COLUMNS") ? atoi(getenv("TWOG_ATTN_COLUMNS")) : 1;
+    static const int cols_on = twog_env_int("TWOG_ATTN_COLUMNS", 1);
     bool columns = !staged && cols_on;
     for (int i = 0; i < n; ++i) columns = columns && (a[i].H + a[i].O) <= 10 && (a[i].D & 1) == 0;
     g.columns = columns ? 1 : 0;
@@ -891,7 +891,7 @@ extern "C" int twog_attn_fwd(const twog_attn_t* a, int n, void* stream) {
         // 256 threads: the butterfly costs the same per wave whatever the workgroup size, and six small workgroups per
         // CU overlap their phases better than three large ones (measured at the BASELINE shape: 0.262 ms with 512
         // threads, 0.231 with 256, 0.250 with 128; the row-parallel kernel: 0.283)
-        static const int cols_threads = getenv("TWOG_ATTN_COLS_THREADS") ? atoi(getenv("TWOG_ATTN_COLS_THREADS")) : 256;
+        static const int cols_threads = twog_env_int("TWOG_ATTN_COLS_THREADS", 256);
         g_last_path = TWOG_ATTN_PATH_GRAM_COLUMNS | cols_threads << TWOG_ATTN_PATH_THREADS_SHIFT;
         hipLaunchKernelGGL(attn_fwd_cols_kernel, dim3(maxinst, n, 1), dim3(cols_threads), lds, (hipStream_t)stream, g);
         TWOG_CHECK_LAUNCH();
@@ -923,11 +923,11 @@ extern "C" int twog_attn_bwd(const twog_attn_bwd_t* a, int n, void* stream) {
     }
     if (lds > LDS_LIMIT) return -3;
     g.staged = staged ? 1 : 0;
-    static const int wg_on = getenv("TWOG_ATTN_WAVE_GROUPS") ? atoi(getenv("TWOG_ATTN_WAVE_GROUPS")) : 1;
+    static const int wg_on = twog_env_int("TWOG_ATTN_WAVE_GROUPS", 1);
     g.wave_groups = wg_on;
     static std::atomic<uint32_t> lds_attr_done{0};
     twog_allow_dynamic_lds(attn_bwd_kernel, (int)LDS_LIMIT, lds_attr_done);
-    static const int cols_on = getenv("TWOG_ATTN_COLUMNS") ? atoi(getenv("TWOG_ATTN_COLUMNS")) : 1;
+    static const int cols_on = twog_env_int("TWOG_ATTN_COLUMNS", 1);
     bool columns = !staged && cols_on;
     for (int i = 0; i < n; ++i) columns = columns && a[i].f.H <= 2 && a[i].f.O <= 8 && (a[i].f.hidden & 1) == 0;
     if (columns) {

@@ -21,7 +21,7 @@ struct Vec<1> {
 };
 template <>
 struct Vec<4> {
-    typedef float T __attribute__((ext_vector_type(4)));
+    typedef f32x4 T;
     static __device__ __forceinline__ T zero() { return T{0.f, 0.f, 0.f, 0.f}; }
 };
 

@@ -224,14 +224,13 @@ extern "C" int twog_gate_bwd(const twog_gate_t* g, const float* d_hard, const fl
 // the same update with 16-byte accesses (cols % 4 == 0, 16-byte aligned rows): one thread per four columns of a row, the row's
 // scale read once, no 64-bit division per element; bit-identical (one fmaf per element)
 __global__ __launch_bounds__(256) void rank1_vec_kernel(twog_rows_t dst, const float* s, const float* v, int rows, int qpr) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
     const unsigned total = (unsigned)rows * (unsigned)qpr;
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         const unsigned r = i / (unsigned)qpr, q = i - r * (unsigned)qpr;
-        f4* d = reinterpret_cast<f4*>(twog_row_ptr(dst, (int)r) + 4 * q);
-        const f4 w = *reinterpret_cast<const f4*>(v + 4 * q);
+        f32x4* d = reinterpret_cast<f32x4*>(twog_row_ptr(dst, (int)r) + 4 * q);
+        const f32x4 w = *reinterpret_cast<const f32x4*>(v + 4 * q);
         const float sr = s[r];
-        f4 x = *d;
+        f32x4 x = *d;
 #pragma unroll
         for (int k = 0; k < 4; ++k) x[k] = fmaf(sr, w[k], x[k]);
         *d = x;

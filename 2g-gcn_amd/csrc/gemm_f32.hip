@@ -15,11 +15,7 @@
 // conflict-free ds_read_b32. Workgroup ids are remapped so that tiles sharing an A row-panel run on one XCD (its
 // L2 then serves the panel once). Tall reductions (dW = dY^T X, K = rows) use deterministic split-K: partial slabs in
 // the caller's workspace, summed in fixed order by a second kernel.
-#include <cstdlib>
-#include "twog_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));  // native vector: loads/stores stay in registers (SROA)
+#include "bf16x3.h"
 
 namespace {
 
@@ -393,18 +389,8 @@ __device__ __forceinline__ void gemm_mainloop(const twog_rows_t A, const twog_ro
 // X3: the 128x128 class on the bf16 matrix cores with fp32-exact operands (default; TWOG_GEMM_X3=0 selects the native
 // fp32-MFMA kernels above for every launch).
 //
-// Every fp32 operand element is split EXACTLY into three bf16 values, x = h + m + l: h = x truncated to its top 8
-// significant bits, m = (x - h) truncated, l = x - h - m (at most 8 significant bits are left: no rounding anywhere,
-// the 24-bit significand is three 8-bit chunks). A product a b = sum of nine chunk products; the six with weight
-// >= 2^-16 -- hh, hm, mh, mm, hl, lh -- run on v_mfma_f32_32x32x16_bf16 (bf16 x bf16 products are exact in the fp32
-// accumulator); the three dropped ones (ml, lm, ll) are <= 2^-21 |a b| in the worst case and ~2^-24 |a b| on average,
-// i.e. of the order of the rounding the fp32 accumulation applies to every partial sum anyway: measured against fp64
-// products the kernel's error equals the native fp32-MFMA kernel's on every shape of tools/gemm_x3_bench.py (0.7-2.5e-6
-// of the largest output for K = 512 ... 61 440); adding the two products m l and l m (exact to 2^-30) changes no digit of
-// that error and costs 15 % (TWOG_X3_PRODUCTS=8 at build time; the shipped default is 6). The truncating split makes the
-// dropped terms carry the sign of a b -- a bias towards zero of ~2^-24 |a b| per product, far below what the accumulate
-// itself does (see TTMP in compute()). Six bf16 MFMAs of 16 k-steps cost 192 cycles per
-// 32x32 block where the fp32 MFMA (32x32x2) needs 512: 2.67x the matrix rate for the same result to fp32 rounding.
+// The split of every fp32 operand element into three bf16 planes, the six products kept of the nine and the error they
+// leave are specified in bf16x3.h (split3 is the 4-wide form used here).
 //
 // Structure: 128x128 tile, 8 waves of 32x64, k-tiles of 16 (one bf16 MFMA k-step), the same branch-free 16-byte global
 // loads into registers (two stages); the split happens once per element on the way into LDS (5.5 VALU operations per
@@ -413,35 +399,6 @@ __device__ __forceinline__ void gemm_mainloop(const twog_rows_t A, const twog_ro
 // are swapped on every second group of 16 rows (the ds_read_b128 fragment reads and the ds_write_b64 stores are conflict-free); k-major operands ([k][row]) are stored as they come, [k][128 rows] rows of 256 bytes with 16-byte
 // chunks XOR-swizzled by the k row, and transposed on the way out by ds_read_b64_tr_b16 (each 16-lane group receives a
 // 4 k x 16 rows block column-major: the MFMA's k-contiguous fragment with no data movement of our own).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t pack_hi16(uint32_t lo, uint32_t hi) {   // {hi[31:16], lo[31:16]}
-    return __builtin_amdgcn_perm(hi, lo, 0x07060302);
-}
-// (Non-finite operands: NaN stays NaN; an operand of +-Inf gives NaN where an fp32 multiply would give +-Inf, because the
-// split subtracts Inf - Inf. The path's GEMM operands are activations, weights and gradients -- finite in any run that is
-// not already broken; the masked softmax's -inf lives inside the attention kernels, never in a GEMM operand.)
-// four consecutive fp32 values -> their three bf16 planes (4 x 2 bytes each), by truncation: h = the top 8 significant bits,
-// m = the top 8 of x - h, l = x - h - m. Exact (both subtractions are, and at most 8 significant bits are left for l), never
-// overflows (a rounding split -- v_cvt_pk_bf16_f32 -- measured 5-8 % slower with the same end-to-end error).
-__device__ __forceinline__ void split3(const f32x4 v, i32x2& ph, i32x2& pm, i32x2& pl) {
-    uint32_t x[4], r1[4], r2[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float f0 = v[i];   // (a scalar copy: __builtin_bit_cast applied to the vector ELEMENT v[i] reads element 0)
-        x[i] = __float_as_uint(f0);
-        const float f1 = f0 - __uint_as_float(x[i] & 0xffff0000u);
-        r1[i] = __float_as_uint(f1);
-        r2[i] = __float_as_uint(f1 - __uint_as_float(r1[i] & 0xffff0000u));
-    }
-    ph = i32x2{(int)pack_hi16(x[0], x[1]), (int)pack_hi16(x[2], x[3])};
-    pm = i32x2{(int)pack_hi16(r1[0], r1[1]), (int)pack_hi16(r1[2], r1[3])};
-    pl = i32x2{(int)pack_hi16(r2[0], r2[1]), (int)pack_hi16(r2[2], r2[3])};
-}
-
 // The reduced plane counts (twog_gemm_set_precision: 'high' = two planes, 'medium' = one; specification with the error
 // constants in tests/matmul_precision_ref.py). Both round to nearest even -- a truncating split would leave a bias towards
 // zero of ~2^-9 |a b| with one plane and ~2^-17 |a b| with two, no longer below the accumulate's -- through v_cvt_pk_bf16_f32, whose packed
@@ -1637,7 +1594,7 @@ static void launch_x3_128(const Group& g, bool akm, bool bkm, bool kg, dim3 grid
 
 // the bf16x3 128x128 class serves this group: aligned operands, whole 16-deep k-tiles (TWOG_GEMM_X3=0: native fp32 MFMA)
 static bool x3_128_ok(const Group& g) {
-    static const int x3_on = getenv("TWOG_GEMM_X3") ? atoi(getenv("TWOG_GEMM_X3")) : 1;
+    static const int x3_on = twog_env_int("TWOG_GEMM_X3", 1);
     bool ok = x3_on != 0 && (g.k_per_split % X3_BK) == 0;
     for (int i = 0; i < g.n; ++i) ok = ok && g.p[i].a_vec && g.p[i].b_vec && (g.p[i].K % X3_BK) == 0 && g.p[i].M >= 4 && g.p[i].N >= 4;
     return ok;
@@ -1653,7 +1610,7 @@ int launch(Group& g, int akm, int bkm, hipStream_t st) {
     if constexpr (BM == 128 && NT == 512) {
         // X3 (fp32-exact operands on the bf16 matrix cores, gemm_mainloop_x3): aligned operands, whole k-tiles, plain rows
         if (x3_128_ok(g)) {
-            static const int split_acc = getenv("TWOG_X3_DW_SPLIT_ACC") ? atoi(getenv("TWOG_X3_DW_SPLIT_ACC")) : 0;
+            static const int split_acc = twog_env_int("TWOG_X3_DW_SPLIT_ACC", 0);
             // opt-in reduced precision (twog_gemm_set_precision): two or one bf16 plane per operand; the split-accumulator TT
             // launches keep all six products
             const int np = (akm && bkm && split_acc) ? 3 : g_precision == TWOG_GEMM_PRECISION_HIGH ? 2 : g_precision == TWOG_GEMM_PRECISION_MEDIUM ? 1 : 3;
@@ -1726,12 +1683,12 @@ static void prepare_group(const twog_gemm_t* pr, int n, int a_kmajor, int b_kmaj
         if (pr[i].K > kmax) kmax = pr[i].K;
         if (pr[i].M < 96 || pr[i].N < 96) wide = false;
     }
-    static const int force_tile = getenv("TWOG_GEMM_TILE") ? atoi(getenv("TWOG_GEMM_TILE")) : 0;
-    static const int force_split = getenv("TWOG_GEMM_SPLITK") ? atoi(getenv("TWOG_GEMM_SPLITK")) : 0;
+    static const int force_tile = twog_env_int("TWOG_GEMM_TILE", 0);
+    static const int force_split = twog_env_int("TWOG_GEMM_SPLITK", 0);
     const int64_t reach128 = tiles128 * (workspace ? (kmax >= 1024 ? kmax / 512 : 1) : 1);
     // (200 since the class multiplies on the bf16 pipes: its tiles run at twice the 64x64 class's rate, so a launch that
     // leaves a fifth of the CUs without a 128-tile still wins -- bs64 step 67.10 -> 66.71 ms; 224: 66.78, 176: 67.15)
-    static const int big_min = getenv("TWOG_GEMM_BIG_MIN") ? atoi(getenv("TWOG_GEMM_BIG_MIN")) : 200;
+    static const int big_min = twog_env_int("TWOG_GEMM_BIG_MIN", 200);
     big = wide && (tiles128 >= big_min || reach128 >= 256);
     if (force_tile == 128) big = true;
     if (force_tile == 64) big = false;
@@ -1740,8 +1697,8 @@ static void prepare_group(const twog_gemm_t* pr, int n, int a_kmajor, int b_kmaj
     // even at 32 rows, a reduction worth splitting between two waves, no grouped k-major rows
     bm = BMN;
     {
-        static const int bm32_on = getenv("TWOG_GEMM_BM32") ? atoi(getenv("TWOG_GEMM_BM32")) : 1;
-        static const int ks_allowed = getenv("TWOG_GEMM_KS") ? atoi(getenv("TWOG_GEMM_KS")) : 1;
+        static const int bm32_on = twog_env_int("TWOG_GEMM_BM32", 1);
+        static const int ks_allowed = twog_env_int("TWOG_GEMM_KS", 1);
         int64_t tiles32 = 0;
         bool plain = true;
         for (int i = 0; i < n; ++i) {
@@ -1768,7 +1725,7 @@ static void prepare_group(const twog_gemm_t* pr, int n, int a_kmajor, int b_kmaj
         P.tiles_n = (P.N + BMN - 1) / BMN;
         P.tile_start = t;
         P.batch = q.batch > 0 ? q.batch : 1;
-        static const int force_nmajor = getenv("TWOG_GEMM_NMAJOR") ? atoi(getenv("TWOG_GEMM_NMAJOR")) : -1;
+        static const int force_nmajor = twog_env_int("TWOG_GEMM_NMAJOR", -1);
         P.n_major = force_nmajor >= 0 ? force_nmajor : (P.N > P.M ? 1 : 0);
         P.a_bs = q.a_batch_stride; P.b_bs = q.b_batch_stride; P.c_bs = q.c_batch_stride;
         const int ntiles = P.batch * P.tiles_m * P.tiles_n;
@@ -1788,8 +1745,8 @@ static void prepare_group(const twog_gemm_t* pr, int n, int a_kmajor, int b_kmaj
     }
     g.total_tiles = t;
     // grouped tile order for the 128x128 class (TWOG_GEMM_GROUP=0: plain order; the 64x64 chain launches keep it)
-    static const int group = getenv("TWOG_GEMM_GROUP") ? atoi(getenv("TWOG_GEMM_GROUP")) : 8;
-    static const int group64 = getenv("TWOG_GEMM_GROUP64") ? atoi(getenv("TWOG_GEMM_GROUP64")) : 0;
+    static const int group = twog_env_int("TWOG_GEMM_GROUP", 8);
+    static const int group64 = twog_env_int("TWOG_GEMM_GROUP64", 0);
     g.group = big ? group : group64;
     g.splitk = 1;
     g.k_per_split = ((kmax + BK - 1) / BK) * BK;
@@ -1817,7 +1774,7 @@ static void prepare_group(const twog_gemm_t* pr, int n, int a_kmajor, int b_kmaj
         // (g.xcd_split, see gemm_tile). An XCD holds 64 such workgroups (32 CUs x 2): take the smallest multiple of 8 whose
         // t * s / 8 workgroups per XCD fill whole rounds of 64 to 95 % (48 tiles -> 32 splits = 3 rounds; 32 -> 16; 64 -> 8),
         // else the best one -- unless the plain choice quantises clearly better. TWOG_GEMM_XCD_SPLIT=0: tile chunks.
-        static const int xcd_on = getenv("TWOG_GEMM_XCD_SPLIT") ? atoi(getenv("TWOG_GEMM_XCD_SPLIT")) : 1;
+        static const int xcd_on = twog_env_int("TWOG_GEMM_XCD_SPLIT", 1);
         int want8 = 0;
         if (xcd_on && big && want > 1 && force_split <= 0 && t <= 512) {
             double best8 = 0.0;
@@ -1854,7 +1811,7 @@ static void prepare_group(const twog_gemm_t* pr, int n, int a_kmajor, int b_kmaj
 // X3 on the 64-row tile class pays where the launch is bound by its MFMAs: a real batch (many tiles), reductions of at least
 // 256. TWOG_GEMM_X3=0 (everything native fp32) and TWOG_GEMM_X3S=0 (only this class) turn it off.
 static bool x3s_ok(const Group& g, int a_kmajor, int xk, int min_tiles = 96) {
-    static const int on = (getenv("TWOG_GEMM_X3") ? atoi(getenv("TWOG_GEMM_X3")) : 1) && (getenv("TWOG_GEMM_X3S") ? atoi(getenv("TWOG_GEMM_X3S")) : 1);
+    static const int on = twog_env_int("TWOG_GEMM_X3", 1) && twog_env_int("TWOG_GEMM_X3S", 1);
     if (!on || a_kmajor || g.splitk != 1 || g.total_tiles < min_tiles) return false;
     int kmax = 0;
     for (int i = 0; i < g.n; ++i) {
@@ -1868,7 +1825,7 @@ static bool x3s_ok(const Group& g, int a_kmajor, int xk, int min_tiles = 96) {
 // KU k-tiles per barrier interval for the X3 chain kernels (gemm_mainloop_x3s): every reduction a multiple of `depth`
 static int x3s_ku(const Group& g, int depth) {
     // (2 since round 4: 176-tile K = 1 536 launch 27.8 -> 26.0 us, 160 tiles 27.3 -> 24.7 us; bit-identical results)
-    static const int ku = getenv("TWOG_X3S_KU") ? atoi(getenv("TWOG_X3S_KU")) : 2;
+    static const int ku = twog_env_int("TWOG_X3S_KU", 2);
     if (ku <= 1) return 1;
     for (int i = 0; i < g.n; ++i)
         if (g.p[i].K % depth) return 1;
@@ -1882,7 +1839,7 @@ static int x3s_ku(const Group& g, int depth) {
 // 1 = never split, n > 1 = always n slices (tuning / tests).
 constexpr size_t XS_COUNTER_BYTES = 16384;   // 4096 tickets at the start of the chain workspace
 static int pick_xsplit(int tiles, int kmax, int bm, size_t ws_bytes) {
-    static const int force = getenv("TWOG_GEMM_XSPLIT") ? atoi(getenv("TWOG_GEMM_XSPLIT")) : 0;
+    static const int force = twog_env_int("TWOG_GEMM_XSPLIT", 0);
     if (force == 1 || tiles <= 0 || tiles > 4096 || ws_bytes <= XS_COUNTER_BYTES) return 1;
     const int kt = (kmax + BK - 1) / BK;
     const size_t tile_bytes = (size_t)bm * 64 * sizeof(float);
@@ -1927,7 +1884,7 @@ static bool try_xsplit(Group& g, int bm, int kmax, void* chain_ws, size_t chain_
     g.slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(chain_ws) + XS_COUNTER_BYTES);
     // epilogue operands (previous C, gate operands: up to 8 values per output element) in every slice: only while the
     // launch is latency-bound, i.e. its outputs are a few hundred KB (8 clips per GPU: 48 rows x 512)
-    static const int early_tiles = getenv("TWOG_GEMM_XS_EARLY") ? atoi(getenv("TWOG_GEMM_XS_EARLY")) : 96;
+    static const int early_tiles = twog_env_int("TWOG_GEMM_XS_EARLY", 96);
     g.xs_early = g.total_tiles <= early_tiles ? 1 : 0;
     launch_fn(dim3(g.total_tiles, g.splitk));
     return true;
@@ -1941,7 +1898,7 @@ static bool try_xsplit(Group& g, int bm, int kmax, void* chain_ws, size_t chain_
 // by the tile's last arriver in slice order (the LA branch of gemm_tile): deterministic, and the fused gate epilogue runs
 // on the complete sum as before. TWOG_X3_XL: 0 = the model below, 1 = never, n > 1 = always n slices.
 static int pick_xl_split(int tiles, int kmax, size_t ws_bytes) {
-    static const int force = getenv("TWOG_X3_XL") ? atoi(getenv("TWOG_X3_XL")) : 0;
+    static const int force = twog_env_int("TWOG_X3_XL", 0);
     if (force == 1 || tiles < 96 || tiles > 4096 || ws_bytes <= XS_COUNTER_BYTES || kmax % 32) return 1;
     const int kt = kmax / 32;
     const int by_ws = (int)((ws_bytes - XS_COUNTER_BYTES) / ((size_t)64 * 64 * sizeof(float) * (size_t)tiles));
@@ -1960,7 +1917,7 @@ static int pick_xl_split(int tiles, int kmax, size_t ws_bytes) {
     };
     int best = 1;
     int best_c = cost(1);
-    static const int min_gain = getenv("TWOG_X3_XL_GAIN") ? atoi(getenv("TWOG_X3_XL_GAIN")) : 15;   // per cent the model must promise
+    static const int min_gain = twog_env_int("TWOG_X3_XL_GAIN", 15);   // per cent the model must promise
     static const int cand[] = {2, 3, 4};
     for (int S : cand) {
         if (S > by_ws || kt / S < 8) break;
@@ -1992,7 +1949,7 @@ static bool colsums_served(const twog_gemm_t* pr, int n, int a_kmajor, int b_kma
         plain = plain && pr[i].batch <= 1 && pr[i].M % 4 == 0 && pr[i].A.inner <= 1 && pr[i].B.inner <= 1;   // (no grouped rows: the KG kernels have no register left)
     }
     if (!any) return true;
-    static const int w8 = getenv("TWOG_GEMM_W8") ? atoi(getenv("TWOG_GEMM_W8")) : 1;
+    static const int w8 = twog_env_int("TWOG_GEMM_W8", 1);
     return a_kmajor && b_kmajor && big && w8 && plain && x3_128_ok(g);
 }
 
@@ -2001,7 +1958,7 @@ static bool colsums_served(const twog_gemm_t* pr, int n, int a_kmajor, int b_kma
 // of 128 x 64 (one per CU: 192), 320 become 160. Taken when that count falls by 15 % and at least half the chip stays busy.
 // TWOG_X3_ROWS128=0: never.
 static bool rows128_pays(const Group& g) {
-    static const int on = getenv("TWOG_X3_ROWS128") ? atoi(getenv("TWOG_X3_ROWS128")) : 1;
+    static const int on = twog_env_int("TWOG_X3_ROWS128", 1);
     if (!on) return false;
     int t64 = 0, t128 = 0;
     for (int i = 0; i < g.n; ++i) {
@@ -2090,19 +2047,19 @@ static int gemm_impl(const twog_gemm_t* problems, int n_problems, int a_kmajor, 
         bool big;
         int bm;
         prepare_group(pr, n, a_kmajor, b_kmajor, workspace, workspace_bytes, g, order, big, bm);
-        static const int depth = getenv("TWOG_GEMM_DEPTH") ? atoi(getenv("TWOG_GEMM_DEPTH")) : 0;  // tuning knob
+        static const int depth = twog_env_int("TWOG_GEMM_DEPTH", 0);  // tuning knob
         const int d128 = depth ? (depth & 3) : 2, d64 = depth ? ((depth >> 2) & 3) : 2;
         int rc;
         // 128x128 tiles run with 8 waves (4 x 2 grid, 32x64 per wave): four waves per SIMD hide the LDS / barrier
         // latencies that a 4-wave tile (two per SIMD) exposes: +5 % on every big shape (TWOG_GEMM_W8=0: 4 waves)
-        static const int w8 = getenv("TWOG_GEMM_W8") ? atoi(getenv("TWOG_GEMM_W8")) : 1;
+        static const int w8 = twog_env_int("TWOG_GEMM_W8", 1);
         bool grouped = false;  // grouped k-major rows keep the 4-wave tiles: their pointer-carrying 8-wave kernels exceed
                                // 128 VGPRs (3 waves/SIMD) and measure 7 % slower
         for (int i = 0; i < n; ++i) grouped = grouped || (a_kmajor && pr[i].A.inner > 1) || (b_kmajor && pr[i].B.inner > 1);
         g_last_class = (big ? TWOG_GEMM_CLASS_TILE128 : 0) | (big && w8 && !grouped ? TWOG_GEMM_CLASS_WAVES8 : 0) |
                        (grouped ? TWOG_GEMM_CLASS_KG : 0) | (g.splitk > 1 ? TWOG_GEMM_CLASS_SPLITK : 0);
         // few 64x64 tiles (at most ~1.5 per CU) with a reduction worth splitting: 8-wave workgroups, k-split inside
-        static const int ks_on = getenv("TWOG_GEMM_KS") ? atoi(getenv("TWOG_GEMM_KS")) : 1;
+        static const int ks_on = twog_env_int("TWOG_GEMM_KS", 1);
         int kmax_ = 0;
         for (int i = 0; i < n; ++i) kmax_ = pr[i].K > kmax_ ? pr[i].K : kmax_;
         const bool ks = ks_on && !big && !a_kmajor && !grouped && g.splitk == 1 && g.total_tiles <= 384 && kmax_ >= 256;
@@ -2168,7 +2125,7 @@ static int gemm_impl(const twog_gemm_t* problems, int n_problems, int a_kmajor, 
             done += n;
             continue;
         }
-        static const int x3_try = getenv("TWOG_GEMM_X3") ? atoi(getenv("TWOG_GEMM_X3")) : 1;   // grouped rows: X3 has 8-wave variants
+        static const int x3_try = twog_env_int("TWOG_GEMM_X3", 1);   // grouped rows: X3 has 8-wave variants
         if (big && w8 && (!grouped || x3_try)) rc = d128 == 2 ? launch<128, 128, 512, 2>(g, a_kmajor, b_kmajor, st) : launch<128, 128, 512, 1>(g, a_kmajor, b_kmajor, st);
         else if (big) rc = d128 == 2 ? launch<128, 128, 256, 2>(g, a_kmajor, b_kmajor, st) : launch<128, 128, 256, 1>(g, a_kmajor, b_kmajor, st);
         else if (!big && x3s_ok(g, a_kmajor, 16)) {
@@ -2237,11 +2194,11 @@ int twog_internal_gemm_gate_bwd(const twog_gemm_t* pr, int n, const twog_gru_ste
         ga.du_part[i] = (gates[src].rows > 0 && gates[src].du && du_part) ? du_part[src] : nullptr;
     }
     for (int i = n; i < MAXP; ++i) { ga.gate_of[i] = -1; ga.du_part[i] = nullptr; }
-    static const int depth = getenv("TWOG_GEMM_DEPTH") ? atoi(getenv("TWOG_GEMM_DEPTH")) : 0;
+    static const int depth = twog_env_int("TWOG_GEMM_DEPTH", 0);
     const int d64 = depth ? ((depth >> 2) & 3) : 2;
     dim3 grid(g.total_tiles, 1), block(256);
     g_last_class = TWOG_GEMM_CLASS_GATE;
-    static const int ks_on = getenv("TWOG_GEMM_KS") ? atoi(getenv("TWOG_GEMM_KS")) : 1;
+    static const int ks_on = twog_env_int("TWOG_GEMM_KS", 1);
     int kmax = 0;
     for (int i = 0; i < n; ++i) kmax = pr[i].K > kmax ? pr[i].K : kmax;
     if (bm == 64 && chain_ws && x3s_ok(g, 0, 32) && xl_setup(g, kmax, chain_ws, chain_ws_bytes)) {
@@ -2305,7 +2262,7 @@ int twog_internal_gemm_gru_fwd(const twog_gemm_t* gh, const twog_gemm_t* gim, co
     // TWOG_GRU_FWD_FUSION: bit 0 = chains without message products (frame-level BiGRU), bit 1 = with (segment level),
     // bit 2 = always (skip the cost model below). Default 3: both levels, each launch decided by the model.
     const int mode = twog_internal_gru_fwd_mode();   // read per call: tests switch it inside one process
-    static const int ksplit = getenv("TWOG_GRU_FWD_KS") ? atoi(getenv("TWOG_GRU_FWD_KS")) : 2;
+    static const int ksplit = twog_env_int("TWOG_GRU_FWD_KS", 2);
     const bool with_msgs = gim != nullptr;
     if (!(mode & (with_msgs ? 2 : 1)) || n <= 0 || n > MAXP) return 1;
     const int h = st[0].hidden;
@@ -2369,8 +2326,8 @@ int twog_internal_gemm_gru_fwd(const twog_gemm_t* gh, const twog_gemm_t* gim, co
     if (dry_run) return 0;
     for (int i = n; i < MAXP; ++i) { g.p[i] = g.p[0]; g.p[i].rt_start = 0x7fffffff; }
     g_last_class = TWOG_GEMM_CLASS_GRUFWD;
-    static const int x3_on = (getenv("TWOG_GEMM_X3") ? atoi(getenv("TWOG_GEMM_X3")) : 1) && (getenv("TWOG_GEMM_X3S") ? atoi(getenv("TWOG_GEMM_X3S")) : 1) &&
-                             (getenv("TWOG_GEMM_X3G") ? atoi(getenv("TWOG_GEMM_X3G")) : 1);
+    static const int x3_on = twog_env_int("TWOG_GEMM_X3", 1) && twog_env_int("TWOG_GEMM_X3S", 1) &&
+                             twog_env_int("TWOG_GEMM_X3G", 1);
     bool x3 = x3_on && ksplit == 2 && h >= 256 && h % 32 == 0;   // whole 32-deep k-tiles of both products
     for (int i = 0; i < n; ++i) x3 = x3 && g.p[i].K2 % 32 == 0;
     if (x3) {

@@ -14,20 +14,18 @@
 // Operands needed in both orientations are kept twice in LDS (as [row][k] and transposed), written once at staging.
 #include "twog_common.h"
 
-typedef float f32x4m __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int MAXN = 64;
 constexpr int LDK = 68;  // stride of LDS arrays whose contiguous dimension is the 64-wide feature axis
 
-__device__ __forceinline__ f32x4m mfma16(float a, float b, f32x4m c) {
+__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
 // acc += A[rt-th row tile][0..K) * B[ct-th col tile][0..K)^T with both operands stored [row][k], k contiguous
-__device__ __forceinline__ f32x4m tile_mm(const float* a, int lda, const float* b, int ldb, int ksteps, int i16, int g,
-                                          f32x4m acc) {
+__device__ __forceinline__ f32x4 tile_mm(const float* a, int lda, const float* b, int ldb, int ksteps, int i16, int g,
+                                          f32x4 acc) {
     const float* pa = a + i16 * lda + g;
     const float* pb = b + i16 * ldb + g;
 #pragma unroll 4
@@ -35,8 +33,8 @@ __device__ __forceinline__ f32x4m tile_mm(const float* a, int lda, const float* 
     return acc;
 }
 // same with B stored [k][col] (col contiguous, row stride ldb): bank-conflicted reads, only used when LDS is short
-__device__ __forceinline__ f32x4m tile_mm_bt(const float* a, int lda, const float* b, int ldb, int ksteps, int i16, int g,
-                                             f32x4m acc) {
+__device__ __forceinline__ f32x4 tile_mm_bt(const float* a, int lda, const float* b, int ldb, int ksteps, int i16, int g,
+                                             f32x4 acc) {
     const float* pa = a + i16 * lda + g;
     const float* pb = b + g * ldb + i16;
 #pragma unroll 4
@@ -117,7 +115,7 @@ __global__ __launch_bounds__(512, 1) void gcn_attn2_fwd_kernel(const float* xin,
         // P = X M + d
         for (int t = wv; t < RT * 4; t += nw) {
             const int rt = t >> 2, ct = t & 3;
-            f32x4m acc = {0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             acc = tile_mm(sX + rt * 16 * LDK, LDK, sMt + ct * 16 * LDK, LDK, 16, i16, g, acc);
             const float dv = sd[ct * 16 + i16];
 #pragma unroll
@@ -127,7 +125,7 @@ __global__ __launch_bounds__(512, 1) void gcn_attn2_fwd_kernel(const float* xin,
         // scores = P X^T
         for (int t = wv; t < RT * RT; t += nw) {
             const int rt = t / RT, ct = t - rt * RT;
-            f32x4m acc = {0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             acc = tile_mm(sP + rt * 16 * LDK, LDK, sX + ct * 16 * LDK, LDK, 16, i16, g, acc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) sS[(rt * 16 + 4 * g + r) * LDN + ct * 16 + i16] = acc[r];
@@ -148,7 +146,7 @@ __global__ __launch_bounds__(512, 1) void gcn_attn2_fwd_kernel(const float* xin,
         // Z = S X
         for (int t = wv; t < RT * 4; t += nw) {
             const int rt = t >> 2, ct = t & 3;
-            f32x4m acc = {0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             acc = tile_mm(sS + rt * 16 * LDN, LDN, sXt + ct * 16 * LDN, LDN, RT * 4, i16, g, acc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -193,9 +191,9 @@ __global__ __launch_bounds__(NT, 1) void gcn_attn2_bwd_kernel(const float* xin, 
     if (threadIdx.x < 64) sd[threadIdx.x] = md[64 * 64 + threadIdx.x];
     // dMt accumulators: 16 tiles (nt, kt) of 16x16, tile t owned by wave t % nw (two tiles per wave at 8 waves)
     constexpr int TU = 1024 / NT;   // tiles of a 16-tile list per wave: 2 with 8 waves, 1 with 16
-    f32x4m accM[TU];
+    f32x4 accM[TU];
 #pragma unroll
-    for (int u = 0; u < TU; ++u) accM[u] = f32x4m{0.f, 0.f, 0.f, 0.f};
+    for (int u = 0; u < TU; ++u) accM[u] = f32x4{0.f, 0.f, 0.f, 0.f};
     float dd_acc = 0.f;  // threads 0..63: dd[n]
     // the next frame's X, dZ and S rows are fetched into registers while this frame is computed (the frame loop is a chain
     // of six barrier-separated phases on ONE workgroup per CU: nothing else would hide the loads)
@@ -229,7 +227,7 @@ __global__ __launch_bounds__(NT, 1) void gcn_attn2_bwd_kernel(const float* xin, 
         // P^T (recomputed) and dA; dX1 = S^T dZ starts the dX accumulators
         for (int t = wv; t < RT * 4; t += nw) {
             const int rt = t >> 2, ct = t & 3;
-            f32x4m acc = {0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             acc = tile_mm(sX + rt * 16 * LDK, LDK, sMt + ct * 16 * LDK, LDK, 16, i16, g, acc);
             const float dv = sd[ct * 16 + i16];
 #pragma unroll
@@ -240,15 +238,15 @@ __global__ __launch_bounds__(NT, 1) void gcn_attn2_bwd_kernel(const float* xin, 
         }
         for (int t = wv; t < RT * RT; t += nw) {
             const int rt = t / RT, ct = t - rt * RT;
-            f32x4m acc = {0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             acc = tile_mm(sdZ + rt * 16 * LDK, LDK, sX + ct * 16 * LDK, LDK, 16, i16, g, acc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) sdS[(rt * 16 + 4 * g + r) * LDN + ct * 16 + i16] = acc[r];
         }
         // this wave's dX tiles (at most 2 with 8 waves and RT <= 4): tile u -> t = wv + u * nw
-        f32x4m accX[TU];
+        f32x4 accX[TU];
 #pragma unroll
-        for (int u = 0; u < TU; ++u) accX[u] = f32x4m{0.f, 0.f, 0.f, 0.f};
+        for (int u = 0; u < TU; ++u) accX[u] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int u = 0; u < TU; ++u) {
             const int t = wv + u * nw;
@@ -274,7 +272,7 @@ __global__ __launch_bounds__(NT, 1) void gcn_attn2_bwd_kernel(const float* xin, 
         // dP = dS X  (-> sdZ / sdZt buffers, dZ is no longer needed)
         for (int t = wv; t < RT * 4; t += nw) {
             const int rt = t >> 2, ct = t & 3;
-            f32x4m acc = {0.f, 0.f, 0.f, 0.f};
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             acc = tile_mm(sdS + rt * 16 * LDN, LDN, sXt + ct * 16 * LDN, LDN, RT * 4, i16, g, acc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -387,7 +385,7 @@ extern "C" int twog_gcn_attn2_bwd(const float* x, const float* md, const float* 
     const size_t lds = (size_t)plan[2];
     // 16 waves: the phases are lists of 9 ... 16 independent 16x16 tiles, each a chain of 12-16 dependent MFMAs -- with 8 waves
     // every list takes two rounds with half the waves idle in the second (TWOG_GCN_ATTN2_WAVES=8: the 8-wave form)
-    static const int waves = getenv("TWOG_GCN_ATTN2_WAVES") ? atoi(getenv("TWOG_GCN_ATTN2_WAVES")) : 16;
+    static const int waves = twog_env_int("TWOG_GCN_ATTN2_WAVES", 16);
     static std::atomic<uint32_t> lds_attr_done{0}, lds_attr_done16{0};
     if (waves == 16) {
         twog_allow_dynamic_lds(gcn_attn2_bwd_kernel<1024>, 160 * 1024, lds_attr_done16);

@@ -23,14 +23,12 @@
 // are read straight from global memory (16 KB, L1-resident); grid = one workgroup per CU, looping over groups. The backward pass recomputes e1 from the geometry input (embed1_fwd, bit-identical arithmetic).
 #include "twog_common.h"
 
-typedef float f32x4g __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int MAXN = 64;
 constexpr int LDK = 68;   // row stride of [row][64 features] LDS arrays: = 4 (mod 16) words -> conflict-free k-contiguous reads
 
-__device__ __forceinline__ f32x4g mfma16(float a, float b, f32x4g c) {
+__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
@@ -63,7 +61,7 @@ __device__ __forceinline__ void frag64(const float* row, int g, float (&f)[16]) 
         f[4 * c] = v.x; f[4 * c + 1] = v.y; f[4 * c + 2] = v.z; f[4 * c + 3] = v.w;
     }
 }
-__device__ __forceinline__ f32x4g mm64(const float (&a)[16], const float (&b)[16], f32x4g acc) {
+__device__ __forceinline__ f32x4 mm64(const float (&a)[16], const float (&b)[16], f32x4 acc) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc = mfma16(a[i], b[i], acc);
     return acc;
@@ -162,7 +160,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_fused_fwd_kernel(const flo
                 const int ct = c0 + cc;
                 float bf[16];
                 frag64(w2 + (ct * 16 + i16) * 64, g, bf);
-                const f32x4g acc = mm64(ae, bf, f32x4g{0.f, 0.f, 0.f, 0.f});
+                const f32x4 acc = mm64(ae, bf, f32x4{0.f, 0.f, 0.f, 0.f});
                 const int col = ct * 16 + i16;
                 const float bias = sb2[col];
 #pragma unroll
@@ -193,7 +191,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_fused_fwd_kernel(const flo
                 for (int ct = 0; ct < 4; ++ct) {
                     float bf[16];
                     frag64(sMt + (ct * 16 + i16) * LDK, g, bf);
-                    const f32x4g acc = mm64(af, bf, f32x4g{0.f, 0.f, 0.f, 0.f});
+                    const f32x4 acc = mm64(af, bf, f32x4{0.f, 0.f, 0.f, 0.f});
                     const int col = ct * 16 + i16;
                     const float dv = sd[col];
 #pragma unroll
@@ -201,13 +199,13 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_fused_fwd_kernel(const flo
                 }
             }
             // scores against every node of the frame: NT column tiles (NT <= 4), kept in the accumulators
-            f32x4g sc[4];
+            f32x4 sc[4];
             {
                 float af[16];
                 frag64(priv + i16 * LDK, g, af);
 #pragma unroll
                 for (int ct = 0; ct < 4; ++ct) {
-                    sc[ct] = f32x4g{0.f, 0.f, 0.f, 0.f};
+                    sc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
                     if (ct < NT) {
                         float bf[16];
                         frag64(sX + (fbase + ct * 16 + i16) * LDK, g, bf);
@@ -260,7 +258,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_fused_fwd_kernel(const flo
                 bool kpad[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) kpad[j] = g + 4 * (KSTEPS - 4 + j) >= N;
-                f32x4g zc[4];
+                f32x4 zc[4];
 #pragma unroll
                 for (int ct = 0; ct < 4; ++ct) {
                     const float* pb = sX + (fbase + g) * LDK + ct * 16 + i16;
@@ -269,7 +267,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_fused_fwd_kernel(const flo
                     for (int kk = 0; kk < KSTEPS; ++kk) xb[kk] = pb[kk * 4 * LDK];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) xb[KSTEPS - 4 + j] = kpad[j] ? 0.f : xb[KSTEPS - 4 + j];
-                    zc[ct] = f32x4g{0.f, 0.f, 0.f, 0.f};
+                    zc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int kk = 0; kk < KSTEPS; ++kk) zc[ct] = mfma16(sa[kk], xb[kk], zc[ct]);
                 }
@@ -299,7 +297,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_fused_fwd_kernel(const flo
 int twog_internal_plan_fused_fwd(int n_frames, int n_nodes, int out[4]) {
     if (n_nodes > MAXN || n_nodes < 1) return -1;
     // frames per group: as many as fit the CU's LDS (rows of X for the group + one scratch tile per wave), at most 8
-    static const int force_fg = getenv("TWOG_GCN_FG") ? atoi(getenv("TWOG_GCN_FG")) : 0;
+    static const int force_fg = twog_env_int("TWOG_GCN_FG", 0);
     Layout best = layout_of(n_nodes, 1);
     for (int fg = 2; fg <= 8; ++fg) {
         const Layout L = layout_of(n_nodes, fg);

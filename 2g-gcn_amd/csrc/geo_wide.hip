@@ -22,8 +22,6 @@
 // MFMA ignores EXEC: short tiles are padded with zeros SELECTED into the operand, the wave / strip indices are scalar.
 #include "twog_common.h"
 
-typedef float f32x4w __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int LDK = 68;      // row stride of [row][64 features] LDS arrays (= 4 mod 16 words)
@@ -33,7 +31,7 @@ constexpr int FWD_PRIV = 16 * LDK;                 // per wave: P rows / Z rows;
 constexpr int BWD_PRIV = 16 * LDK + 2 * 16 * LDT;  // per wave: dP (G) rows + two staging tiles
 constexpr int MAX_GRID = 256;
 
-__device__ __forceinline__ f32x4w mfma16(float a, float b, f32x4w c) {
+__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 // the 64-deep operand fragment of geo_fused.hip: lane group g takes k = 16c + 4g + j for step 4c + j
@@ -52,7 +50,7 @@ __device__ __forceinline__ void frag64_or_zero(const float* row, bool on, int g,
         f[4 * c] = v.x; f[4 * c + 1] = v.y; f[4 * c + 2] = v.z; f[4 * c + 3] = v.w;
     }
 }
-__device__ __forceinline__ f32x4w mm64(const float (&a)[16], const float (&b)[16], f32x4w acc) {
+__device__ __forceinline__ f32x4 mm64(const float (&a)[16], const float (&b)[16], f32x4 acc) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc = mfma16(a[i], b[i], acc);
     return acc;
@@ -147,7 +145,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_wide_fwd_kernel(const floa
                 const int ct = c0 + cc;
                 float bf[16];
                 frag64(w2 + (ct * 16 + i16) * 64, g, bf);
-                const f32x4w acc = mm64(ae, bf, f32x4w{0.f, 0.f, 0.f, 0.f});
+                const f32x4 acc = mm64(ae, bf, f32x4{0.f, 0.f, 0.f, 0.f});
                 const int col = ct * 16 + i16;
                 const float bias = sb2[col];
 #pragma unroll
@@ -174,20 +172,20 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_wide_fwd_kernel(const floa
                 for (int ct = 0; ct < 4; ++ct) {
                     float bf[16];
                     frag64(sMt + (ct * 16 + i16) * LDK, g, bf);
-                    const f32x4w acc = mm64(af, bf, f32x4w{0.f, 0.f, 0.f, 0.f});
+                    const f32x4 acc = mm64(af, bf, f32x4{0.f, 0.f, 0.f, 0.f});
                     const int col = ct * 16 + i16;
                     const float dv = sd[col];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) priv[(4 * g + r) * LDK + col] = acc[r] + dv;
                 }
             }
-            f32x4w sc[NTC];
+            f32x4 sc[NTC];
             {
                 float af[16];
                 frag64(priv + i16 * LDK, g, af);
 #pragma unroll
                 for (int ct = 0; ct < NTC; ++ct) {
-                    sc[ct] = f32x4w{0.f, 0.f, 0.f, 0.f};
+                    sc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
                     if (ct < nt) {
                         float bf[16];
                         frag64(sX + (ct * 16 + i16) * LDK, g, bf);
@@ -217,9 +215,9 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_wide_fwd_kernel(const floa
             }
             // adjacency rows -> global (16 lanes write 64 contiguous bytes of a row); Z = S X tile by tile: the tile goes through
             // the staging area (P is dead) from the accumulator layout [row 4g + r][col i16] to the operand layout [row i16][k]
-            f32x4w zc[4];
+            f32x4 zc[4];
 #pragma unroll
-            for (int oc = 0; oc < 4; ++oc) zc[oc] = f32x4w{0.f, 0.f, 0.f, 0.f};
+            for (int oc = 0; oc < 4; ++oc) zc[oc] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ct = 0; ct < NTC; ++ct) {
                 if (ct < nt) {
@@ -274,9 +272,9 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_wide_bwd_kernel(const floa
     float* tA = rowsP + 16 * LDK;                   // [16][LDT] staging tile
     float* tB = tA + 16 * LDT;                      // [16][LDT] staging tile
     stage_md(md, sMt, sd);
-    f32x4w accM[16];   // this wave's share of dMt: tile (n tile, k tile) = accM[4 nt + kt]
+    f32x4 accM[16];   // this wave's share of dMt: tile (n tile, k tile) = accM[4 nt + kt]
 #pragma unroll
-    for (int u = 0; u < 16; ++u) accM[u] = f32x4w{0.f, 0.f, 0.f, 0.f};
+    for (int u = 0; u < 16; ++u) accM[u] = f32x4{0.f, 0.f, 0.f, 0.f};
     float dd_acc = 0.f;   // lane n: this wave's share of dd[n]
     for (int f = blockIdx.x; f < n_frames; f += gridDim.x) {
         const int64_t r0 = (int64_t)f * N;
@@ -301,7 +299,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_wide_bwd_kernel(const floa
             for (int ct = 0; ct < nt; ++ct) {
                 float bf[16];
                 frag64(sX + (ct * 16 + i16) * LDK, g, bf);
-                const f32x4w da = mm64(af, bf, f32x4w{0.f, 0.f, 0.f, 0.f});
+                const f32x4 da = mm64(af, bf, f32x4{0.f, 0.f, 0.f, 0.f});
                 const int col = ct * 16 + i16;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -315,13 +313,13 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_wide_bwd_kernel(const floa
                 tr[r] = sum16(tr[r]);
                 if (i16 == 0) st[base + 4 * g + r] = tr[r];
             }
-            f32x4w dp[4];
+            f32x4 dp[4];
 #pragma unroll
-            for (int oc = 0; oc < 4; ++oc) dp[oc] = f32x4w{0.f, 0.f, 0.f, 0.f};
+            for (int oc = 0; oc < 4; ++oc) dp[oc] = f32x4{0.f, 0.f, 0.f, 0.f};
             for (int ct = 0; ct < nt; ++ct) {
                 float bf[16];
                 frag64(sX + (ct * 16 + i16) * LDK, g, bf);
-                const f32x4w da = mm64(af, bf, f32x4w{0.f, 0.f, 0.f, 0.f});
+                const f32x4 da = mm64(af, bf, f32x4{0.f, 0.f, 0.f, 0.f});
                 const int col = ct * 16 + i16;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -348,7 +346,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_wide_bwd_kernel(const floa
                 frag64(rowsP + i16 * LDK, g, af);
 #pragma unroll
                 for (int oc = 0; oc < 4; ++oc) {
-                    f32x4w acc = {0.f, 0.f, 0.f, 0.f};
+                    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int kk = 0; kk < 16; ++kk) {
                         const int k = 16 * (kk >> 2) + 4 * g + (kk & 3);
@@ -387,15 +385,15 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_wide_bwd_kernel(const floa
             const int jbase = jt * 16, col = jbase + i16;
             float bx[16];
             frag64(sX + (jbase + i16) * LDK, g, bx);
-            f32x4w acc1[4], accG[4];
+            f32x4 acc1[4], accG[4];
 #pragma unroll
-            for (int oc = 0; oc < 4; ++oc) acc1[oc] = accG[oc] = f32x4w{0.f, 0.f, 0.f, 0.f};
+            for (int oc = 0; oc < 4; ++oc) acc1[oc] = accG[oc] = f32x4{0.f, 0.f, 0.f, 0.f};
             float csp = 0.f;   // this lane's share of colsum_i dS[i][col]
             for (int it = 0; it < nt; ++it) {
                 const int ibase = it * 16;
                 float af[16];
                 frag64_or_zero(dz + (r0 + ibase + i16) * 64, ibase + i16 < N, g, af);
-                const f32x4w da = mm64(af, bx, f32x4w{0.f, 0.f, 0.f, 0.f});
+                const f32x4 da = mm64(af, bx, f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = ibase + 4 * g + r;
@@ -445,7 +443,7 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void gcn_wide_bwd_kernel(const floa
             for (int oc = 0; oc < 4; ++oc) {
                 float bf[16];
                 frag64(sMt + (oc * 16 + i16) * LDK, g, bf);
-                const f32x4w acc2 = mm64(ag, bf, f32x4w{0.f, 0.f, 0.f, 0.f});
+                const f32x4 acc2 = mm64(ag, bf, f32x4{0.f, 0.f, 0.f, 0.f});
                 const float dv = sd[oc * 16 + i16];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {

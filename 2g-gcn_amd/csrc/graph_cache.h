@@ -77,7 +77,7 @@ int run(const Desc& d_in, hipStream_t user, F enqueue) {
     }
     State& S = state();
     std::lock_guard<std::mutex> lock(S.mu);
-    static const int hash_bits = getenv("TWOG_GRAPH_HASH_BITS") ? atoi(getenv("TWOG_GRAPH_HASH_BITS")) : 64;
+    static const int hash_bits = twog_env_int("TWOG_GRAPH_HASH_BITS", 64);
     uint64_t key = fnv1a(d.bytes.data(), d.bytes.size());
     if (hash_bits < 64) key = hash_bits <= 0 ? 0 : (key & ((1ull << hash_bits) - 1));
     key ^= 0x9e3779b97f4a7c15ull * (uint64_t)(dev + 1);

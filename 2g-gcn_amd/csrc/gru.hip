@@ -80,35 +80,34 @@ __global__ __launch_bounds__(256) void gru_step_fwd_vec_kernel(const FwdGroup g)
     const int rl = (int)threadIdx.x / lpr, q = (int)threadIdx.x - rl * lpr;
     const int r = (int)blockIdx.x * rpb + rl;
     if (rl >= rpb || r >= S.rows) return;
-    typedef float f4 __attribute__((ext_vector_type(4)));
     const int j = 4 * q;
     const float* gi = twog_row_ptr(S.gi, r);
     const float* gh = twog_row_ptr(S.gh, r);
-    f4 ir = *reinterpret_cast<const f4*>(gi + j), iz = *reinterpret_cast<const f4*>(gi + H + j), in_ = *reinterpret_cast<const f4*>(gi + 2 * H + j);
+    f32x4 ir = *reinterpret_cast<const f32x4*>(gi + j), iz = *reinterpret_cast<const f32x4*>(gi + H + j), in_ = *reinterpret_cast<const f32x4*>(gi + 2 * H + j);
     if (S.gi2.ptr) {
         const float* gi2 = twog_row_ptr(S.gi2, r);
-        ir += *reinterpret_cast<const f4*>(gi2 + j);
-        iz += *reinterpret_cast<const f4*>(gi2 + H + j);
-        in_ += *reinterpret_cast<const f4*>(gi2 + 2 * H + j);
+        ir += *reinterpret_cast<const f32x4*>(gi2 + j);
+        iz += *reinterpret_cast<const f32x4*>(gi2 + H + j);
+        in_ += *reinterpret_cast<const f32x4*>(gi2 + 2 * H + j);
     }
-    const f4 hr = *reinterpret_cast<const f4*>(gh + j), hz = *reinterpret_cast<const f4*>(gh + H + j), hn = *reinterpret_cast<const f4*>(gh + 2 * H + j);
-    f4 h0 = {0.f, 0.f, 0.f, 0.f};
-    if (S.h_prev.ptr) h0 = *reinterpret_cast<const f4*>(twog_row_ptr(S.h_prev, r) + j);
+    const f32x4 hr = *reinterpret_cast<const f32x4*>(gh + j), hz = *reinterpret_cast<const f32x4*>(gh + H + j), hn = *reinterpret_cast<const f32x4*>(gh + 2 * H + j);
+    f32x4 h0 = {0.f, 0.f, 0.f, 0.f};
+    if (S.h_prev.ptr) h0 = *reinterpret_cast<const f32x4*>(twog_row_ptr(S.h_prev, r) + j);
     const float uu = gate_u(S.u, S.u_ld_outer, S.u_ld_inner, S.u_inner, r);
-    f4 rg, z, n, ho;
+    f32x4 rg, z, n, ho;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         float rk, zk, nk;
         ho[k] = gru_gate_unit(ir[k], iz[k], in_[k], hr[k], hz[k], hn[k], h0[k], S.u != nullptr, uu, rk, zk, nk);
         rg[k] = rk; z[k] = zk; n[k] = nk;
     }
-    *reinterpret_cast<f4*>(twog_row_ptr(S.h_out, r) + j) = ho;
+    *reinterpret_cast<f32x4*>(twog_row_ptr(S.h_out, r) + j) = ho;
     if (S.save.ptr) {
         float* sv = twog_row_ptr(S.save, r);
-        *reinterpret_cast<f4*>(sv + j) = rg;
-        *reinterpret_cast<f4*>(sv + H + j) = z;
-        *reinterpret_cast<f4*>(sv + 2 * H + j) = n;
-        *reinterpret_cast<f4*>(sv + 3 * H + j) = hn;
+        *reinterpret_cast<f32x4*>(sv + j) = rg;
+        *reinterpret_cast<f32x4*>(sv + H + j) = z;
+        *reinterpret_cast<f32x4*>(sv + 2 * H + j) = n;
+        *reinterpret_cast<f32x4*>(sv + 3 * H + j) = hn;
     }
 }
 
@@ -208,7 +207,7 @@ extern "C" int twog_gru_step_fwd(const twog_gru_step_t* steps, int n_steps, void
             if (g.s[i].hidden > maxh) maxh = g.s[i].hidden;
         }
         if (maxrows > 0) {
-            static const int vec_on = getenv("TWOG_GRU_STEP_VEC") ? atoi(getenv("TWOG_GRU_STEP_VEC")) : 1;
+            static const int vec_on = twog_env_int("TWOG_GRU_STEP_VEC", 1);
             bool vec = vec_on != 0;
             for (int i = 0; i < n; ++i) vec = vec && gru_step_vec_ok(g.s[i]) && g.s[i].hidden == maxh;
             if (vec) {

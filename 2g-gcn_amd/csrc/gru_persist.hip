@@ -24,21 +24,14 @@
 // the launch-per-step path (kernels.py).
 // With 8 combinations (the bench shape) the 32 workgroups of a combination share blockIdx mod 8, i.e. an XCD: their
 // exchange stays in that XCD's L2 -- a matter of speed, never of correctness. Bit-reproducible: fixed summation order.
-#include "twog_common.h"
+#include "bf16x3.h"
 #include "persist_common.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((__vector_size__(4 * sizeof(unsigned))));
-
 constexpr int MAXG = 8;     // (entity type, direction) groups
 constexpr int MAXC = 32;    // (group, row chunk) combinations, each worked by hidden / 16 workgroups
 constexpr int MAXTW = 4;    // row tiles per wave at most: a chunk has at most 4 * MAXTW tiles
-constexpr int SC1 = 16;     // aux bits of the buffer instructions: sc1 (write-through stores / L2-served loads)
 
 struct PGroup {
     const float* gi;     // [bs][T][E][6h]
@@ -58,26 +51,12 @@ struct PArgs {
     int spin_limit;
 };
 
-__device__ __forceinline__ uint32_t pack_hi16(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302); }
-
-// eight consecutive fp32 values -> the three bf16 planes of an MFMA fragment (element j = value j), by truncation: exact
-__device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, bf16x8& ph, bf16x8& pm, bf16x8& pl) {
+// The exact 3 x bf16 split of the weights and the streamed states (bf16x3.h), behind this file's timing probe.
+__device__ __forceinline__ Planes split_gp(const f32x4 a, const f32x4 b) {
 #ifdef TWOG_GP_PROBE_NOSPLIT   // timing probe only (wrong results): what the per-wave split of the streamed states costs
-    ph = __builtin_bit_cast(bf16x8, a); pm = __builtin_bit_cast(bf16x8, b); pl = ph;
-    return;
+    { Planes q; q.h = __builtin_bit_cast(bf16x8, a); q.m = __builtin_bit_cast(bf16x8, b); q.l = q.h; return q; }
 #endif
-    uint32_t x[8], r1[8], r2[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float f0 = i < 4 ? a[i] : b[i - 4];
-        x[i] = __float_as_uint(f0);
-        const float f1 = f0 - __uint_as_float(x[i] & 0xffff0000u);
-        r1[i] = __float_as_uint(f1);
-        r2[i] = __float_as_uint(f1 - __uint_as_float(r1[i] & 0xffff0000u));
-    }
-    ph = __builtin_bit_cast(bf16x8, i32x4{(int)pack_hi16(x[0], x[1]), (int)pack_hi16(x[2], x[3]), (int)pack_hi16(x[4], x[5]), (int)pack_hi16(x[6], x[7])});
-    pm = __builtin_bit_cast(bf16x8, i32x4{(int)pack_hi16(r1[0], r1[1]), (int)pack_hi16(r1[2], r1[3]), (int)pack_hi16(r1[4], r1[5]), (int)pack_hi16(r1[6], r1[7])});
-    pl = __builtin_bit_cast(bf16x8, i32x4{(int)pack_hi16(r2[0], r2[1]), (int)pack_hi16(r2[2], r2[3]), (int)pack_hi16(r2[4], r2[5]), (int)pack_hi16(r2[6], r2[7])});
+    return split8(a, b);
 }
 
 // four floats of the transposition scratch, read AS floats: a load through a vector-typed pointer does not alias the
@@ -126,18 +105,17 @@ __global__ __launch_bounds__(256, 1) void bigru_persist_fwd_kernel(const PArgs P
     for (int f = wave; f < NKB * 3; f += 4) {
         const int kb = f / 3, c = f - kb * 3;
         const float* w = G.w_hh + (int64_t)(c * h + slice * 16 + i16) * h + kb * 32 + 8 * g4;
-        bf16x8 ph, pm, pl;
-        split8(*reinterpret_cast<const f32x4*>(w), *reinterpret_cast<const f32x4*>(w + 4), ph, pm, pl);
-        wfrag[((kb * 3 + c) * 3 + 0) * 64 + lane] = __builtin_bit_cast(i32x4, ph);
-        wfrag[((kb * 3 + c) * 3 + 1) * 64 + lane] = __builtin_bit_cast(i32x4, pm);
-        wfrag[((kb * 3 + c) * 3 + 2) * 64 + lane] = __builtin_bit_cast(i32x4, pl);
+        const Planes p = split_gp(*reinterpret_cast<const f32x4*>(w), *reinterpret_cast<const f32x4*>(w + 4));
+        wfrag[((kb * 3 + c) * 3 + 0) * 64 + lane] = __builtin_bit_cast(i32x4, p.h);
+        wfrag[((kb * 3 + c) * 3 + 1) * 64 + lane] = __builtin_bit_cast(i32x4, p.m);
+        wfrag[((kb * 3 + c) * 3 + 2) * 64 + lane] = __builtin_bit_cast(i32x4, p.l);
     }
     float bias[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) bias[c] = G.b_hh ? G.b_hh[c * h + slice * 16 + i16] : 0.f;
     __syncthreads();
     if (nt == 0) return;   // (a wave without tiles neither waits nor is waited for: the counters are per wave)
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(G.out, 0, 0xffffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_out = rsrc_of(G.out);
     const int col = slice * 16 + i16;
     // byte offset of (row, column 0 of this direction) at time x in `out`: rows (b, e) of [bs][T][E][2h]
     auto out_off = [&](int row, int x) -> uint32_t {
@@ -191,30 +169,32 @@ __global__ __launch_bounds__(256, 1) void bigru_persist_fwd_kernel(const PArgs P
             auto load_a = [&](int kb, f32x4 (&a)[TW][2]) {
 #pragma unroll
                 for (int i = 0; i < TW; ++i) {
-                    a[i][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_out, (int)(abase[i] + 128u * kb), 0, SC1));
-                    a[i][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_out, (int)(abase[i] + 128u * kb + 16u), 0, SC1));
+                    a[i][0] = ld_sc1(rs_out, abase[i] + 128u * kb);
+                    a[i][1] = ld_sc1(rs_out, abase[i] + 128u * kb + 16u);
                 }
             };
             auto mac = [&](int kb, const f32x4 (&a)[TW][2]) {
-                bf16x8 ah[TW], am[TW], al[TW];
+                Planes A[TW];
 #pragma unroll
-                for (int i = 0; i < TW; ++i) split8(a[i][0], a[i][1], ah[i], am[i], al[i]);
+                for (int i = 0; i < TW; ++i) A[i] = split_gp(a[i][0], a[i][1]);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    const bf16x8 wh = __builtin_bit_cast(bf16x8, wfrag[((kb * 3 + c) * 3 + 0) * 64 + lane]);
-                    const bf16x8 wm = __builtin_bit_cast(bf16x8, wfrag[((kb * 3 + c) * 3 + 1) * 64 + lane]);
-                    const bf16x8 wl = __builtin_bit_cast(bf16x8, wfrag[((kb * 3 + c) * 3 + 2) * 64 + lane]);
+                    Planes W;
+                    W.h = __builtin_bit_cast(bf16x8, wfrag[((kb * 3 + c) * 3 + 0) * 64 + lane]);
+                    W.m = __builtin_bit_cast(bf16x8, wfrag[((kb * 3 + c) * 3 + 1) * 64 + lane]);
+                    W.l = __builtin_bit_cast(bf16x8, wfrag[((kb * 3 + c) * 3 + 2) * 64 + lane]);
 #pragma unroll
-                    for (int i = 0; i < TW; ++i) {
+                    for (int i = 0; i < TW; ++i)
                         if (i < nt) {
-                            hi[i][c] = mfma(ah[i], wh, hi[i][c]);
-                            lo[i][c] = mfma(ah[i], wm, lo[i][c]);
-                            lo[i][c] = mfma(am[i], wh, lo[i][c]);
-                            lo[i][c] = mfma(am[i], wm, lo[i][c]);
-                            lo[i][c] = mfma(ah[i], wl, lo[i][c]);
-                            lo[i][c] = mfma(al[i], wh, lo[i][c]);
+                            // (mac6 of bf16x3.h written out: with the accumulators as Acc[TW][3] instead of these two arrays
+                            // every instantiation of this kernel gets another register allocation)
+                            hi[i][c] = mfma(A[i].h, W.h, hi[i][c]);
+                            lo[i][c] = mfma(A[i].h, W.m, lo[i][c]);
+                            lo[i][c] = mfma(A[i].m, W.h, lo[i][c]);
+                            lo[i][c] = mfma(A[i].m, W.m, lo[i][c]);
+                            lo[i][c] = mfma(A[i].h, W.l, lo[i][c]);
+                            lo[i][c] = mfma(A[i].l, W.h, lo[i][c]);
                         }
-                    }
                 }
             };
             // D k-blocks in flight beside the one being multiplied (straight-line code: the compiler counts its waits)
@@ -247,7 +227,7 @@ __global__ __launch_bounds__(256, 1) void bigru_persist_fwd_kernel(const PArgs P
                 const int srow = lane >> 2, sc = (lane & 3) * 4;
                 const f32x4 v = row4(scratch + srow * 20 + sc);   // same wave wrote it: LDS operations of a wave run in order
                 const int row = rt * 16 + srow;
-                if (row < G.rows)
+                if (row < G.rows)   // (longhand: st_sc1 here changes the register allocation of the four-tile instantiations)
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_out,
                                                            (int)(out_off(row, t) + 4u * (uint32_t)(slice * 16 + sc)), 0, SC1);
                 lanes_sync();
@@ -322,15 +302,14 @@ __global__ __launch_bounds__(256, 1) void bigru_persist_bwd_kernel(const BArgs P
         f32x4 a, b;
 #pragma unroll
         for (int j = 0; j < 4; ++j) { a[j] = w[(int64_t)j * h]; b[j] = w[(int64_t)(j + 4) * h]; }
-        bf16x8 ph, pm, pl;
-        split8(a, b, ph, pm, pl);
-        wfrag[(kb * 3 + 0) * 64 + lane] = __builtin_bit_cast(i32x4, ph);
-        wfrag[(kb * 3 + 1) * 64 + lane] = __builtin_bit_cast(i32x4, pm);
-        wfrag[(kb * 3 + 2) * 64 + lane] = __builtin_bit_cast(i32x4, pl);
+        const Planes p = split_gp(a, b);
+        wfrag[(kb * 3 + 0) * 64 + lane] = __builtin_bit_cast(i32x4, p.h);
+        wfrag[(kb * 3 + 1) * 64 + lane] = __builtin_bit_cast(i32x4, p.m);
+        wfrag[(kb * 3 + 2) * 64 + lane] = __builtin_bit_cast(i32x4, p.l);
     }
     __syncthreads();
     if (!mine) return;
-    const __amdgpu_buffer_rsrc_t rs_dgh = __builtin_amdgcn_make_buffer_rsrc(G.d_gh, 0, 0xffffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_dgh = rsrc_of(G.d_gh);
     const int col = slice * 16 + i16;
     // element offset of row (b, e) at time x in a [bs][T][E][width] tensor
     auto row_off = [&](int row, int x, int width) -> int64_t {
@@ -386,7 +365,7 @@ __global__ __launch_bounds__(256, 1) void bigru_persist_bwd_kernel(const BArgs P
             for (int r = 0; r < 4; ++r) scratch[(4 * g4 + r) * 20 + i16] = dgh_[gte][r];
             lanes_sync();
             const f32x4 v = row4(scratch + srow * 20 + sc);
-            if (row_s < G.rows)
+            if (row_s < G.rows)   // (longhand: st_sc1 here changes the register allocation of the h = 512 instantiation)
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_dgh, (int)(4 * (o6 + (int64_t)gte * h)), 0, SC1);
             lanes_sync();
         }
@@ -408,23 +387,19 @@ __global__ __launch_bounds__(256, 1) void bigru_persist_bwd_kernel(const BArgs P
         if (!twog_wait_counter(pub, (unsigned)(T - s) * (unsigned)n_wg, P.error, P.spin_limit, lane)) return;
         // ---- carry = direct + d_gh[rows][0 : 3h] . W_hh[:, own units]
         const uint32_t abase = (uint32_t)(4 * (row_off(min(rt * 16 + i16, G.rows - 1), t, 6 * h) + dir * 3 * h + 8 * g4));
-        f32x4 hi = {0.f, 0.f, 0.f, 0.f}, lo = {0.f, 0.f, 0.f, 0.f};
+        Acc acc;
+        acc_zero(acc);
         auto load_a = [&](int kb, f32x4 (&a)[2]) {
-            a[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_dgh, (int)(abase + 128u * kb), 0, SC1));
-            a[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_dgh, (int)(abase + 128u * kb + 16u), 0, SC1));
+            a[0] = ld_sc1(rs_dgh, abase + 128u * kb);
+            a[1] = ld_sc1(rs_dgh, abase + 128u * kb + 16u);
         };
         auto mac = [&](int kb, const f32x4 (&a)[2]) {
-            bf16x8 ah, am, al;
-            split8(a[0], a[1], ah, am, al);
-            const bf16x8 wh = __builtin_bit_cast(bf16x8, wfrag[(kb * 3 + 0) * 64 + lane]);
-            const bf16x8 wm = __builtin_bit_cast(bf16x8, wfrag[(kb * 3 + 1) * 64 + lane]);
-            const bf16x8 wl = __builtin_bit_cast(bf16x8, wfrag[(kb * 3 + 2) * 64 + lane]);
-            hi = mfma(ah, wh, hi);
-            lo = mfma(ah, wm, lo);
-            lo = mfma(am, wh, lo);
-            lo = mfma(am, wm, lo);
-            lo = mfma(ah, wl, lo);
-            lo = mfma(al, wh, lo);
+            const Planes A = split_gp(a[0], a[1]);   // (before the fragment reads: the other order is another register allocation)
+            Planes W;
+            W.h = __builtin_bit_cast(bf16x8, wfrag[(kb * 3 + 0) * 64 + lane]);
+            W.m = __builtin_bit_cast(bf16x8, wfrag[(kb * 3 + 1) * 64 + lane]);
+            W.l = __builtin_bit_cast(bf16x8, wfrag[(kb * 3 + 2) * 64 + lane]);
+            mac6(acc, A, W);
         };
         f32x4 ring[D][2];
 #pragma unroll
@@ -435,7 +410,7 @@ __global__ __launch_bounds__(256, 1) void bigru_persist_bwd_kernel(const BArgs P
             if (kb + D < NKB) load_a(kb + D, ring[kb % D]);
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) carry[r] = direct[r] + (hi[r] + lo[r]);
+        for (int r = 0; r < 4; ++r) carry[r] = direct[r] + (acc.hi[r] + acc.lo[r]);
         cur = nxt;
     }
 }
@@ -513,18 +488,12 @@ static int launch_plan(const int* E_of_type, int n_types, int bs, int hidden, in
     return n;
 }
 
-static hipError_t device_cus(int* n_cus) {
-    int dev = 0;
-    const hipError_t e = hipGetDevice(&dev);
-    return e != hipSuccess ? e : hipDeviceGetAttribute(n_cus, hipDeviceAttributeMultiprocessorCount, dev);
-}
-
 // The partition and the launch numbers of (E_of_type[n_types], bs, hidden) on n_cus compute units (<= 0: those of the current
 // device), without a launch; with n_cus > 0 without any device call. Layout of `out`: include/twog_gcn.h.
 extern "C" int twog_bigru_persistent_plan(const int32_t* E_of_type, int n_types, int bs, int hidden, int n_cus, int32_t* out) {
     if (!out || (n_types > 0 && !E_of_type)) return -2;
     if (n_cus <= 0) {
-        const hipError_t e = device_cus(&n_cus);
+        const hipError_t e = twog_device_cus(&n_cus);
         if (e != hipSuccess) return -(int)e;
     }
     for (int i = 0; i < TWOG_BIGRU_PLAN_INTS; ++i) out[i] = 0;
@@ -551,7 +520,7 @@ extern "C" int twog_bigru_persistent_plan(const int32_t* E_of_type, int n_types,
 extern "C" int twog_bigru_persistent_supported(const twog_bigru_t* types, int n_types, int bs, int hidden) {
     int n_cus = 0;
     if (n_types <= 0 || n_types > MAXG / 2) return 0;
-    if (device_cus(&n_cus) != hipSuccess) return 0;
+    if (twog_device_cus(&n_cus) != hipSuccess) return 0;
     PCombo combos[MAXC];
     PLaunch L;
     int Es[MAXG / 2];
@@ -569,7 +538,7 @@ extern "C" int twog_bigru_fwd_persistent(const twog_bigru_t* types, int n_types,
     if (n_types <= 0 || T <= 0) return 0;
     if (n_types > MAXG / 2) return -2;
     int n_cus = 0;
-    const hipError_t e = device_cus(&n_cus);
+    const hipError_t e = twog_device_cus(&n_cus);
     if (e != hipSuccess) return -(int)e;
     PArgs P;
     PLaunch L;
@@ -622,7 +591,7 @@ extern "C" int twog_bigru_fwd_persistent(const twog_bigru_t* types, int n_types,
 extern "C" int twog_bigru_bwd_persistent_supported(const twog_bigru_bwd_t* types, int n_types, int bs, int hidden) {
     int n_cus = 0;
     if (n_types <= 0 || n_types > MAXG / 2) return 0;
-    if (device_cus(&n_cus) != hipSuccess) return 0;
+    if (twog_device_cus(&n_cus) != hipSuccess) return 0;
     PCombo combos[MAXC];
     PLaunch L;
     int Es[MAXG / 2];
@@ -636,7 +605,7 @@ extern "C" int twog_bigru_bwd_persistent(const twog_bigru_bwd_t* types, int n_ty
     if (n_types <= 0 || T <= 0) return 0;
     if (n_types > MAXG / 2) return -2;
     int n_cus = 0;
-    const hipError_t e = device_cus(&n_cus);
+    const hipError_t e = twog_device_cus(&n_cus);
     if (e != hipSuccess) return -(int)e;
     BArgs P;
     PLaunch L;

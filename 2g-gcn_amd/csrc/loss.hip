@@ -14,12 +14,6 @@ namespace {
 
 struct Terms { twog_loss_t t[TWOG_LOSS_MAX_TERMS]; };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // {sum, count} of a 256-thread block -> partials[term = blockIdx.y][block = blockIdx.x], in a fixed order
 __device__ __forceinline__ void block_partial(double sum, double cnt, double* partials) {
     __shared__ double red[2][4];
@@ -60,8 +54,12 @@ __global__ __launch_bounds__(256) void loss_partial_kernel(const Terms T, double
     block_partial(sum, cnt, partials);
 }
 
-__global__ void loss_final_kernel(const Terms T, int n_terms, int n_blocks, const double* partials, double* stats,
-                                  float* losses) {
+// One thread per term adds the term's block partials in block order: {sum, count} (weighted criterion: {sum, kept weight})
+// into stats, weight * mean into losses. Shared by loss_final_kernel and wloss_final_kernel (TermT = twog_loss_t / twog_wloss_t);
+// it holds no multiply that feeds an add, so it reads the same on either side of the contraction pragma below.
+template <class TermT>
+__device__ __forceinline__ void final_body(const TermT* terms, int n_terms, int n_blocks, const double* partials, double* stats,
+                                           float* losses) {
     const int term = blockIdx.x * blockDim.x + threadIdx.x;
     if (term >= n_terms) return;
     double sum = 0.0, cnt = 0.0;
@@ -71,11 +69,16 @@ __global__ void loss_final_kernel(const Terms T, int n_terms, int n_blocks, cons
     }
     stats[term * 2] = sum;
     stats[term * 2 + 1] = cnt;
-    const twog_loss_t& L = T.t[term];
+    const TermT& L = terms[term];
     double v;
-    if (L.kind == 0) v = sum / cnt;  // 0 / 0 -> NaN like torch's mean over an empty selection
+    if (L.kind == 0) v = sum / cnt;  // 0 / 0 -> NaN like torch's mean over an empty selection (F.nll_loss(weight=): no kept weight)
     else v = cnt > 0.0 ? sum / cnt : 0.0;
     losses[term] = L.weight * (float)v;
+}
+
+__global__ void loss_final_kernel(const Terms T, int n_terms, int n_blocks, const double* partials, double* stats,
+                                  float* losses) {
+    final_body(T.t, n_terms, n_blocks, partials, stats, losses);
 }
 
 __global__ __launch_bounds__(256) void loss_bwd_kernel(const Terms T, const double* stats, const float* dlosses) {
@@ -199,7 +202,7 @@ inline bool smooth_terms_ok(const twog_smooth_loss_t* t, int n) {
 // ------------------------------------------------------------------------------------------------------------------
 // The criterion with class weights (NLL) and the positive-class weight (BCE): twog_wloss_t in include/twog_gcn.h states
 // every operation. The kernels above are left as they are (their multiply-adds may be fused; these are not), so the
-// per-element arithmetic is written out again here; the launch shape and the block reduction are shared. With cw == 1 and
+// per-element arithmetic is written out again here; the launch shape, the block reduction and the final sums are shared. With cw == 1 and
 // p <= 1 every partial sum below is the one loss_partial_kernel forms: sum + 1.0 * (-x) == sum - x.
 struct WTerms { twog_wloss_t t[TWOG_LOSS_MAX_TERMS]; };
 
@@ -238,20 +241,7 @@ __global__ __launch_bounds__(256) void wloss_partial_kernel(const WTerms T, doub
 
 __global__ void wloss_final_kernel(const WTerms T, int n_terms, int n_blocks, const double* partials, double* stats,
                                    float* losses) {
-    const int term = blockIdx.x * blockDim.x + threadIdx.x;
-    if (term >= n_terms) return;
-    double sum = 0.0, den = 0.0;
-    for (int b = 0; b < n_blocks; ++b) {
-        sum += partials[((int64_t)term * n_blocks + b) * 2];
-        den += partials[((int64_t)term * n_blocks + b) * 2 + 1];
-    }
-    stats[term * 2] = sum;
-    stats[term * 2 + 1] = den;
-    const twog_wloss_t& L = T.t[term];
-    double v;
-    if (L.kind == 0) v = sum / den;  // 0 / 0 -> NaN, as F.nll_loss(weight=) with no kept weight
-    else v = den > 0.0 ? sum / den : 0.0;
-    losses[term] = L.weight * (float)v;
+    final_body(T.t, n_terms, n_blocks, partials, stats, losses);
 }
 
 __global__ __launch_bounds__(256) void wloss_bwd_kernel(const WTerms T, const double* stats, const float* dlosses) {
@@ -296,82 +286,67 @@ inline bool wterms_ok(const twog_wloss_t* t, int n) {
     return true;
 }
 
+// The forward launches of one criterion (TermsT = Terms / SmoothTerms / WTerms; ok = its argument check): copy the terms into
+// the by-value struct, then the partial and the final sums.
+template <class TermsT, class TermT, class PartialK, class FinalK>
+int launch_fwd(bool ok, const TermT* terms, int n_terms, PartialK partial_kernel, FinalK final_kernel, double* partials,
+               double* stats, float* losses, void* stream) {
+    if (!ok) return -1;
+    if (n_terms == 0) return 0;
+    TermsT T;
+    for (int i = 0; i < n_terms; ++i) T.t[i] = terms[i];
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(partial_kernel, dim3(TWOG_LOSS_BLOCKS, n_terms), dim3(256), 0, st, T, partials);
+    TWOG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(final_kernel, dim3(1), dim3(64), 0, st, T, n_terms, TWOG_LOSS_BLOCKS, partials, stats, losses);
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
+// the backward launch of one criterion
+template <class TermsT, class TermT, class BwdK>
+int launch_bwd(bool ok, const TermT* terms, int n_terms, BwdK bwd_kernel, const double* stats, const float* dlosses,
+               void* stream) {
+    if (!ok) return -1;
+    if (n_terms == 0) return 0;
+    TermsT T;
+    for (int i = 0; i < n_terms; ++i) T.t[i] = terms[i];
+    hipLaunchKernelGGL(bwd_kernel, dim3(TWOG_LOSS_BLOCKS * 4, n_terms), dim3(256), 0, (hipStream_t)stream, T, stats, dlosses);
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int twog_weighted_loss_fwd(const twog_wloss_t* terms, int n_terms, double* partials, double* stats,
                                       float* losses, void* stream) {
-    if (!wterms_ok(terms, n_terms)) return -1;
-    if (n_terms == 0) return 0;
-    WTerms T;
-    for (int i = 0; i < n_terms; ++i) T.t[i] = terms[i];
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(wloss_partial_kernel, dim3(TWOG_LOSS_BLOCKS, n_terms), dim3(256), 0, st, T, partials);
-    TWOG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(wloss_final_kernel, dim3(1), dim3(64), 0, st, T, n_terms, TWOG_LOSS_BLOCKS, partials, stats, losses);
-    TWOG_CHECK_LAUNCH();
-    return 0;
+    return launch_fwd<WTerms>(wterms_ok(terms, n_terms), terms, n_terms, wloss_partial_kernel, wloss_final_kernel, partials,
+                              stats, losses, stream);
 }
 
 extern "C" int twog_weighted_loss_bwd(const twog_wloss_t* terms, int n_terms, const double* stats, const float* dlosses,
                                       void* stream) {
-    if (!wterms_ok(terms, n_terms)) return -1;
-    if (n_terms == 0) return 0;
-    WTerms T;
-    for (int i = 0; i < n_terms; ++i) T.t[i] = terms[i];
-    hipLaunchKernelGGL(wloss_bwd_kernel, dim3(TWOG_LOSS_BLOCKS * 4, n_terms), dim3(256), 0, (hipStream_t)stream, T, stats,
-                       dlosses);
-    TWOG_CHECK_LAUNCH();
-    return 0;
+    return launch_bwd<WTerms>(wterms_ok(terms, n_terms), terms, n_terms, wloss_bwd_kernel, stats, dlosses, stream);
 }
 
 extern "C" int twog_smooth_loss_fwd(const twog_smooth_loss_t* terms, int n_terms, double* partials, double* stats,
                                     float* losses, void* stream) {
-    if (!smooth_terms_ok(terms, n_terms)) return -1;
-    if (n_terms == 0) return 0;
-    SmoothTerms T;
-    for (int i = 0; i < n_terms; ++i) T.t[i] = terms[i];
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(smooth_partial_kernel, dim3(TWOG_LOSS_BLOCKS, n_terms), dim3(256), 0, st, T, partials);
-    TWOG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(smooth_final_kernel, dim3(1), dim3(64), 0, st, T, n_terms, TWOG_LOSS_BLOCKS, partials, stats, losses);
-    TWOG_CHECK_LAUNCH();
-    return 0;
+    return launch_fwd<SmoothTerms>(smooth_terms_ok(terms, n_terms), terms, n_terms, smooth_partial_kernel, smooth_final_kernel,
+                                   partials, stats, losses, stream);
 }
 
 extern "C" int twog_smooth_loss_bwd(const twog_smooth_loss_t* terms, int n_terms, const double* stats, const float* dlosses,
                                     void* stream) {
-    if (!smooth_terms_ok(terms, n_terms)) return -1;
-    if (n_terms == 0) return 0;
-    SmoothTerms T;
-    for (int i = 0; i < n_terms; ++i) T.t[i] = terms[i];
-    hipLaunchKernelGGL(smooth_bwd_kernel, dim3(TWOG_LOSS_BLOCKS * 4, n_terms), dim3(256), 0, (hipStream_t)stream, T, stats,
-                       dlosses);
-    TWOG_CHECK_LAUNCH();
-    return 0;
+    return launch_bwd<SmoothTerms>(smooth_terms_ok(terms, n_terms), terms, n_terms, smooth_bwd_kernel, stats, dlosses, stream);
 }
 
 extern "C" int twog_multitask_loss_fwd(const twog_loss_t* terms, int n_terms, double* partials, double* stats,
                                        float* losses, void* stream) {
-    if (!terms_ok(terms, n_terms)) return -1;
-    if (n_terms == 0) return 0;
-    Terms T;
-    for (int i = 0; i < n_terms; ++i) T.t[i] = terms[i];
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(loss_partial_kernel, dim3(TWOG_LOSS_BLOCKS, n_terms), dim3(256), 0, st, T, partials);
-    TWOG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, st, T, n_terms, TWOG_LOSS_BLOCKS, partials, stats, losses);
-    TWOG_CHECK_LAUNCH();
-    return 0;
+    return launch_fwd<Terms>(terms_ok(terms, n_terms), terms, n_terms, loss_partial_kernel, loss_final_kernel, partials, stats,
+                             losses, stream);
 }
 
 extern "C" int twog_multitask_loss_bwd(const twog_loss_t* terms, int n_terms, const double* stats, const float* dlosses,
                                        void* stream) {
-    if (!terms_ok(terms, n_terms)) return -1;
-    if (n_terms == 0) return 0;
-    Terms T;
-    for (int i = 0; i < n_terms; ++i) T.t[i] = terms[i];
-    hipLaunchKernelGGL(loss_bwd_kernel, dim3(TWOG_LOSS_BLOCKS * 4, n_terms), dim3(256), 0, (hipStream_t)stream, T, stats,
-                       dlosses);
-    TWOG_CHECK_LAUNCH();
-    return 0;
+    return launch_bwd<Terms>(terms_ok(terms, n_terms), terms, n_terms, loss_bwd_kernel, stats, dlosses, stream);
 }

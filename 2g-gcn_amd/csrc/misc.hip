@@ -397,9 +397,8 @@ extern "C" int twog_guard_outputs(const twog_guard_t* g, void* stream) {
 // Returns 0 and the stream, or a negative code when the runtime refuses (the caller then uses an ordinary stream).
 extern "C" int twog_stream_create_masked(int n_cus, void** stream_out) {
     if (!stream_out || n_cus <= 0) return -2;
-    int dev = 0, total = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -2;
-    if (hipDeviceGetAttribute(&total, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || total <= 0) return -2;
+    int total = 0;
+    if (twog_device_cus(&total) != hipSuccess || total <= 0) return -2;
     if (n_cus > total) n_cus = total;
     uint32_t mask[16] = {0};
     const int words = (total + 31) / 32;

@@ -217,12 +217,6 @@ __device__ __forceinline__ int lanes_below(unsigned long long mask) {
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
 
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // precision, recall and F1 with the reference's three zero-denominator rules (metrics.py:49-60). Every operation is one
 // correctly rounded fp64 division, product or sum of the reference's own expression; no multiply feeds an add, and
 // contraction is off so that it stays that way.

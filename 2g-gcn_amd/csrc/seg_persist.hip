@@ -29,7 +29,7 @@
 // gru_persist.hip); the reduction of a product is split over the four waves of a workgroup by k-blocks and combined
 // through LDS in wave order: fixed summation order, bit-reproducible. Weights are streamed from L2 / Infinity Cache
 // every step (704 KB per slice and direction at h = 512: more than LDS holds), 160-192 KB per workgroup and step.
-#include "twog_common.h"
+#include "bf16x3.h"
 #include "persist_common.h"
 
 // The wave index is read through a SCALAR register: every per-wave condition (`kb = wave + 4 j < nkb`: is this k-block slot
@@ -45,12 +45,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((__vector_size__(4 * sizeof(unsigned))));
-
-constexpr int SC1 = 16;          // aux bits of the buffer instructions: sc1
 constexpr int RS = 20;           // floats per row of a 16 x 16 result tile in LDS (16-byte aligned, 4 banks apart)
 constexpr int CNT_STRIDE = 32;   // uint32 between two counters (a 128-byte line each)
 constexpr int SYNC_WORDS = 4096; // uint32 of the caller's sync buffer; the error word is the last line
@@ -82,66 +76,18 @@ struct SegArgs {
     unsigned* error;
 };
 
-__device__ __forceinline__ uint32_t pack_hi16(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302); }
-
-// eight consecutive fp32 values -> the three bf16 planes of an MFMA fragment (element j = value j), by truncation: exact
-struct Planes { bf16x8 h, m, l; };
-__device__ __forceinline__ Planes split8(const f32x4 a, const f32x4 b) {
+// The exact 3 x bf16 split of the streamed fragments (bf16x3.h), behind this file's timing probe.
+__device__ __forceinline__ Planes split_sp(const f32x4 a, const f32x4 b) {
 #ifdef TWOG_SP_PROBE_NOSPLIT   // timing probe only (wrong results): what the split of the streamed fragments costs a step
     { Planes q; q.h = __builtin_bit_cast(bf16x8, a); q.m = __builtin_bit_cast(bf16x8, b); q.l = q.h; return q; }
 #endif
-    uint32_t x[8], r1[8], r2[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float f0 = i < 4 ? a[i] : b[i - 4];
-        x[i] = __float_as_uint(f0);
-        const float f1 = f0 - __uint_as_float(x[i] & 0xffff0000u);
-        r1[i] = __float_as_uint(f1);
-        r2[i] = __float_as_uint(f1 - __uint_as_float(r1[i] & 0xffff0000u));
-    }
-    Planes p;
-    p.h = __builtin_bit_cast(bf16x8, i32x4{(int)pack_hi16(x[0], x[1]), (int)pack_hi16(x[2], x[3]), (int)pack_hi16(x[4], x[5]), (int)pack_hi16(x[6], x[7])});
-    p.m = __builtin_bit_cast(bf16x8, i32x4{(int)pack_hi16(r1[0], r1[1]), (int)pack_hi16(r1[2], r1[3]), (int)pack_hi16(r1[4], r1[5]), (int)pack_hi16(r1[6], r1[7])});
-    p.l = __builtin_bit_cast(bf16x8, i32x4{(int)pack_hi16(r2[0], r2[1]), (int)pack_hi16(r2[2], r2[3]), (int)pack_hi16(r2[4], r2[5]), (int)pack_hi16(r2[6], r2[7])});
-    return p;
-}
-
-struct Acc { f32x4 hi, lo; };
-__device__ __forceinline__ void acc_zero(Acc& c) { c.hi = f32x4{0.f, 0.f, 0.f, 0.f}; c.lo = f32x4{0.f, 0.f, 0.f, 0.f}; }
-// c += A B with A, B given as planes: h.h into `hi`, the five small products into `lo`
-__device__ __forceinline__ void mac6(Acc& c, const Planes& a, const Planes& b) {
-    c.hi = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.h, c.hi, 0, 0, 0);
-    c.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.m, c.lo, 0, 0, 0);
-    c.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.m, b.h, c.lo, 0, 0, 0);
-    c.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.m, b.m, c.lo, 0, 0, 0);
-    c.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.l, c.lo, 0, 0, 0);
-    c.lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.l, b.h, c.lo, 0, 0, 0);
-}
-
-// the same six products into ONE accumulator
-__device__ __forceinline__ void mac6_one(f32x4& c, const Planes& a, const Planes& b) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.h, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.m, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.m, b.h, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.m, b.m, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.l, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.l, b.h, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ f32x4 ld_sc1(const __amdgpu_buffer_rsrc_t rs, uint32_t byte_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, SC1));
-}
-__device__ __forceinline__ void st_sc1(const __amdgpu_buffer_rsrc_t rs, uint32_t byte_off, const f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, (int)byte_off, 0, SC1);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const float* p) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, 0xffffffff, 0x00020000);
+    return split8(a, b);
 }
 
 // weight fragment: lane l holds W[row0 + (l & 15)][k0 + 8 (l >> 4) + j], j = 0..7
 __device__ __forceinline__ Planes load_w(const float* w, int64_t ld, int row0, int k0, int lane) {
     const float* p = w + (int64_t)(row0 + (lane & 15)) * ld + k0 + 8 * (lane >> 4);
-    return split8(*reinterpret_cast<const f32x4*>(p), *reinterpret_cast<const f32x4*>(p + 4));
+    return split_sp(*reinterpret_cast<const f32x4*>(p), *reinterpret_cast<const f32x4*>(p + 4));
 }
 
 // raw (fp32) weight fragments, kept in registers for the whole sequence: lane l holds W[row0 + (l & 15)][k0 + 8 (l >> 4) + j]
@@ -398,20 +344,20 @@ __device__ __forceinline__ bool p1_step(const SegArgs& P, const Geo& G, int s, f
                 if (kb < nkb) {
                     Planes A[MT];
 #pragma unroll
-                    for (int i = 0; i < MT; ++i) A[i] = split8(buf[jj][i][0], buf[jj][i][1]);
+                    for (int i = 0; i < MT; ++i) A[i] = split_sp(buf[jj][i][0], buf[jj][i][1]);
                     {
-                        const Planes B = split8(Wr[j][0].a, Wr[j][0].b);
+                        const Planes B = split_sp(Wr[j][0].a, Wr[j][0].b);
 #pragma unroll
                         for (int i = 0; i < MH; ++i) mac6(a_sh[i], A[i], B);
                     }
                     {
-                        const Planes B = split8(Wr[j][1].a, Wr[j][1].b);
+                        const Planes B = split_sp(Wr[j][1].a, Wr[j][1].b);
 #pragma unroll
                         for (int i = 0; i < MO; ++i) mac6(a_so[i], A[MH + i], B);
                     }
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
-                        const Planes B = split8(Wr[j][2 + c].a, Wr[j][2 + c].b);
+                        const Planes B = split_sp(Wr[j][2 + c].a, Wr[j][2 + c].b);
 #pragma unroll
                         for (int i = 0; i < MK; ++i) mac6(a_g[i][c], A[(RK == 0 ? 0 : MH) + i], B);
                     }
@@ -628,10 +574,10 @@ __device__ __forceinline__ bool p2_step(const SegArgs& P, const Geo& G, int s, f
     k_stream<KW2, MK, TWOG_SP_P2_CH>(rs_mg, off, nkb, wave, [&](int j, const f32x4 (&A)[MK][2]) {
         Planes Ap[MK];
 #pragma unroll
-        for (int i = 0; i < MK; ++i) Ap[i] = split8(A[i][0], A[i][1]);
+        for (int i = 0; i < MK; ++i) Ap[i] = split_sp(A[i][0], A[i][1]);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const Planes B = split8(Wr[j][c].a, Wr[j][c].b);
+            const Planes B = split_sp(Wr[j][c].a, Wr[j][c].b);
 #pragma unroll
             for (int i = 0; i < MK; ++i) mac6_one(acc[i][c], Ap[i], B);
         }
@@ -838,7 +784,7 @@ __device__ __forceinline__ Planes load_wk(const float* w, int64_t ld, int k0, in
     f32x4 a, b;
 #pragma unroll
     for (int j = 0; j < 4; ++j) { a[j] = p[(int64_t)j * ld]; b[j] = p[(int64_t)(j + 4) * ld]; }
-    return split8(a, b);
+    return split_sp(a, b);
 }
 
 // ---- Q1 of receiver kind RK: one step
@@ -889,10 +835,10 @@ __device__ __forceinline__ bool q1_step(const SegBwdArgs& P, const Geo& G, int s
         k_stream<KW3, MK, 3>(rs_gi, off, nkb, wave, [&](int j, const f32x4 (&A)[MK][2]) {
             Planes Ap[MK];
 #pragma unroll
-            for (int i = 0; i < MK; ++i) Ap[i] = split8(A[i][0], A[i][1]);
+            for (int i = 0; i < MK; ++i) Ap[i] = split_sp(A[i][0], A[i][1]);
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk) {
-                const Planes B = split8(Wr[j][blk].a, Wr[j][blk].b);
+                const Planes B = split_sp(Wr[j][blk].a, Wr[j][blk].b);
 #pragma unroll
                 for (int i = 0; i < MK; ++i) mac6_one(acc[i][blk], Ap[i], B);
             }
@@ -1068,9 +1014,9 @@ __device__ __forceinline__ bool q2_step(const SegBwdArgs& P, const Geo& G, int s
 #endif
 #ifdef TWOG_SP_Q2_X3   // (experiment, as in P2: 3 x bf16 products with one accumulator)
             k_stream<KW2, MK, TWOG_SP_Q2_CH>(rs_p, off, nkb, wave, [&](int j, const f32x4 (&A)[MK][2]) {
-                const Planes B = split8(We[j].a, We[j].b);
+                const Planes B = split_sp(We[j].a, We[j].b);
 #pragma unroll
-                for (int i = 0; i < MK; ++i) mac6_one(acc[i], split8(A[i][0], A[i][1]), B);
+                for (int i = 0; i < MK; ++i) mac6_one(acc[i], split_sp(A[i][0], A[i][1]), B);
             });
 #else
             k_stream<KW2, MK>(rs_p, off, nkb, wave, [&](int j, const f32x4 (&A)[MK][2]) {
@@ -1218,9 +1164,9 @@ __device__ __forceinline__ bool q2_step(const SegBwdArgs& P, const Geo& G, int s
         }
 #ifdef TWOG_SP_Q2_X3
         k_stream<KW3, MK, TWOG_SP_Q2_CH>(rs_gh, off, nkb, wave, [&](int j, const f32x4 (&A)[MK][2]) {
-            const Planes B = split8(Wh[j].a, Wh[j].b);
+            const Planes B = split_sp(Wh[j].a, Wh[j].b);
 #pragma unroll
-            for (int i = 0; i < MK; ++i) mac6_one(acc[i], split8(A[i][0], A[i][1]), B);
+            for (int i = 0; i < MK; ++i) mac6_one(acc[i], split_sp(A[i][0], A[i][1]), B);
         });
 #else
         k_stream<KW3, MK>(rs_gh, off, nkb, wave, [&](int j, const f32x4 (&A)[MK][2]) {
@@ -1377,21 +1323,13 @@ bool make_plan(const twog_segrnn_t& S, int n_cus, SegPlan& pl) {
     return pl.grid <= n_cus && pl.grid % 8 == 0;
 }
 
-int device_cus(int& n_cus) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return -(int)e;
-    e = hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return e == hipSuccess ? 0 : -(int)e;
-}
-
 }  // namespace
 
 // 2 if twog_segrnn_fwd_persistent serves this shape on the current device (and is the faster path: it is only served
 // where a chunk's rows fit three 16-row tiles, i.e. small batches), 0 if not.
 extern "C" int twog_segrnn_persistent_supported(const twog_segrnn_t* desc) {
     int n_cus = 0;
-    if (!desc || device_cus(n_cus) != 0) return 0;
+    if (!desc || twog_device_cus(&n_cus) != hipSuccess) return 0;
     SegPlan pl;
     return make_plan(*desc, n_cus, pl) ? 2 : 0;
 }
@@ -1405,8 +1343,8 @@ extern "C" int twog_segrnn_fwd_persistent(const twog_segrnn_t* desc, void* sync,
     if (!desc || !sync) return -2;
     const twog_segrnn_t& S = *desc;
     int n_cus = 0;
-    int rc = device_cus(n_cus);
-    if (rc) return rc;
+    const hipError_t e = twog_device_cus(&n_cus);
+    if (e != hipSuccess) return -(int)e;
     SegPlan pl;
     if (!make_plan(S, n_cus, pl)) return -2;
     SegArgs P;
@@ -1470,7 +1408,7 @@ size_t bwd_lds(const twog_segrnn_t& S, const SegPlan& pl) {
 // shape is not served
 extern "C" size_t twog_segrnn_bwd_persistent_scratch_bytes(const twog_segrnn_t* desc) {
     int n_cus = 0;
-    if (!desc || device_cus(n_cus) != 0) return 0;
+    if (!desc || twog_device_cus(&n_cus) != hipSuccess) return 0;
     SegPlan pl;
     if (!make_plan(*desc, n_cus, pl)) return 0;
     const twog_segrnn_t& S = *desc;
@@ -1488,8 +1426,8 @@ extern "C" int twog_segrnn_bwd_persistent(const twog_segrnn_t* desc, const twog_
     const twog_segrnn_t& S = *desc;
     const twog_segrnn_bwd_t& B = *bdesc;
     int n_cus = 0;
-    int rc = device_cus(n_cus);
-    if (rc) return rc;
+    const hipError_t e = twog_device_cus(&n_cus);
+    if (e != hipSuccess) return -(int)e;
     SegPlan pl;
     if (!make_plan(S, n_cus, pl)) return -2;
     if (scratch_bytes < twog_segrnn_bwd_persistent_scratch_bytes(desc)) return -2;

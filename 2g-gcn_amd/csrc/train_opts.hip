@@ -11,12 +11,6 @@
 
 namespace {
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // fixed-order block sum (256 threads): waves by shuffle, then wave 0 adds the four wave sums in index order
 __device__ __forceinline__ double block_sum_f64(double v, double* red) {
     v = wave_sum_f64(v);

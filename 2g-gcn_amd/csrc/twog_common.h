@@ -3,15 +3,32 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <cstdlib>
 #include "../../include/twog_gcn.h"
 
 #define TWOG_WAVE 64
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));  // native vector: loads/stores stay in registers (SROA)
 
 #define TWOG_CHECK_LAUNCH()                         \
     do {                                            \
         hipError_t e_ = hipGetLastError();          \
         if (e_ != hipSuccess) return -(int)e_;      \
     } while (0)
+
+// An integer switch of the environment: atoi of the variable when it is set (set but empty reads as 0), dflt when it is not.
+// Reads on every call; a site that wants one reading per process keeps the result in a `static const`.
+inline int twog_env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+// compute units of the current device
+inline hipError_t twog_device_cus(int* n) {
+    int dev = 0;
+    const hipError_t e = hipGetDevice(&dev);
+    return e != hipSuccess ? e : hipDeviceGetAttribute(n, hipDeviceAttributeMultiprocessorCount, dev);
+}
 
 // Raises a kernel's dynamic-LDS limit once per device (function attributes are per device; the flag word is one bit per
 // device ordinal, so a process that drives several GPUs -- or several host threads -- stays correct).
@@ -80,6 +97,16 @@ __device__ __forceinline__ int64_t twog_row_off(const twog_rows_t& m, int r) {
 __device__ __forceinline__ float* twog_row_ptr(const twog_rows_t& m, int r) { return m.ptr + twog_row_off(m, r); }
 
 __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ int wave_sum_int(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;

@@ -435,7 +435,7 @@ def test_saved_state_is_released_by_backward_not_by_the_loss(fake_backend):
 
 def test_x3_operand_split_is_exact():
     """The 128x128 GEMM class multiplies fp32 operands on the bf16 matrix cores after splitting every element into three
-    bf16 values by truncation (csrc/gemm_f32.hip, split3): h = top 8 significant bits, m = the next 8, l = the rest. The
+    bf16 values by truncation (csrc/bf16x3.h, split3): h = top 8 significant bits, m = the next 8, l = the rest. The
     arithmetic restated in numpy: the three chunks are exactly representable in bf16 (low 16 bits zero) and add up to the
     element EXACTLY -- so the six products the kernel keeps differ from the exact product only by the three dropped
     cross terms (m l, l m, l l: <= 2^-21 relative in the worst case, ~2^-24 on average)."""

@@ -1835,7 +1835,7 @@ print('OK')
 
 
 def test_gemm_x3_nonfinite_operands_stay_nonfinite(K):
-    """Documented difference of the X3 kernels (csrc/gemm_f32.hip, split3): an operand of +-Inf gives NaN where an fp32
+    """Documented difference of the X3 kernels (csrc/bf16x3.h, split3): an operand of +-Inf gives NaN where an fp32
     multiply gives +-Inf (the split subtracts Inf - Inf); a NaN stays a NaN. Either way the affected outputs are NOT finite
     -- a broken run cannot look healthy -- and every other output is untouched."""
     g = torch.Generator().manual_seed(3)
