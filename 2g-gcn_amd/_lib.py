@@ -194,6 +194,22 @@ class Ranges(C.Structure):  # twog_ranges_t
                 ('pad_', C.c_int32)]
 
 
+VITERBI_CHUNK = 16   # TWOG_VITERBI_CHUNK
+VITERBI_ROUTES = ('lds', 'workspace')   # TWOG_VITERBI_ROUTE_LDS, TWOG_VITERBI_ROUTE_WORKSPACE
+
+
+def viterbi_workspace(lib, bs, n_classes, T, E):
+    """twog_viterbi_workspace of the loaded library `lib`: (route, bytes), route 'lds' or 'workspace'. No device is touched.
+    ValueError beyond the limits of twog_viterbi_limits."""
+    nbytes = C.c_size_t(0)
+    rc = lib.twog_viterbi_workspace(int(bs), int(n_classes), int(T), int(E), C.byref(nbytes))
+    if rc == -2:
+        raise ValueError(f'the Viterbi decode takes up to 64 classes and 4096 model steps, not {n_classes} and {T}')
+    if rc < 0:
+        raise RuntimeError(f'twog_viterbi_workspace failed with code {rc}')
+    return VITERBI_ROUTES[rc], nbytes.value
+
+
 BIGRU_PLAN_HEAD, BIGRU_PLAN_MAX_COMBOS = 8, 32   # TWOG_BIGRU_PLAN_HEAD, TWOG_BIGRU_PLAN_MAX_COMBOS
 BIGRU_PLAN_INTS = BIGRU_PLAN_HEAD + 4 * BIGRU_PLAN_MAX_COMBOS   # TWOG_BIGRU_PLAN_INTS
 
@@ -366,6 +382,10 @@ SIGNATURES = {
     'twog_segment_f1_limits': [C.POINTER(C.c_int), C.POINTER(C.c_int)],
     'twog_segment_edit': [_P, _P, _I, _I, _I, _L, _I, _L, _I, _P, _P, _P, _P, _P, _P],
     'twog_segment_edit_limits': [C.POINTER(C.c_int)],
+    'twog_viterbi_limits': [C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    'twog_viterbi_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
+    'twog_viterbi_decode': [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, C.c_size_t, _P],
+    'twog_transition_counts': [_P, _I, _I, _I, _I, _I, _L, _P, _P],
 }
 
 _lib = None

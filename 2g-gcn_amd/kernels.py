@@ -1755,6 +1755,79 @@ class HipKernels:
                     'twog_segment_edit')
         return score, distance, n_true, n_pred, valid, packed
 
+    # ---------------------------------------------------------------- Viterbi decode under a transition model
+    def viterbi_limits(self):
+        """(largest class count, most model steps) viterbi_decode takes."""
+        max_classes, max_steps = C.c_int(0), C.c_int(0)
+        self._check(self.lib.twog_viterbi_limits(C.byref(max_classes), C.byref(max_steps)), 'twog_viterbi_limits')
+        return max_classes.value, max_steps.value
+
+    def viterbi_route(self, bs, num_classes, T, E):
+        """(route, workspace bytes) of a decode of this shape: 'lds' keeps the back-pointers in LDS, 'workspace' in device
+        memory. Launch-free; ValueError beyond viterbi_limits."""
+        return L.viterbi_workspace(self.lib, bs, num_classes, T, E)
+
+    def viterbi_decode(self, logp, transitions, initial=None, lengths=None, downsampling=1, target_steps=None):
+        """The best label path of every (clip, entity) sequence of (bs, C, T, E) log-probabilities under fp32 (C, C)
+        transition scores (row = from) and optional (C,) initial scores, as include/twog_gcn.h defines it at
+        twog_viterbi_decode. lengths: int64 (bs,) on the device, in model steps, or None. Returns (labels int64 (bs,
+        target_steps, E), upsampled like predict_labels, and score fp32 (bs, E)). ValueError beyond viterbi_limits,
+        before any launch."""
+        assert logp.dim() == 4 and logp.dtype == torch.float32
+        logp = logp.contiguous()
+        bs, Cn, T, E = logp.shape
+        max_classes, max_steps = self.viterbi_limits()
+        if Cn > max_classes or T > max_steps:
+            raise ValueError(f'viterbi_decode takes up to {max_classes} classes and {max_steps} model steps, not {Cn} and {T}')
+        assert transitions.shape == (Cn, Cn) and transitions.dtype == torch.float32 and transitions.is_contiguous() \
+            and transitions.device == logp.device, (tuple(transitions.shape), transitions.dtype)
+        if initial is not None:
+            assert initial.shape == (Cn,) and initial.dtype == torch.float32 and initial.is_contiguous() \
+                and initial.device == logp.device
+        if lengths is not None:
+            assert lengths.shape == (bs,) and lengths.dtype == torch.int64 and lengths.is_contiguous() \
+                and lengths.device == logp.device, (tuple(lengths.shape), lengths.dtype, lengths.device)
+        target_steps = T * int(downsampling) if target_steps is None else int(target_steps)
+        labels = torch.empty(bs, target_steps, E, dtype=torch.int64, device=logp.device)
+        score = torch.empty(bs, E, dtype=torch.float32, device=logp.device)
+        if bs == 0 or E == 0 or T == 0:
+            return labels, score
+        _, ws_bytes = self.viterbi_route(bs, Cn, T, E)
+        ws = self.workspace(ws_bytes, logp.device, 'viterbi') if ws_bytes else None
+        self._check(self.lib.twog_viterbi_decode(logp.data_ptr(), bs, Cn, T, E, transitions.data_ptr(), _ptr(initial),
+                                                 _ptr(lengths), max(1, int(downsampling)), target_steps, labels.data_ptr(),
+                                                 score.data_ptr(), _ptr(ws), ws_bytes, self._stream()), 'twog_viterbi_decode')
+        return labels, score
+
+    def transition_counts(self, targets, num_classes, stride, ignore_index, counts):
+        """ADDS to counts int64 (C, C) (row = from, column = to) the label pairs (targets[b, k * stride, e], targets[b,
+        (k + 1) * stride, e]) of an int64 (bs, T_tgt, E) tensor, in place; a pair with a label equal to ignore_index or
+        outside [0, C) is skipped."""
+        assert targets.dim() == 3 and targets.dtype == torch.int64 and targets.is_contiguous()
+        assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.shape == (num_classes, num_classes)
+        assert counts.device == targets.device
+        bs, T_tgt, E = targets.shape
+        if bs and E:
+            self._check(self.lib.twog_transition_counts(targets.data_ptr(), bs, T_tgt, E, int(num_classes), int(stride),
+                                                        int(ignore_index), counts.data_ptr(), self._stream()),
+                        'twog_transition_counts')
+        return counts
+
+
+def viterbi_decode(logp, transitions, initial=None, lengths=None, downsampling=1, target_steps=None):
+    """`get_kernels().viterbi_decode`: see HipKernels.viterbi_decode."""
+    return get_kernels().viterbi_decode(logp, transitions, initial, lengths, downsampling, target_steps)
+
+
+def viterbi_limits():
+    """`get_kernels().viterbi_limits()`: (largest class count, most model steps)."""
+    return get_kernels().viterbi_limits()
+
+
+def transition_counts(targets, num_classes, stride, ignore_index, counts):
+    """`get_kernels().transition_counts`: see HipKernels.transition_counts."""
+    return get_kernels().transition_counts(targets, num_classes, stride, ignore_index, counts)
+
 
 def segment_f1_words(n_seq, K):
     """8-byte words of the packed result of segment_f1: n_seq * K fp64, then (3 * n_seq * K + n_seq) int32."""

@@ -15,6 +15,10 @@ sums on the device over a whole test set and merges over ranks by a sum.
 
 The segmental edit score (twog_segment_edit) is the third number an action-segmentation model is reported with; the
 reference does not compute it, so its definition is stated at `edit_score_per_example`.
+
+`ViterbiDecoder` replaces the per-step argmax by the best label path under a label-transition model (twog_viterbi_decode;
+the reference has no such decode either, `viterbi_labels` states the definition); `transition_counts`,
+`transition_log_probs` and `switch_penalty` make the model. `process_output` and `EvaluationAccumulator` take a decoder.
 """
 from collections import namedtuple
 
@@ -49,16 +53,140 @@ def predict_labels(output: torch.Tensor, target: torch.Tensor = None, downsampli
     return get_kernels().predict_labels(output, max(1, int(downsampling)), steps)
 
 
-def process_output(outputs, downsampling: int = 1, targets=None, index_to_name=None):
+def process_output(outputs, downsampling: int = 1, targets=None, index_to_name=None, decoder=None, lengths=None):
     """predict.py:186-202 for predictions: list over batches of lists of (bs, C, T, E) outputs -> {index: int64 labels
-    (N, T, E) on the device} (the reference returns numpy arrays of the same values)."""
+    (N, T, E) on the device} (the reference returns numpy arrays of the same values). decoder: a `ViterbiDecoder` (one for
+    every output, or a dict {key: decoder}; an output without one keeps the argmax) that replaces the per-step argmax;
+    lengths: with a decoder, one int64 (bs,) device tensor of model steps per batch, or None."""
     per_index = {}
     for bi, output in enumerate(outputs):
         for i, tensor in enumerate(output):
             tgt = None if targets is None else targets[bi][i]
             key = index_to_name[i] if index_to_name is not None else i
-            per_index.setdefault(key, []).append(predict_labels(tensor, tgt, downsampling))
+            dec = decoder.get(key) if isinstance(decoder, dict) else decoder
+            if dec is None:
+                labels = predict_labels(tensor, tgt, downsampling)
+            else:
+                labels = dec(tensor, tgt, downsampling, None if lengths is None else lengths[bi])
+            per_index.setdefault(key, []).append(labels)
     return {k: torch.cat(v, 0) for k, v in per_index.items()}
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# Viterbi decode under a label-transition model (twog_viterbi_decode) and the statistics such a model is made from
+def transition_counts(targets, num_classes: int, stride: int = 1, ignore_index: int = -1, out=None) -> torch.Tensor:
+    """int64 (C, C) counts (row = from, column = to) of the label pairs (targets[b, k * stride, e], targets[b, (k + 1) *
+    stride, e]) of a (bs, T, E) or (bs, T) label tensor on the device: the transitions at the model's rate when `stride`
+    is the loader's downsampling. A pair that touches `ignore_index` or a label outside [0, C) is not counted. With `out`
+    the counts are ADDED to it, so that a pass over a loader accumulates (as `losses.class_counts` does); no host
+    synchronisation either way."""
+    K = get_kernels()
+    targets = targets.to(torch.int64)
+    if targets.ndim == 2:
+        targets = targets.unsqueeze(-1)
+    if targets.ndim != 3:
+        raise ValueError(f'labels (bs, T) or (bs, T, E) expected, not {tuple(targets.shape)}')
+    if int(stride) < 1:
+        raise ValueError(f'stride must be at least 1, not {stride}')
+    max_classes = K.viterbi_limits()[0]
+    if num_classes > max_classes:
+        raise ValueError(f'transition_counts takes up to {max_classes} classes, not {num_classes}')
+    if out is None:
+        out = K.zeros(num_classes, num_classes, dtype=torch.int64, device=targets.device)
+    return K.transition_counts(targets.contiguous(), int(num_classes), int(stride), int(ignore_index), out)
+
+
+def transition_log_probs(counts, smoothing: float = 1.0) -> torch.Tensor:
+    """fp32 (C, C) log((n + s) / (row sum + C * s)) of transition counts, computed in fp64 on the host from ONE copy of
+    the counts and rounded to fp32 once; returned on the device of `counts`. With smoothing 0 an unseen transition is
+    -inf (forbidden); a row with no counts at all (and no smoothing) is all zeros: nothing is known about leaving it."""
+    device = counts.device if isinstance(counts, torch.Tensor) else None
+    n = (counts.cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)).astype(np.float64)
+    if n.ndim != 2 or n.shape[0] != n.shape[1]:
+        raise ValueError(f'square counts expected, not {n.shape}')
+    s = float(smoothing)
+    den = n.sum(1, keepdims=True) + n.shape[0] * s
+    with np.errstate(divide='ignore', invalid='ignore'):
+        logp = np.log((n + s) / den)
+    logp = np.where(den > 0, logp, 0.0).astype(np.float32)
+    out = torch.from_numpy(logp)
+    return out.to(device) if device is not None else out
+
+
+def switch_penalty(num_classes: int, penalty: float, device=None) -> torch.Tensor:
+    """fp32 (C, C) transition scores with 0 on the diagonal and -penalty elsewhere: the model that needs no training
+    data; every change of label costs `penalty` nats."""
+    a = np.full((num_classes, num_classes), -float(penalty), dtype=np.float32)
+    np.fill_diagonal(a, 0.0)
+    out = torch.from_numpy(a)
+    return out.to(device) if device is not None else out
+
+
+def viterbi_labels(output, transitions, initial=None, target=None, downsampling: int = 1, lengths=None):
+    """(labels int64 (bs, T_target, E), score fp32 (bs, E)): the best label path of every sequence = (clip b, entity e) of
+    (bs, C, T, E) log-probabilities, with T_target as `predict_labels` has it. `transitions` A fp32 (C, C) (row = from,
+    column = to), `initial` pi fp32 (C,) or None (all zero), `lengths` int64 (bs,) on the device in model steps (clamped to
+    [0, T]; None means T), all on the output's device. With logp[t, c] = output[b, c, t, e] and L the length, in fp32 with
+    one rounding per add, nothing fused or reordered:
+
+        d[0][c] = logp[0,c] + pi[c]
+        m[t][c] = max over c' of (d[t-1][c'] + A[c',c])      psi[t][c] = the SMALLEST c' that attains it
+        d[t][c] = m[t][c] + logp[t,c]                        (t = 1 .. L-1)
+        y[L-1]  = the smallest c attaining max d[L-1][.]     y[t-1] = psi[t][y[t]]      score = max d[L-1][.]
+
+    A candidate replaces the running best only when it is strictly greater: that is the tie-break (among paths of equal
+    score the smallest one compared from the last step backwards) and it decides what -inf does; -inf entries of A
+    (forbidden transitions) are in contract, NaN is not (it still gives labels in [0, C)). labels[b, t', e] = y[min(t' //
+    downsampling, L - 1)]; a length of 0 gives label 0 everywhere and score 0.0. tests/viterbi_ref.py is this definition
+    in numpy, and the kernel (twog_viterbi_decode) meets it bit for bit. ValueError beyond `kernels.viterbi_limits()`."""
+    if output.ndim != 4:
+        raise RuntimeError(f'Number of dimensions for output is {output.ndim}')  # predict.py:66-67
+    downsampling = max(1, int(downsampling))
+    steps = output.shape[-2] if (downsampling <= 1 or target is None) else target.shape[-2]   # as predict_labels
+    return get_kernels().viterbi_decode(output, transitions, initial, lengths, downsampling, steps)
+
+
+class ViterbiDecoder:
+    """The sequence-level replacement of `predict_labels`: the best label path of every (clip, entity) under fp32 (C, C)
+    transition scores (row = from, column = to; -inf forbids a transition) and optional (C,) initial scores, decoded on
+    the device by twog_viterbi_decode (`viterbi_labels` states the recurrence and its tie-break). The tensors are kept
+    on the device in fp32 and moved once to the device of the first output decoded.
+
+    decoder(output, target=None, downsampling=1, lengths=None) returns what `predict_labels` returns for the same
+    arguments, int64 (bs, T_target, E); lengths int64 (bs,) on the device gives the valid model steps of every clip, the
+    labels behind them repeat the last decoded one. `last_score` holds the fp32 (bs, E) path scores of the last call."""
+
+    def __init__(self, transitions, initial=None):
+        as_f32 = lambda v: torch.as_tensor(v).detach().to(torch.float32).contiguous()
+        self.transitions = as_f32(transitions)
+        if self.transitions.ndim != 2 or self.transitions.shape[0] != self.transitions.shape[1]:
+            raise ValueError(f'transitions must be (C, C), not {tuple(self.transitions.shape)}')
+        self.num_classes = self.transitions.shape[0]
+        self.initial = None if initial is None else as_f32(initial)
+        if self.initial is not None and self.initial.shape != (self.num_classes,):
+            raise ValueError(f'initial must be ({self.num_classes},), not {tuple(self.initial.shape)}')
+        self.last_score = None
+
+    def __call__(self, output: torch.Tensor, target: torch.Tensor = None, downsampling: int = 1, lengths=None):
+        if output.ndim != 4:
+            raise RuntimeError(f'Number of dimensions for output is {output.ndim}')  # predict.py:66-67
+        downsampling = max(1, int(downsampling))
+        steps = output.shape[-2] if (downsampling <= 1 or target is None) else target.shape[-2]   # as predict_labels
+        return self.decode(output, downsampling, steps, lengths)
+
+    def decode(self, output, downsampling, steps, lengths=None):
+        """The labels at `steps` target steps, int64 (bs, steps, E): step t' reads model step t' // downsampling, as
+        twog_eval_update evaluates it."""
+        if output.shape[1] != self.num_classes:
+            raise ValueError(f'the output has {output.shape[1]} classes, the transition model {self.num_classes}')
+        if self.transitions.device != output.device:
+            self.transitions = self.transitions.to(output.device)
+            self.initial = None if self.initial is None else self.initial.to(output.device)
+        if lengths is not None:
+            lengths = lengths.to(device=output.device, dtype=torch.int64).contiguous()
+        labels, self.last_score = get_kernels().viterbi_decode(output, self.transitions, self.initial, lengths,
+                                                               int(downsampling), int(steps))
+        return labels
 
 
 def f1_at_k(y_true, y_pred, num_classes: int, *, overlap: float, ignore_value: float = None) -> float:
@@ -444,10 +572,15 @@ class EvaluationAccumulator:
     'thread' for a batch it cannot take (an overlap <= 0, more steps than its limit). `last_f1_route` names what the last
     update ran. edit: also keep, per name, the sum of the per-sequence segmental edit scores (twog_segment_edit on the same
     labels, `bg_label` as in `edit_score_per_example`) and of its valid sequences; `result()[name]['edit']` is their
-    ratio. That metric has one route: a batch with more steps than `segment_edit_limits()` is a ValueError."""
+    ratio. That metric has one route: a batch with more steps than `segment_edit_limits()` is a ValueError.
+    decoder: a `ViterbiDecoder` for every name, or a list with one (or None) per name. A name with a decoder is evaluated on
+    the decoded labels instead of the per-step argmax: twog_viterbi_decode, `_select_steps`, twog_confusion_counts, and
+    the F1 and edit kernels on those labels; `update(..., lengths=)` passes the valid model steps of the clips to it. A
+    step_index entry beyond the last target step is counted in the second error counter and evaluated as padding, as
+    twog_eval_update does. Without a decoder nothing changes."""
 
     def __init__(self, names, num_classes, downsampling: int = 1, overlaps=(0.1, 0.25, 0.5), f1_route: str = 'thread',
-                 edit: bool = False, bg_label=None):
+                 edit: bool = False, bg_label=None, decoder=None):
         if f1_route not in ('thread', 'workgroup'):
             raise ValueError(f"f1_route must be 'thread' or 'workgroup', not {f1_route!r}")
         self.f1_route = f1_route
@@ -460,6 +593,12 @@ class EvaluationAccumulator:
         self.overlaps = tuple(float(o) for o in overlaps)
         self.edit = bool(edit)
         self.bg_label = bg_label
+        self.decoders = list(decoder) if isinstance(decoder, (list, tuple)) else [decoder] * len(self.names)
+        if len(self.decoders) != len(self.names):
+            raise ValueError('decoder must be one decoder or one (or None) per name')
+        for name, dec, c in zip(self.names, self.decoders, self.num_classes):
+            if dec is not None and dec.num_classes != c:
+                raise ValueError(f'output {name!r} has {c} classes, its transition model {dec.num_classes}')
         # 8-byte words: per name [C * C counts, 2 flags] as int64, then per name [f1 sums, valid sums] as fp64, then with
         # `edit` per name [edit sum, valid sum] as fp64
         self._state = None
@@ -484,11 +623,12 @@ class EvaluationAccumulator:
             self._edit = [self._floats[n_f1 + 2 * i:n_f1 + 2 * i + 1] for i in range(len(self.names))]
             self._edit_valid = [self._floats[n_f1 + 2 * i + 1:n_f1 + 2 * i + 2] for i in range(len(self.names))]
 
-    def update(self, outputs, targets, step_index=None):
+    def update(self, outputs, targets, step_index=None, lengths=None):
         """One batch: outputs / targets are the model's lists (the last len(names) are used), output (bs, C, T, E)
         log-probabilities, target (bs, T_tgt, E) labels on the same device; step_index (bs, S) from
         `half_rate_step_index` / `segment_step_index`, already on the device (a host tensor would be copied, which
-        synchronises)."""
+        synchronises). lengths: int64 (bs,) on the device, the valid model steps of every clip, for the names that have
+        a decoder (the argmax has no use for it)."""
         K = get_kernels()
         n = len(self.names)
         outputs, targets = list(outputs)[-n:], list(targets)[-n:]
@@ -509,8 +649,11 @@ class EvaluationAccumulator:
                 self._allocate(out.device)
             if step_index is not None:
                 step_index = step_index.to(device=out.device, dtype=torch.int32)
-            labels, kept = K.eval_update(out, self.downsampling, tgt.to(torch.int64), step_index, self._counts[i],
-                                         self._flags[i], want_labels=True)
+            if self.decoders[i] is None:
+                labels, kept = K.eval_update(out, self.downsampling, tgt.to(torch.int64), step_index, self._counts[i],
+                                             self._flags[i], want_labels=True)
+            else:
+                labels, kept = self._decoded(K, i, out, tgt.to(torch.int64), step_index, lengths)
             if self.edit:
                 score, _, _, _, edit_valid, _ = K.segment_edit(kept, labels, -1, self.bg_label, entity_minor=True)
                 K.segment_f1_accumulate(score.view(-1, 1), edit_valid, self._edit[i], self._edit_valid[i])
@@ -524,6 +667,21 @@ class EvaluationAccumulator:
                 f1, valid = K.f1_at_k(kept, labels, self.num_classes[i], overlap, -1)
                 self._f1[i][j:j + 1].add_(f1.sum(dtype=torch.float64))
                 self._valid[i][j:j + 1].add_(valid.sum(dtype=torch.float64))
+
+    def _decoded(self, K, i, out, tgt, step_index, lengths):
+        """What eval_update does for name i, on the decoder's labels: (labels, targets) int64 (bs, S or T_tgt, E) of the
+        evaluated positions, their pairs added to the counts. Kernels and torch device operations only."""
+        T_tgt = tgt.shape[1]
+        labels = self.decoders[i].decode(out, self.downsampling, T_tgt, lengths)
+        kept = tgt
+        if step_index is not None:
+            beyond = step_index >= T_tgt          # counted, then evaluated as padding: never read
+            self._flags[i][1:2].add_(beyond.sum() * tgt.shape[2])
+            index = step_index.masked_fill(beyond, -1)
+            labels, kept = _select_steps(labels, index, 0), _select_steps(tgt, index, -1)
+        labels, kept = labels.contiguous(), kept.contiguous()
+        K.confusion_counts(kept.reshape(-1), labels.reshape(-1), self.num_classes[i], self._counts[i], self._flags[i])
+        return labels, kept
 
     def _update_f1_workgroup(self, K, i, kept, labels) -> bool:
         """One twog_segment_f1 per max_overlaps overlaps on the entity-minor labels, one accumulate each; False (nothing

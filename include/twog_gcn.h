@@ -1225,6 +1225,49 @@ int twog_segment_edit_limits(int* max_steps);
 #define TWOG_CLASS_COUNTS_MAX 4096
 int twog_class_counts(const int64_t* targets, int64_t n, int n_classes, int64_t ignore_index, int64_t* counts, void* stream);
 
+/* ===============================================================================================================
+ * Viterbi decoding of frame labels under a label-transition model (the reference project has no
+ * such decode, tests/viterbi_ref.py is the specification). For one sequence = one (clip b, entity e), with
+ * logp[t][c] = logp[b][c][t][e] at the model's own step rate, L the decoded length, A fp32 [C][C] transition scores
+ * (row = from, column = to) and pi fp32 [C] initial scores (NULL: all zero). All arithmetic is fp32, one rounding per
+ * add, nothing fused or reordered:
+ *     d[0][c] = logp[0][c] + pi[c]
+ *     m[t][c] = max over c' of (d[t-1][c'] + A[c'][c])     psi[t][c] = the SMALLEST c' that attains it
+ *     d[t][c] = m[t][c] + logp[t][c]                       (t = 1 .. L-1)
+ *     y[L-1]  = the smallest c attaining max d[L-1][.]     y[t-1] = psi[t][y[t]]     score = max d[L-1][.]
+ * A candidate replaces the running best only when it is strictly greater: that is the tie-break (among paths of equal
+ * score the smallest one compared from the last step backwards) and it decides what -inf does; -inf entries of A
+ * (forbidden transitions) are in contract. NaN is out of contract, but never gives a label outside [0, C) or an access
+ * outside the buffers.
+ * lengths: int64 [bs] on the device, in model steps, clamped by the kernel to [0, T]; NULL means T. A length of 0 writes
+ *   label 0 everywhere and score 0.0.
+ * labels int64 [bs][T_out][E]: labels[b][t'][e] = y[min(t' / downsampling, L - 1)], the upsampling of twog_predict_labels;
+ *   score fp32 [bs][E].
+ * Back-pointers are one byte per (t, c). twog_viterbi_workspace (launch-free) returns the route of a shape:
+ *   TWOG_VITERBI_ROUTE_LDS, *bytes = 0: they fit in LDS beside the staging buffers, `workspace` is not touched;
+ *   TWOG_VITERBI_ROUTE_WORKSPACE: they go to `workspace`, *bytes of device memory (256-byte aligned) that the call may
+ *   overwrite and whose content means nothing afterwards.
+ * The time axis is staged through LDS in chunks of TWOG_VITERBI_CHUNK steps. The result does not depend on the route, the
+ * chunking or the batch a sequence is decoded in, bit for bit.
+ * twog_viterbi_limits: the largest C (64) and T (4096). Returns: -1 for a bad size, -2 beyond the limits (or C * T * E
+ * >= 2^31, bs > 65535), -3 for a workspace that is NULL or too small on the workspace route.
+ *
+ * twog_transition_counts: ADDS to counts int64 [C][C] (row = from, column = to) one for every (b, e, k) with
+ *   (k + 1) * stride < T_tgt whose labels targets[b][k * stride][e] and targets[b][(k + 1) * stride][e] (int64
+ *   [bs][T_tgt][E]) are both in [0, C) and both != ignore_index: the statistics at the model's rate (stride = the
+ *   loader's downsampling). LDS histograms and integer atomics: the totals do not depend on the order. -2 for C > 64.
+ * =============================================================================================================== */
+#define TWOG_VITERBI_CHUNK 16
+#define TWOG_VITERBI_ROUTE_LDS 0
+#define TWOG_VITERBI_ROUTE_WORKSPACE 1
+int twog_viterbi_limits(int* max_classes, int* max_steps);
+int twog_viterbi_workspace(int bs, int n_classes, int T, int E, size_t* bytes);
+int twog_viterbi_decode(const float* logp, int bs, int n_classes, int T, int E, const float* A, const float* pi,
+                        const int64_t* lengths, int downsampling, int T_out, int64_t* labels, float* score,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int twog_transition_counts(const int64_t* targets, int bs, int T_tgt, int E, int n_classes, int stride,
+                           int64_t ignore_index, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
