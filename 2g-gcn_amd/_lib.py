@@ -210,6 +210,21 @@ def viterbi_workspace(lib, bs, n_classes, T, E):
     return VITERBI_ROUTES[rc], nbytes.value
 
 
+CRF_CHUNK, CRF_SEQ_WORDS = 16, 4   # TWOG_CRF_CHUNK, TWOG_CRF_SEQ_WORDS
+
+
+def crf_workspace(lib, bs, n_classes, T, E):
+    """twog_crf_workspace of the loaded library `lib`: the bytes of (alpha, seq, partials). No device is touched.
+    ValueError beyond the limits of twog_crf_limits."""
+    alpha, seq, partials = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    rc = lib.twog_crf_workspace(int(bs), int(n_classes), int(T), int(E), C.byref(alpha), C.byref(seq), C.byref(partials))
+    if rc == -2:
+        raise ValueError(f'the CRF loss takes up to 64 classes and 4096 model steps, not {n_classes} and {T}')
+    if rc < 0:
+        raise RuntimeError(f'twog_crf_workspace failed with code {rc}')
+    return alpha.value, seq.value, partials.value
+
+
 BIGRU_PLAN_HEAD, BIGRU_PLAN_MAX_COMBOS = 8, 32   # TWOG_BIGRU_PLAN_HEAD, TWOG_BIGRU_PLAN_MAX_COMBOS
 BIGRU_PLAN_INTS = BIGRU_PLAN_HEAD + 4 * BIGRU_PLAN_MAX_COMBOS   # TWOG_BIGRU_PLAN_INTS
 
@@ -386,6 +401,10 @@ SIGNATURES = {
     'twog_viterbi_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
     'twog_viterbi_decode': [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, C.c_size_t, _P],
     'twog_transition_counts': [_P, _I, _I, _I, _I, _I, _L, _P, _P],
+    'twog_crf_limits': [C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    'twog_crf_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
+    'twog_crf_nll_fwd': [_P, _P, _I, _I, _I, _I, _P, _P, _L, _F, _P, _P, _P, _P, _P],
+    'twog_crf_nll_bwd': [_P, _P, _I, _I, _I, _I, _P, _L, _F, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P],
 }
 
 _lib = None

@@ -1,0 +1,461 @@
+// Linear-chain CRF loss: the sequence negative log-likelihood of the frame labels under learned transition scores, forward
+// and backward. The reference project has no such term; the definition is the numpy specification
+// tests/crf_ref.py, restated at twog_crf_nll_fwd in include/twog_gcn.h.
+//
+// Shape of the recursion kernels, after viterbi.hip: serial in t, parallel in the class. One wave per sequence (clip b,
+// entity e), lane c owns class c. A workgroup is one clip and up to CRF_MAX_WAVES neighbouring entities; together its waves
+// stage time chunks of the clip's (C, chunk, E) slab through LDS, the loads of the next chunk in flight while this one is
+// consumed. The labels of a chunk are fetched the same way, one per lane, so a step reads its label from a register and the
+// kept / removed decision is wave-uniform.
+//   forward : lane c holds the column A[:, c]; alpha of the previous kept step comes from the other lanes by v_readlane.
+//   backward: lane c' holds the row A[c', :] and its row of sum_k (xi_k - indicator) in registers; u = x + beta of the next
+//             kept step comes from the other lanes by v_readlane. d input goes through a second pair of LDS buffers and
+//             leaves in the layout the slab was fetched in, so a removed step costs one zero per class and nothing is
+//             cleared beforehand.
+// Every logsumexp is taken in the log domain with the maximum subtracted (expf / logf of the device library, not the
+// fast forms): finite A and pi of any size are in contract, nothing can underflow as a whole.
+// No floating-point atomics: the sums over sequences are made by second-stage kernels in index order in fp64.
+#include "twog_common.h"
+
+namespace {
+
+constexpr int CRF_MAX_CLASSES = 64;     // one wave: lane c owns class c (the limits of viterbi.hip)
+constexpr int CRF_MAX_STEPS = 4096;
+constexpr int CRF_CHUNK = TWOG_CRF_CHUNK;
+constexpr int CRF_MAX_WAVES = 8;        // entities of one clip per workgroup ...
+constexpr int CRF_MAX_WAVES_WIDE = 4;   // ... and beyond 32 classes: one wave per SIMD, so that a lane's two rows of 64 values
+                                        // (backward: A[c', :] and its sums) stay in the register file with no scratch
+__host__ __device__ constexpr int crf_max_waves(int classes) { return classes > 32 ? CRF_MAX_WAVES_WIDE : CRF_MAX_WAVES; }
+constexpr size_t CRF_LDS_LIMIT = 160 * 1024;
+constexpr int CRF_FINAL_THREADS = 256;
+
+struct CrfPlan {
+    int waves;             // entities per workgroup
+    int groups;            // workgroups per clip
+    size_t buf_floats;     // one LDS buffer: C rows of CRF_CHUNK * waves + 1 floats
+    size_t alpha_bytes, seq_bytes, partial_bytes;
+};
+
+// The one statement of the launch geometry and the workspaces: twog_crf_workspace reports it, the launchers use it.
+inline CrfPlan crf_plan(int bs, int C, int T, int E) {
+    CrfPlan p;
+    p.waves = E < crf_max_waves(C) ? E : crf_max_waves(C);
+    p.groups = (E + p.waves - 1) / p.waves;
+    p.buf_floats = (size_t)C * (CRF_CHUNK * p.waves + 1);          // odd row stride: lanes c hit different banks
+    const size_t n_seq = (size_t)bs * E;
+    p.alpha_bytes = n_seq * T * C * sizeof(float);
+    p.seq_bytes = n_seq * TWOG_CRF_SEQ_WORDS * sizeof(float);
+    p.partial_bytes = n_seq * C * (C + 1) * sizeof(float);
+    return p;
+}
+
+// the label of a step as the chain sees it: the class of a kept step, -1 for a removed one (the NLL terms' rule)
+__device__ __forceinline__ int chain_label(long long y, long long ignore, int C) {
+    return (y != ignore && y >= 0 && y < C) ? (int)y : -1;
+}
+
+// What a thread stages of every chunk: elements k * nthreads + tid of the (C, chunk, EW) slab, k = 0 .. CMAX / 4 - 1. A class
+// row of the slab is CRF_CHUNK * EW = nthreads / 4 elements, so element k is class 4 k + c0 at the same (step, entity) for
+// every k: the offsets are one base and one stride each.
+struct Staging {
+    int c0, tt, soff0, sstep;
+    int64_t goff0, gstep;
+    bool column;              // the thread's entity exists
+    __device__ __forceinline__ void init(int tid, int C, int T, int E, int EW, int e0) {
+        const int per_class = CRF_CHUNK * EW, row = per_class + 1;
+        c0 = tid / per_class;
+        const int rem = tid - c0 * per_class;
+        tt = rem / EW;
+        const int ew = rem - tt * EW;
+        column = e0 + ew < E;
+        goff0 = ((int64_t)c0 * T + tt) * E + ew;
+        gstep = (int64_t)4 * T * E;
+        soff0 = c0 * row + rem;
+        sstep = 4 * row;
+    }
+    __device__ __forceinline__ bool has(int k, int C) const { return column && 4 * k + c0 < C; }
+};
+
+// grid (groups, bs), 64 * EW threads: wave w runs entity blockIdx.x * EW + w of clip blockIdx.y.
+// LDS: stage[2][C][CRF_CHUNK * EW + 1] floats.
+// alpha [bs * E][T][C]: written at the kept steps only. seq [bs * E][TWOG_CRF_SEQ_WORDS]: logZ, gold, nll, K (int bits).
+template <int CMAX>
+__global__ __launch_bounds__(64 * crf_max_waves(CMAX)) void crf_fwd_kernel(
+    const float* __restrict__ logp, int C, int T, int E, const float* __restrict__ A, const float* __restrict__ pi,
+    const long long* __restrict__ target, long long ignore, float* __restrict__ alpha_ws, float* __restrict__ seq, int EW) {
+    extern __shared__ float smem[];
+    constexpr int R = CMAX / 4;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int b = blockIdx.y, e0 = blockIdx.x * EW, e = e0 + w;
+    const bool runs = e < E;                          // wave-uniform; a wave without an entity still stages
+    const int row = CRF_CHUNK * EW + 1;
+    const int buf_floats = C * row;
+    float* stage = smem;
+
+    Staging S;
+    S.init(tid, C, T, E, EW, e0);
+    const float* base = logp + (int64_t)b * C * T * E + e0;
+    float pre[R];
+    auto fetch = [&](int t0) {
+#pragma unroll
+        for (int k = 0; k < R; ++k)
+            pre[k] = (S.has(k, C) && t0 + S.tt < T) ? base[(int64_t)t0 * E + S.goff0 + k * S.gstep] : 0.0f;
+    };
+    auto commit = [&](int buf) {
+#pragma unroll
+        for (int k = 0; k < R; ++k)
+            if (S.has(k, C)) stage[buf * buf_floats + S.soff0 + k * S.sstep] = pre[k];
+    };
+    const long long* labels = target + (int64_t)b * T * E + (runs ? e : 0);
+    auto fetch_label = [&](int t0) {
+        return (runs && lane < CRF_CHUNK && t0 + lane < T) ? chain_label(labels[(int64_t)(t0 + lane) * E], ignore, C) : -1;
+    };
+
+    const float NEG_INF = -__builtin_inff();
+    const bool owns = lane < C;
+    // column A[:, c]; a lane without a class takes column 0 (finite values: its sums stay finite and are dropped)
+    float a[CMAX];
+#pragma unroll
+    for (int cp = 0; cp < CMAX; ++cp) a[cp] = cp < C ? A[cp * C + (owns ? lane : 0)] : NEG_INF;
+    const float pi_c = pi[owns ? lane : 0];
+    const int my_row = (owns ? lane : 0) * row + w;
+    const int64_t s_idx = (int64_t)b * E + (runs ? e : 0);
+    float* alpha_out = alpha_ws + s_idx * T * C;
+
+    float alpha = NEG_INF, gold = 0.0f;
+    int K = 0, y_prev = 0;
+    const int n_chunks = (T + CRF_CHUNK - 1) / CRF_CHUNK;
+    fetch(0);
+    int lab_pre = fetch_label(0);
+    for (int ch = 0; ch < n_chunks; ++ch) {
+        const int buf = ch & 1, t0 = ch * CRF_CHUNK;
+        commit(buf);          // buffer `buf` was last read in chunk ch - 2, which every wave left before the barrier of ch - 1
+        __syncthreads();
+        const int lab = lab_pre;
+        if (ch + 1 < n_chunks) {                          // in flight while this chunk is consumed
+            fetch(t0 + CRF_CHUNK);
+            lab_pre = fetch_label(t0 + CRF_CHUNK);
+        }
+        if (!runs) continue;
+        const float* mine = stage + buf * buf_floats + my_row;
+        const int n_here = T - t0 < CRF_CHUNK ? T - t0 : CRF_CHUNK;
+        for (int tt = 0; tt < n_here; ++tt) {
+            const int y = __builtin_amdgcn_readlane(lab, tt);
+            if (y < 0) continue;                          // a removed step: not part of the chain
+            const float x = mine[tt * EW];
+            const float x_y = lane_value(x, y);
+            if (K == 0) {
+                alpha = pi_c + x;
+                gold = pi[y] + x_y;
+            } else {
+                float m = NEG_INF;
+#pragma unroll
+                for (int cp = 0; cp < CMAX; ++cp) m = fmaxf(m, lane_value(alpha, cp) + a[cp]);
+                float s = 0.0f;
+#pragma unroll
+                for (int cp = 0; cp < CMAX; ++cp) s += expf((lane_value(alpha, cp) + a[cp]) - m);
+                alpha = x + (m + logf(s));
+                gold = gold + (A[y_prev * C + y] + x_y);
+            }
+            if (!owns) alpha = NEG_INF;
+            else alpha_out[(int64_t)(t0 + tt) * C + lane] = alpha;
+            y_prev = y;
+            ++K;
+        }
+    }
+    if (!runs) return;
+    float logZ = 0.0f;
+    if (K > 0) {
+        const float m = wave_max(alpha);
+        const float s = wave_sum(owns ? expf(alpha - m) : 0.0f);
+        logZ = m + logf(s);
+    } else {
+        gold = 0.0f;
+    }
+    if (lane == 0) {
+        float* o = seq + s_idx * TWOG_CRF_SEQ_WORDS;
+        o[0] = logZ;
+        o[1] = gold;
+        o[2] = logZ - gold;
+        o[3] = __int_as_float(K);
+    }
+}
+
+// One workgroup: sum of nll_seq and of K over the sequences in fp64, thread i taking sequences i, i + 256, ... and the
+// threads' sums added in a fixed tree; {sum, count} into stats, weight * sum / count (0 when nothing is kept) into loss.
+__global__ __launch_bounds__(CRF_FINAL_THREADS) void crf_final_kernel(const float* __restrict__ seq, int64_t n_seq,
+                                                                       float weight, double* stats, float* loss) {
+    __shared__ double red[2][CRF_FINAL_THREADS];
+    double sum = 0.0, cnt = 0.0;
+    for (int64_t s = threadIdx.x; s < n_seq; s += CRF_FINAL_THREADS) {
+        sum += (double)seq[s * TWOG_CRF_SEQ_WORDS + 2];
+        cnt += (double)__float_as_int(seq[s * TWOG_CRF_SEQ_WORDS + 3]);
+    }
+    red[0][threadIdx.x] = sum;
+    red[1][threadIdx.x] = cnt;
+    __syncthreads();
+    for (int o = CRF_FINAL_THREADS / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + o];
+            red[1][threadIdx.x] += red[1][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        stats[0] = red[0][0];
+        stats[1] = red[1][0];
+        loss[0] = weight * (float)(red[1][0] > 0.0 ? red[0][0] / red[1][0] : 0.0);
+    }
+}
+
+// Same geometry as crf_fwd_kernel, the kept steps walked from the last to the first.
+// LDS: stage[2][C][row] floats, then (dinput != NULL) out[2][C][row] floats.
+// partials (NULL: the parameters need no gradient) [bs * E][C + 1][C]: rows 0 .. C-1 = sum_k (xi_k - indicator) of the
+// sequence, row C = gamma_0 - indicator, all before the factor g.
+template <int CMAX>
+__global__ __launch_bounds__(64 * crf_max_waves(CMAX)) void crf_bwd_kernel(
+    const float* __restrict__ logp, int C, int T, int E, const float* __restrict__ A, const long long* __restrict__ target,
+    long long ignore, const float* __restrict__ alpha_ws, const float* __restrict__ seq, const double* __restrict__ stats,
+    const float* __restrict__ dloss, float weight, float* __restrict__ dinput, int accumulate, float* __restrict__ partials,
+    int EW) {
+    extern __shared__ float smem[];
+    constexpr int R = CMAX / 4;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int b = blockIdx.y, e0 = blockIdx.x * EW, e = e0 + w;
+    const bool runs = e < E;
+    const int row = CRF_CHUNK * EW + 1;
+    const int buf_floats = C * row;
+    float* stage = smem;
+    float* out = smem + 2 * buf_floats;
+
+    const double cnt = stats[1];
+    const float g = cnt > 0.0 ? weight * dloss[0] / (float)cnt : 0.0f;
+
+    Staging S;
+    S.init(tid, C, T, E, EW, e0);
+    const float* base = logp + (int64_t)b * C * T * E + e0;
+    float* dbase = dinput ? dinput + (int64_t)b * C * T * E + e0 : nullptr;
+    float pre[R];
+    auto fetch = [&](int t0) {
+#pragma unroll
+        for (int k = 0; k < R; ++k)
+            pre[k] = (S.has(k, C) && t0 + S.tt < T) ? base[(int64_t)t0 * E + S.goff0 + k * S.gstep] : 0.0f;
+    };
+    auto commit = [&](int buf) {
+#pragma unroll
+        for (int k = 0; k < R; ++k)
+            if (S.has(k, C)) stage[buf * buf_floats + S.soff0 + k * S.sstep] = pre[k];
+    };
+    auto flush = [&](int buf, int t0) {                   // the d input of a finished chunk, in the layout it was fetched in
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            if (!S.has(k, C) || t0 + S.tt >= T) continue;
+            float* dst = dbase + (int64_t)t0 * E + S.goff0 + k * S.gstep;
+            const float v = out[buf * buf_floats + S.soff0 + k * S.sstep];
+            *dst = accumulate ? *dst + v : v;
+        }
+    };
+    const long long* labels = target + (int64_t)b * T * E + (runs ? e : 0);
+    auto fetch_label = [&](int t0) {
+        return (runs && lane < CRF_CHUNK && t0 + lane < T) ? chain_label(labels[(int64_t)(t0 + lane) * E], ignore, C) : -1;
+    };
+
+    const float NEG_INF = -__builtin_inff();
+    const bool owns = lane < C;
+    // row A[c', :]; a lane without a class takes row 0 (finite sums, dropped), a column without a class is 0 under u = -inf
+    float ar[CMAX], acc[CMAX];
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) {
+        ar[c] = c < C ? A[(owns ? lane : 0) * C + c] : 0.0f;
+        acc[c] = 0.0f;
+    }
+    const int my_row = (owns ? lane : 0) * row + w;
+    const int64_t s_idx = (int64_t)b * E + (runs ? e : 0);
+    const float* alpha_in = alpha_ws + s_idx * T * C + (owns ? lane : 0);
+    const float logZ = seq[s_idx * TWOG_CRF_SEQ_WORDS];
+
+    float u = NEG_INF, first_d = 0.0f;                    // u = x + beta of the next kept step; first_d = gamma_0 - indicator
+    int y_next = -1;                                      // its label, -1: no kept step behind this one yet
+    const int n_chunks = (T + CRF_CHUNK - 1) / CRF_CHUNK;
+    fetch((n_chunks - 1) * CRF_CHUNK);
+    int lab_pre = fetch_label((n_chunks - 1) * CRF_CHUNK);
+    float alpha_pre = alpha_in[(int64_t)(T - 1) * C];     // one step ahead of its use; a removed step's slot is read, never used
+    for (int it = 0; it < n_chunks; ++it) {
+        const int buf = it & 1, t0 = (n_chunks - 1 - it) * CRF_CHUNK;
+        commit(buf);
+        __syncthreads();      // stage[buf] is whole, and every wave has left the chunk before: out[buf ^ 1] is whole
+        if (dinput && it > 0) flush(buf ^ 1, t0 + CRF_CHUNK);
+        const int lab = lab_pre;
+        if (it + 1 < n_chunks) {
+            fetch(t0 - CRF_CHUNK);
+            lab_pre = fetch_label(t0 - CRF_CHUNK);
+        }
+        if (!runs) continue;
+        const float* mine = stage + buf * buf_floats + my_row;
+        float* mine_out = out + buf * buf_floats + my_row;
+        const int n_here = T - t0 < CRF_CHUNK ? T - t0 : CRF_CHUNK;
+        for (int tt = n_here - 1; tt >= 0; --tt) {
+            const int t = t0 + tt;
+            const float alpha_t = owns ? alpha_pre : NEG_INF;
+            if (t > 0) alpha_pre = alpha_in[(int64_t)(t - 1) * C];
+            const int y = __builtin_amdgcn_readlane(lab, tt);
+            float d = 0.0f;
+            if (y >= 0) {
+                const float x = mine[tt * EW];
+                float beta = 0.0f;
+                if (y_next >= 0) {
+                    float m = NEG_INF;
+#pragma unroll
+                    for (int c = 0; c < CMAX; ++c) m = fmaxf(m, ar[c] + lane_value(u, c));
+                    const float scale = expf((alpha_t + m) - logZ);          // xi[c', c] = exp(w[c] - m) * scale
+                    const float ind = lane == y ? 1.0f : 0.0f;
+                    float s = 0.0f;
+#pragma unroll
+                    for (int c = 0; c < CMAX; ++c) {
+                        const float ex = expf((ar[c] + lane_value(u, c)) - m);
+                        s += ex;
+                        acc[c] += ex * scale - (c == y_next ? ind : 0.0f);
+                    }
+                    beta = m + logf(s);
+                }
+                const float gamma = expf((alpha_t + beta) - logZ);
+                first_d = gamma - (lane == y ? 1.0f : 0.0f);
+                d = g * first_d;
+                u = owns ? x + beta : NEG_INF;
+                y_next = y;
+            }
+            if (dinput && owns) mine_out[tt * EW] = d;
+        }
+    }
+    if (dinput) {
+        __syncthreads();
+        flush((n_chunks - 1) & 1, 0);
+    }
+    if (!runs || !partials || !owns) return;
+    float* p = partials + s_idx * (C + 1) * C;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c)
+        if (c < C) p[lane * C + c] = y_next >= 0 ? acc[c] : 0.0f;
+    p[C * C + lane] = y_next >= 0 ? first_d : 0.0f;
+}
+
+// Element j of the (C + 1, C) partial rows summed over the sequences in index order in fp64, times g, rounded once:
+// j < C * C goes to dA, the rest to dpi.
+__global__ __launch_bounds__(256) void crf_param_kernel(const float* __restrict__ partials, int64_t n_seq, int C,
+                                                         const double* __restrict__ stats, const float* __restrict__ dloss,
+                                                         float weight, float* dA, float* dpi, int accumulate) {
+    const int j = blockIdx.x * 256 + threadIdx.x, n = (C + 1) * C;
+    if (j >= n) return;
+    const double cnt = stats[1];
+    const float g = cnt > 0.0 ? weight * dloss[0] / (float)cnt : 0.0f;
+    double sum = 0.0;
+    for (int64_t s = 0; s < n_seq; ++s) sum += (double)partials[s * n + j];
+    const float v = (float)((double)g * sum);
+    float* dst = j < C * C ? dA + j : dpi + (j - C * C);
+    *dst = accumulate ? *dst + v : v;
+}
+
+inline bool crf_shape_ok(int bs, int C, int T, int E) { return bs >= 0 && C >= 1 && T >= 1 && E >= 1; }
+inline bool crf_within_limits(int bs, int C, int T, int E) {
+    return C <= CRF_MAX_CLASSES && T <= CRF_MAX_STEPS && (int64_t)C * T * E <= INT32_MAX && bs <= 65535;
+}
+
+template <int CMAX>
+int launch_crf_fwd(const CrfPlan& p, const float* logp, int bs, int C, int T, int E, const float* A, const float* pi,
+                   const int64_t* target, int64_t ignore, float* alpha, float* seq, hipStream_t st) {
+    static std::atomic<uint32_t> lds_attr_done{0};
+    twog_allow_dynamic_lds(crf_fwd_kernel<CMAX>, (int)CRF_LDS_LIMIT, lds_attr_done);
+    hipLaunchKernelGGL(crf_fwd_kernel<CMAX>, dim3(p.groups, bs), dim3(64 * p.waves), 2 * p.buf_floats * sizeof(float), st,
+                       logp, C, T, E, A, pi, reinterpret_cast<const long long*>(target), (long long)ignore, alpha, seq, p.waves);
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
+template <int CMAX>
+int launch_crf_bwd(const CrfPlan& p, const float* logp, int bs, int C, int T, int E, const float* A, const int64_t* target,
+                   int64_t ignore, const float* alpha, const float* seq, const double* stats, const float* dloss,
+                   float weight, float* dinput, int accumulate, float* partials, hipStream_t st) {
+    static std::atomic<uint32_t> lds_attr_done{0};
+    twog_allow_dynamic_lds(crf_bwd_kernel<CMAX>, (int)CRF_LDS_LIMIT, lds_attr_done);
+    hipLaunchKernelGGL(crf_bwd_kernel<CMAX>, dim3(p.groups, bs), dim3(64 * p.waves),
+                       (dinput ? 4 : 2) * p.buf_floats * sizeof(float), st, logp, C, T, E, A,
+                       reinterpret_cast<const long long*>(target), (long long)ignore, alpha, seq, stats, dloss, weight, dinput,
+                       accumulate, partials, p.waves);
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int twog_crf_limits(int* max_classes, int* max_steps) {
+    if (max_classes) *max_classes = CRF_MAX_CLASSES;
+    if (max_steps) *max_steps = CRF_MAX_STEPS;
+    return 0;
+}
+
+extern "C" int twog_crf_workspace(int bs, int n_classes, int T, int E, size_t* alpha_bytes, size_t* seq_bytes,
+                                  size_t* partial_bytes) {
+    if (!crf_shape_ok(bs, n_classes, T, E)) return -1;
+    if (!crf_within_limits(bs, n_classes, T, E)) return -2;
+    const CrfPlan p = crf_plan(bs, n_classes, T, E);
+    if (alpha_bytes) *alpha_bytes = p.alpha_bytes;
+    if (seq_bytes) *seq_bytes = p.seq_bytes;
+    if (partial_bytes) *partial_bytes = p.partial_bytes;
+    return 0;
+}
+
+extern "C" int twog_crf_nll_fwd(const float* input, const int64_t* target, int bs, int n_classes, int T, int E,
+                                const float* A, const float* pi, int64_t ignore_index, float weight, float* alpha,
+                                float* seq, double* stats, float* loss, void* stream) {
+    const int C = n_classes;
+    if (!crf_shape_ok(bs, C, T, E)) return -1;
+    if (!crf_within_limits(bs, C, T, E)) return -2;
+    if (!A || !pi || !stats || !loss || (bs > 0 && (!input || !target || !alpha || !seq))) return -3;
+    hipStream_t st = (hipStream_t)stream;
+    if (bs > 0) {
+        const CrfPlan p = crf_plan(bs, C, T, E);
+        int rc;
+        if (C <= 8) rc = launch_crf_fwd<8>(p, input, bs, C, T, E, A, pi, target, ignore_index, alpha, seq, st);
+        else if (C <= 16) rc = launch_crf_fwd<16>(p, input, bs, C, T, E, A, pi, target, ignore_index, alpha, seq, st);
+        else if (C <= 32) rc = launch_crf_fwd<32>(p, input, bs, C, T, E, A, pi, target, ignore_index, alpha, seq, st);
+        else rc = launch_crf_fwd<64>(p, input, bs, C, T, E, A, pi, target, ignore_index, alpha, seq, st);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(crf_final_kernel, dim3(1), dim3(CRF_FINAL_THREADS), 0, st, seq, (int64_t)bs * E, weight, stats, loss);
+    TWOG_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int twog_crf_nll_bwd(const float* input, const int64_t* target, int bs, int n_classes, int T, int E,
+                                const float* A, int64_t ignore_index, float weight, const float* alpha, const float* seq,
+                                const double* stats, const float* dloss, float* dinput, int accumulate, float* partials,
+                                float* dA, float* dpi, int accumulate_params, void* stream) {
+    const int C = n_classes;
+    if (!crf_shape_ok(bs, C, T, E)) return -1;
+    if (!crf_within_limits(bs, C, T, E)) return -2;
+    if (!A || !stats || !dloss || (bs > 0 && (!input || !target || !alpha || !seq))) return -3;
+    if ((dA == nullptr) != (dpi == nullptr) || (dA && bs > 0 && !partials)) return -3;
+    if (!dinput && !dA) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (bs > 0) {
+        const CrfPlan p = crf_plan(bs, C, T, E);
+        float* part = dA ? partials : nullptr;
+        int rc;
+        if (C <= 8)
+            rc = launch_crf_bwd<8>(p, input, bs, C, T, E, A, target, ignore_index, alpha, seq, stats, dloss, weight, dinput, accumulate, part, st);
+        else if (C <= 16)
+            rc = launch_crf_bwd<16>(p, input, bs, C, T, E, A, target, ignore_index, alpha, seq, stats, dloss, weight, dinput, accumulate, part, st);
+        else if (C <= 32)
+            rc = launch_crf_bwd<32>(p, input, bs, C, T, E, A, target, ignore_index, alpha, seq, stats, dloss, weight, dinput, accumulate, part, st);
+        else
+            rc = launch_crf_bwd<64>(p, input, bs, C, T, E, A, target, ignore_index, alpha, seq, stats, dloss, weight, dinput, accumulate, part, st);
+        if (rc) return rc;
+    }
+    if (dA) {
+        const int n = (C + 1) * C;
+        hipLaunchKernelGGL(crf_param_kernel, dim3((n + 255) / 256), dim3(256), 0, st, partials, (int64_t)bs * E, C, stats, dloss,
+                           weight, dA, dpi, accumulate_params);
+        TWOG_CHECK_LAUNCH();
+    }
+    return 0;
+}

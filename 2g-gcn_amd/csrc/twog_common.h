@@ -129,4 +129,9 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return t;
 }
 
+// v of lane `lane` (wave-uniform, a constant where the loop around it is unrolled) in every lane: one v_readlane
+__device__ __forceinline__ float lane_value(float v, int lane) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }

@@ -57,10 +57,6 @@ inline VitPlan vit_plan(int bs, int C, int T, int E) {
     return p;
 }
 
-__device__ __forceinline__ float lane_value(float v, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
 // m = max over c' of (d[c'] + a[c']), arg = the smallest c' that attains it: a candidate replaces the running best only
 // when it is strictly greater. Four independent runs over ascending ranges, merged in ascending order under the same rule,
 // give what one run over 0 .. CMAX - 1 gives. Rows c' >= C hold -inf in `a` and in d: they never win.

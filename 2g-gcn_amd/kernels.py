@@ -1609,6 +1609,90 @@ class HipKernels:
         self._check(self.lib.twog_smooth_loss_bwd(self._smooth_terms(terms, dins, accumulate), m, stats.data_ptr(),
                                                   dlosses.data_ptr(), self._stream()), 'twog_smooth_loss_bwd')
 
+    # ---------------------------------------------------------------- linear-chain CRF loss
+    def crf_limits(self):
+        """(largest class count, most model steps) the CRF loss takes: those of viterbi_limits."""
+        max_classes, max_steps = C.c_int(0), C.c_int(0)
+        self._check(self.lib.twog_crf_limits(C.byref(max_classes), C.byref(max_steps)), 'twog_crf_limits')
+        return max_classes.value, max_steps.value
+
+    def crf_workspace(self, bs, num_classes, T, E):
+        """Bytes of the (alpha, seq, partials) workspaces of a CRF term of this shape. Launch-free; ValueError beyond
+        crf_limits."""
+        return L.crf_workspace(self.lib, bs, num_classes, T, E)
+
+    def _crf_term(self, t):
+        """A CRF term: dict(input (bs, C, T, E) fp32 log-probabilities, target int64 (bs, T, E), transitions fp32 (C, C),
+        initial fp32 (C,), weight, ignore). Returns its shape; ValueError beyond crf_limits."""
+        x, y, A, pi = t['input'], t['target'], t['transitions'], t['initial']
+        assert x.is_contiguous() and y.is_contiguous() and x.dtype == torch.float32 and y.dtype == torch.int64
+        assert x.dim() == 4 and y.shape == (x.shape[0], x.shape[2], x.shape[3]), (tuple(x.shape), tuple(y.shape))
+        bs, Cn, T, E = x.shape
+        max_classes, max_steps = self.crf_limits()
+        if Cn > max_classes or T > max_steps:
+            raise ValueError(f'the CRF loss takes up to {max_classes} classes and {max_steps} model steps, not {Cn} and {T}')
+        for p, shape in ((A, (Cn, Cn)), (pi, (Cn,))):
+            assert p.shape == shape and p.dtype == torch.float32 and p.is_contiguous() and p.device == x.device, \
+                (tuple(p.shape), p.dtype, p.device)
+        return bs, Cn, T, E
+
+    def crf_nll_fwd(self, terms, losses_out, stats_out):
+        """The CRF terms (twog_crf_nll_fwd in include/twog_gcn.h), one launch pair each, written into the given views:
+        losses_out [m] fp32 and stats_out [m][2] fp64 = (sum of nll_seq, kept steps), the tail of the tensors
+        multitask_loss_fwd(..., room=) returned. Every term keeps its 'alpha' and 'seq' workspaces for crf_nll_bwd;
+        seq (bs * E, 4) fp32 holds logZ, gold, nll_seq and K (the bits of an int32) per sequence."""
+        m = len(terms)
+        shapes = [self._crf_term(t) for t in terms]   # every refusal before the first launch
+        assert losses_out.shape == (m,) and losses_out.dtype == torch.float32 and losses_out.is_contiguous()
+        assert stats_out.shape == (m, 2) and stats_out.dtype == torch.float64 and stats_out.is_contiguous()
+        for j, (t, (bs, Cn, T, E)) in enumerate(zip(terms, shapes)):
+            x = t['input']
+            assert losses_out.device == x.device and stats_out.device == x.device
+            if T == 0 or E == 0:
+                bs = 0   # no sequence: the sums alone, over nothing
+            alpha_bytes, seq_bytes, _ = self.crf_workspace(bs, Cn, max(T, 1), max(E, 1))
+            t['alpha'] = torch.empty(alpha_bytes // 4, dtype=torch.float32, device=x.device)
+            t['seq'] = torch.empty(seq_bytes // 4 // L.CRF_SEQ_WORDS, L.CRF_SEQ_WORDS, dtype=torch.float32, device=x.device)
+            self._check(self.lib.twog_crf_nll_fwd(x.data_ptr(), t['target'].data_ptr(), bs, Cn, max(T, 1), max(E, 1),
+                                                  t['transitions'].data_ptr(), t['initial'].data_ptr(), int(t['ignore']),
+                                                  float(t['weight']), t['alpha'].data_ptr(), t['seq'].data_ptr(),
+                                                  stats_out[j].data_ptr(), losses_out[j:].data_ptr(), self._stream()),
+                        'twog_crf_nll_fwd')
+
+    def crf_nll_bwd(self, terms, stats, dlosses, dins, accumulate, need_params):
+        """The gradients of the CRF terms of crf_nll_fwd, scaled by dlosses [m]. d(input) of term j is stored into dins[j]
+        (every element), or with accumulate[j] added to it; dins[j] None: not asked for. need_params[j]: also (dA, dpi) of
+        the term, new tensors. Returns the list of (dA, dpi) or None per term. A term that asks for neither is skipped."""
+        m = len(terms)
+        assert stats.shape == (m, 2) and stats.dtype == torch.float64 and stats.is_contiguous()
+        assert dlosses.shape == (m,) and dlosses.dtype == torch.float32 and dlosses.is_contiguous()
+        ptrs = [d.data_ptr() for d in dins if d is not None]
+        assert len(set(ptrs)) == len(ptrs), 'two CRF terms share a gradient buffer'
+        out = []
+        for j, t in enumerate(terms):
+            d, want = dins[j], bool(need_params[j])
+            if d is None and not want:
+                out.append(None)
+                continue
+            x = t['input']
+            bs, Cn, T, E = x.shape
+            if d is not None:
+                assert d.is_contiguous() and d.dtype == torch.float32 and d.shape == x.shape and d.device == x.device
+            if T == 0 or E == 0:
+                bs = 0
+            dA = dpi = partials = None
+            if want:
+                dA = torch.empty(Cn, Cn, dtype=torch.float32, device=x.device)
+                dpi = torch.empty(Cn, dtype=torch.float32, device=x.device)
+                partials = self.workspace(self.crf_workspace(bs, Cn, max(T, 1), max(E, 1))[2], x.device, 'crf_partials')
+            self._check(self.lib.twog_crf_nll_bwd(x.data_ptr(), t['target'].data_ptr(), bs, Cn, max(T, 1), max(E, 1),
+                                                  t['transitions'].data_ptr(), int(t['ignore']), float(t['weight']),
+                                                  t['alpha'].data_ptr(), t['seq'].data_ptr(), stats[j].data_ptr(),
+                                                  dlosses[j:].data_ptr(), _ptr(d), int(bool(accumulate[j])), _ptr(partials),
+                                                  _ptr(dA), _ptr(dpi), 0, self._stream()), 'twog_crf_nll_bwd')
+            out.append((dA, dpi) if want else None)
+        return out
+
 
     # ---------------------------------------------------------------- inference post-processing
     def predict_labels(self, logp, downsampling, target_steps):
@@ -1822,6 +1906,11 @@ def viterbi_decode(logp, transitions, initial=None, lengths=None, downsampling=1
 def viterbi_limits():
     """`get_kernels().viterbi_limits()`: (largest class count, most model steps)."""
     return get_kernels().viterbi_limits()
+
+
+def crf_limits():
+    """`get_kernels().crf_limits()`: (largest class count, most model steps) of the CRF loss."""
+    return get_kernels().crf_limits()
 
 
 def transition_counts(targets, num_classes, stride, ignore_index, counts):

@@ -17,6 +17,12 @@ Against label imbalance: per-class weights on the NLL terms (`nll_loss(weight=)`
 `misc.segmentation_loss.positive_class_weight`). A call in which any term carries one runs ALL its terms through
 `twog_weighted_loss_fwd/bwd` (twog_wloss_t in include/twog_gcn.h), still one launch per direction; a call without them makes
 the launches it always made. `class_counts` (on the device) and `class_weights` ('balanced', 'effective') give the weights.
+
+For sequence decoding: the linear-chain CRF loss (`LinearChainCRF`, `crf_loss`, `multi_task_loss(..., crf=...)`,
+`misc.crf_loss` of `select_loss`), the sequence negative log-likelihood under learned transition scores, which trains the
+emissions and the (C, C) scores jointly; the scores then go to `postprocess.ViterbiDecoder` (`module.decoder()`). Its terms
+follow the smoothing terms in the same loss tensor, one launch pair per term and direction (`twog_crf_nll_fwd/bwd`;
+definition in include/twog_gcn.h and at `crf_loss`); off by default.
 """
 from functools import partial
 
@@ -63,6 +69,85 @@ def temporal_smoothing_loss(input, target, tau=4.0, ignore_index=-1):
     return _run([input], [target], [_NLL], [0.0], ignore_index, 'mean', [(0, 1.0, tau)])[1]
 
 
+class LinearChainCRF(torch.nn.Module):
+    """The parameters of a linear-chain CRF over `num_classes` labels: `transitions` A fp32 (C, C), row = from, column = to
+    (the convention of `postprocess.viterbi_labels`), and `initial` pi fp32 (C,), both zero-initialised -- with zeros and
+    normalised emissions the CRF loss is the per-sequence NLL. Trained beside the model: `DataParallel(model,
+    extra_modules=[crf])` + `FusedAdam`, as `MultiTaskLossLearner` is. The state_dict is the two tensors."""
+
+    def __init__(self, num_classes: int):
+        super().__init__()
+        self.num_classes = int(num_classes)
+        if self.num_classes < 1:
+            raise ValueError(f'num_classes must be positive, got {num_classes}')
+        self.transitions = torch.nn.Parameter(torch.zeros(self.num_classes, self.num_classes, dtype=torch.float32))
+        self.initial = torch.nn.Parameter(torch.zeros(self.num_classes, dtype=torch.float32))
+
+    @classmethod
+    def from_counts(cls, counts, smoothing: float = 1.0, initial_counts=None):
+        """Start from label statistics: transitions = `postprocess.transition_log_probs(counts, smoothing)` of (C, C)
+        transition counts (`postprocess.transition_counts`); initial = log((n + s) / (sum + C s)) of (C,) first-label counts,
+        zeros without them. The smoothing must be positive: -inf scores are out of the loss's contract."""
+        from .postprocess import transition_log_probs
+        import numpy as np
+        if not smoothing > 0:
+            raise ValueError(f'smoothing must be positive (a -inf score is out of contract for training), got {smoothing}')
+        A = transition_log_probs(counts, smoothing)
+        crf = cls(A.shape[0])
+        with torch.no_grad():
+            crf.transitions.copy_(A)
+            if initial_counts is not None:
+                n = np.asarray(initial_counts.cpu() if torch.is_tensor(initial_counts) else initial_counts).astype(np.float64)
+                if n.shape != (crf.num_classes,):
+                    raise ValueError(f'initial counts must be ({crf.num_classes},), not {n.shape}')
+                s = float(smoothing)
+                crf.initial.copy_(torch.from_numpy(np.log((n + s) / (n.sum() + n.size * s)).astype(np.float32)))
+        return crf
+
+    def decoder(self):
+        """A `postprocess.ViterbiDecoder` over detached copies of the current parameters (for `process_output(decoder=)` /
+        `EvaluationAccumulator(decoder=)`); later training steps do not change it."""
+        from .postprocess import ViterbiDecoder
+        return ViterbiDecoder(self.transitions.detach().clone(), self.initial.detach().clone())
+
+    def extra_repr(self):
+        return f'num_classes={self.num_classes}'
+
+
+def crf_loss(input, target, crf, ignore_index=-1):
+    """The linear-chain CRF loss of (bs, C, T, E) fp32 log-probabilities `input` (the model's outputs at the model's rate, as
+    the NLL terms get them) and int64 (bs, T, E) `target` under the LinearChainCRF `crf`: transitions A fp32 (C, C), row =
+    from, column = to, and initial pi fp32 (C,). Finite A and pi are in contract; +-inf and NaN are not.
+
+    A sequence is (clip b, entity e). Its kept steps t_0 < t_1 < ... < t_{K-1} are those with 0 <= target[b, t, e] < C and
+    target != ignore_index (the NLL terms' rule); every other step is removed from the chain -- padding, an absent entity and a
+    hole in the middle are the same case -- and transitions link consecutive kept steps. K = 0 contributes nothing. With
+    x_k[c] = input[b, c, t_k, e] and y_k = target[b, t_k, e]:
+
+        alpha_0[c] = pi[c] + x_0[c]
+        alpha_k[c] = x_k[c] + logsumexp_{c'} (alpha_{k-1}[c'] + A[c', c])          k = 1 .. K-1
+        logZ       = logsumexp_c alpha_{K-1}[c]
+        gold       = pi[y_0] + x_0[y_0] + sum_{k>=1} (A[y_{k-1}, y_k] + x_k[y_k])
+        nll_seq    = logZ - gold                                                    (>= 0)
+        loss       = (sum over sequences of nll_seq) / (sum over sequences of K)
+
+    The loss is 0 when no step is kept. The count of the term (what a data-parallel count reducer receives) is the total
+    number of kept steps: the term is on the scale of the per-step NLL terms. Gradients, with g = dloss / count:
+
+        beta_{K-1}[c] = 0
+        beta_k[c']    = logsumexp_c (A[c', c] + x_{k+1}[c] + beta_{k+1}[c])
+        gamma_k[c]    = exp(alpha_k[c] + beta_k[c] - logZ)
+        xi_k[c', c]   = exp(alpha_{k-1}[c'] + A[c', c] + x_k[c] + beta_k[c] - logZ)
+        d input[b, c, t_k, e] = g (gamma_k[c] - [c = y_k]), 0 at every removed step
+        dA[c', c] = g sum_seq sum_{k>=1} (xi_k[c', c] - [y_{k-1} = c', y_k = c])       dpi[c] = g sum_seq (gamma_0[c] - [y_0 = c])
+
+    The per-sequence recursions run in fp32, in the log domain with the maximum subtracted; the sums over sequences are carried
+    in fp64 in index order and rounded once; no floating-point atomics, so two runs give the same bits. tests/crf_ref.py at
+    fp64 is this definition in numpy. ValueError beyond `kernels.crf_limits()` (64 classes, 4096 steps), before any launch.
+    (The input rides on an NLL term of weight 0, whose value is dropped and which gets no backward work.)"""
+    return _run([input], [target], [_NLL], [0.0], ignore_index, 'mean', crf=[(0, 1.0, crf)])[1]
+
+
 _KIND = {nll_loss: _NLL, F.nll_loss: _NLL, binary_cross_entropy_loss: _BCE, budget_loss: _BUDGET}
 
 # Data-parallel normalisation (SURVEY 8e (b)): every term is a sum over the valid (non-ignored) targets divided by their
@@ -104,7 +189,9 @@ def get_count_reducer():
 class _MultiTaskLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec, *inputs):
-        kinds, targets, weights, ignore, reducer, smoothing, options = spec
+        kinds, targets, weights, ignore, reducer, smoothing, options, crf = spec
+        # behind the n inputs: (transitions, initial) of every CRF term, so that autograd hands their gradients to the modules
+        inputs, crf_params = inputs[:len(kinds)], inputs[len(kinds):]
         K = get_kernels()
         terms = []
         for x, y, k, w in zip(inputs, targets, kinds, weights):
@@ -120,11 +207,18 @@ class _MultiTaskLoss(torch.autograd.Function):
         fwd = K.weighted_loss_fwd if ctx.weighted else K.multitask_loss_fwd
         smooth = [dict(input=terms[i]['input'], target=terms[i]['target'], weight=w, tau=tau, ignore=ignore)
                   for i, w, tau in smoothing]
-        if smooth:
-            # the smoothing terms follow the n zipped ones in the same tensors: one more launch writes the tail in place
-            n = len(terms)
-            losses, stats = fwd(terms, room=len(smooth))
-            K.smooth_loss_fwd(smooth, losses[n:], stats[n:])
+        chains = [dict(input=terms[i]['input'], target=terms[i]['target'], weight=w, ignore=ignore,
+                       transitions=crf_params[2 * j].detach().contiguous(), initial=crf_params[2 * j + 1].detach().contiguous())
+                  for j, (i, w) in enumerate(crf)]
+        if smooth or chains:
+            # the smoothing terms, then the CRF terms, follow the n zipped ones in the same tensors: one more launch (pair)
+            # each writes its part of the tail in place
+            n, ns = len(terms), len(smooth)
+            losses, stats = fwd(terms, room=ns + len(chains))
+            if smooth:
+                K.smooth_loss_fwd(smooth, losses[n:n + ns], stats[n:n + ns])
+            if chains:
+                K.crf_nll_fwd(chains, losses[n + ns:], stats[n + ns:])
         else:
             losses, stats = fwd(terms)
         if reducer is not None:
@@ -135,23 +229,30 @@ class _MultiTaskLoss(torch.autograd.Function):
             # With class weights the column handed over is den, the sum of the kept weights: the global WEIGHTED mean.
             eff = reducer(stats[:, 1].clone())
             val = stats[:, 0] / eff
-            soft = torch.tensor([k != _NLL for k in kinds] + [True] * len(smooth), device=val.device)
+            soft = torch.tensor([k != _NLL for k in kinds] + [True] * (len(smooth) + len(chains)), device=val.device)
             val = torch.where(soft & (eff <= 0), torch.zeros_like(val), val)
-            w = torch.tensor([float(x) for x in weights] + [t['weight'] for t in smooth], dtype=torch.float32,
+            w = torch.tensor([float(x) for x in weights] + [t['weight'] for t in smooth + chains], dtype=torch.float32,
                              device=val.device)
             losses = w * val.to(torch.float32)
             stats = torch.stack([stats[:, 0], eff], 1).contiguous()
         ctx.terms, ctx.stats = terms, stats
         ctx.smooth, ctx.smooth_index = smooth, [i for i, _, _ in smoothing]
+        ctx.chains, ctx.chain_index = chains, [i for i, _ in crf]
         return losses
 
     @staticmethod
     def backward(ctx, dlosses):
         need = [ctx.needs_input_grad[i + 1] and t['weight'] != 0 for i, t in enumerate(ctx.terms)]
         need_smooth = [ctx.needs_input_grad[i + 1] and t['weight'] != 0 for i, t in zip(ctx.smooth_index, ctx.smooth)]
-        if not any(need) and not any(need_smooth):
-            return (None,) + tuple(None for _ in ctx.terms)
-        K, n = get_kernels(), len(ctx.terms)
+        n, ns = len(ctx.terms), len(ctx.smooth)
+        # a CRF term asks for d(input) and for (dA, dpi) separately; weight 0 or nothing to differentiate: no backward work
+        need_chain_x = [ctx.needs_input_grad[i + 1] and t['weight'] != 0 for i, t in zip(ctx.chain_index, ctx.chains)]
+        need_chain_p = [(ctx.needs_input_grad[1 + n + 2 * j] or ctx.needs_input_grad[2 + n + 2 * j]) and t['weight'] != 0
+                        for j, t in enumerate(ctx.chains)]
+        no_params = (None,) * (2 * len(ctx.chains))
+        if not any(need) and not any(need_smooth) and not any(need_chain_x) and not any(need_chain_p):
+            return (None,) + tuple(None for _ in ctx.terms) + no_params
+        K = get_kernels()
         bwd = K.weighted_loss_bwd if ctx.weighted else K.multitask_loss_bwd
         dins = bwd(ctx.terms, ctx.stats, dlosses, need) if any(need) else [None] * n
         if any(need_smooth):
@@ -164,8 +265,24 @@ class _MultiTaskLoss(torch.autograd.Function):
                     if not acc[j]:
                         dins[i] = torch.empty_like(ctx.terms[i]['input'])
                     sdins[j] = dins[i]
-            K.smooth_loss_bwd(ctx.smooth, ctx.stats[n:], dlosses.contiguous()[n:], sdins, acc)
-        return (None,) + tuple(dins)
+            K.smooth_loss_bwd(ctx.smooth, ctx.stats[n:n + ns], dlosses.contiguous()[n:n + ns], sdins, acc)
+        if not any(need_chain_x) and not any(need_chain_p):
+            return (None,) + tuple(dins) + no_params
+        # the CRF launch adds into the buffer the NLL or smoothing launch of that input wrote on this stream, or stores into
+        # one of its own
+        dins, cdins, acc = list(dins), [None] * len(ctx.chains), [False] * len(ctx.chains)
+        for j, (i, nd) in enumerate(zip(ctx.chain_index, need_chain_x)):
+            if nd:
+                acc[j] = dins[i] is not None
+                if not acc[j]:
+                    dins[i] = torch.empty_like(ctx.terms[i]['input'])
+                cdins[j] = dins[i]
+        grads = K.crf_nll_bwd(ctx.chains, ctx.stats[n + ns:], dlosses.contiguous()[n + ns:], cdins, acc, need_chain_p)
+        params = []
+        for j, gr in enumerate(grads):
+            dA, dpi = gr if need_chain_p[j] else (None, None)
+            params += [dA if ctx.needs_input_grad[1 + n + 2 * j] else None, dpi if ctx.needs_input_grad[2 + n + 2 * j] else None]
+        return (None,) + tuple(dins) + tuple(params)
 
 
 _uploaded_weights = {}   # (values, device) -> fp32 tensor: a host sequence of class weights is uploaded once per device
@@ -217,8 +334,35 @@ def _options(inputs, kinds, class_weights, positive_class_weights):
     return cws, pws
 
 
+def _crf_terms(crf, inputs, kinds):
+    """The `crf` list of multi_task_loss checked against the call, before any launch: [(index, weight)], [module]."""
+    terms, modules = [], []
+    for entry in crf:
+        i, w, module = entry
+        i, w = int(i), float(w)
+        if not 0 <= i < len(kinds) or kinds[i] != _NLL:
+            raise ValueError(f'CRF term on input {i}: not one of the NLL terms of this call')
+        x = inputs[i]
+        if x.dim() != 4:
+            raise ValueError(f'CRF term on input {i}: (bs, C, T, E) log-probabilities are expected, got {tuple(x.shape)}')
+        if not isinstance(module, LinearChainCRF):
+            raise ValueError(f'CRF term on input {i}: a LinearChainCRF module is expected, got {type(module).__name__}')
+        if module.num_classes != x.shape[1]:
+            raise ValueError(f'CRF term on input {i}: a module of {module.num_classes} classes for an input of {x.shape[1]}')
+        max_classes, max_steps = get_kernels().crf_limits()
+        if x.shape[1] > max_classes or x.shape[2] > max_steps:
+            raise ValueError(f'CRF term on input {i}: up to {max_classes} classes and {max_steps} model steps are taken, '
+                             f'not {x.shape[1]} and {x.shape[2]}')
+        terms.append((i, w))
+        modules.append(module)
+    if len({i for i, _ in terms}) != len(terms):
+        # (both would write the gradient buffer of that input)
+        raise ValueError('more than one CRF term on the same input')
+    return terms, modules
+
+
 def _run(inputs, targets, kinds, weights, ignore_value, reduction, smoothing=(), class_weights=None,
-         positive_class_weights=None):
+         positive_class_weights=None, crf=()):
     if reduction != 'mean':
         raise NotImplementedError("only reduction='mean' (the reference's setting) is implemented")
     options = _options(inputs, kinds, class_weights, positive_class_weights)
@@ -231,16 +375,18 @@ def _run(inputs, targets, kinds, weights, ignore_value, reduction, smoothing=(),
     if len({i for i, _, _ in smoothing}) != len(smoothing):
         # (both would write the gradient buffer of that input in the same launch)
         raise ValueError('more than one smoothing term on the same input')
+    crf, modules = _crf_terms(crf, inputs, kinds)
+    crf_params = [p for m in modules for p in (m.transitions, m.initial)]
     # the scope's reducer, and only while autograd records (read here: grad mode is off inside Function.forward)
     reducer = _count_reducer if torch.is_grad_enabled() else None
     losses = _MultiTaskLoss.apply((list(kinds), list(targets), [float(w) for w in weights], ignore_value, reducer,
-                                   smoothing, options), *inputs)
+                                   smoothing, options, crf), *inputs, *crf_params)
     return list(losses.unbind(0))
 
 
 def multi_task_loss(input: list, target: list, loss_functions: list, weight: list = None, ignore_value=-1,
                     reduction: str = 'mean', smoothing: list = None, class_weights: list = None,
-                    positive_class_weights: list = None):
+                    positive_class_weights: list = None, crf: list = None):
     """pyrutils/torch/losses.py:39-51: the list of weighted losses, one per (input, target, loss function).
 
     class_weights / positive_class_weights: lists aligned with the terms. class_weights[i] is None, a [C] tensor (taken as
@@ -251,7 +397,13 @@ def multi_task_loss(input: list, target: list, loss_functions: list, weight: lis
 
     smoothing: a list of (index, weight, tau); term j is weight * temporal_smoothing_loss(input[index], target[index], tau),
     appended after the zipped terms in list order (input[index] must be an NLL term's (bs, C, T, E) log-probabilities). Each
-    input still receives ONE gradient: the smoothing terms take the inputs by index."""
+    input still receives ONE gradient: the smoothing terms take the inputs by index.
+
+    crf: a list of (index, weight, module), module a LinearChainCRF; term j is weight * crf_loss(input[index], target[index],
+    module), appended after the zipped terms and after the smoothing terms, in list order. input[index] must be an NLL term's
+    (bs, C, T, E) input. A class-count mismatch, a non-NLL index, two CRF terms on one input or a shape beyond
+    kernels.crf_limits() raises ValueError before any launch. dA and dpi come back as the gradients of the module's
+    parameters; a term of weight 0, or one whose parameters and input need no gradient, gets no backward work."""
     if weight is None:
         weight = [1.0] * len(input)
     n = min(len(input), len(target), len(loss_functions), len(weight))  # zip semantics
@@ -262,11 +414,30 @@ def multi_task_loss(input: list, target: list, loss_functions: list, weight: lis
         kinds.append(_KIND[fn])
     return _run(list(input[:n]), list(target[:n]), kinds, list(weight[:n]), ignore_value, reduction, smoothing or (),
                 None if class_weights is None else list(class_weights)[:n],
-                None if positive_class_weights is None else list(positive_class_weights)[:n])
+                None if positive_class_weights is None else list(positive_class_weights)[:n], crf or ())
 
 
-def select_loss(model_name: str, model_input_type: str, dataset_name: str, cfg):
-    """vhoi/losses.py:8-70 for model '2G-GCN': (criterion, loss_names). cfg needs `.get('misc', default_value={})`."""
+_CRF_KEYS = ('SAR', 'SAP', 'OAR', 'OAP')
+
+
+def _crf_keys(dataset_name, cfg, crf):
+    """The keys of the CRF terms select_loss appends for this configuration (misc.crf_loss.add), in term order. crf: the dict
+    of modules, or None where only the configuration is known (then: every final-level NLL term of the dataset)."""
+    if not _misc(cfg).get('crf_loss', {}).get('add', False):
+        return []
+    allowed = _CRF_KEYS if dataset_name == 'cad120' else _CRF_KEYS[:2]
+    if crf is None:
+        return list(allowed)
+    unknown = [k for k in crf if k not in allowed]
+    if unknown:
+        raise ValueError(f'CRF modules for {unknown}: the final-level NLL terms of {dataset_name} are {list(allowed)}')
+    return [k for k in allowed if k in crf]
+
+
+def select_loss(model_name: str, model_input_type: str, dataset_name: str, cfg, *, crf=None):
+    """vhoi/losses.py:8-70 for model '2G-GCN': (criterion, loss_names). cfg needs `.get('misc', default_value={})`.
+    crf: with misc.crf_loss = {add: true, weight: w}, a dict of LinearChainCRF modules keyed by 'SAR', 'SAP', 'OAR', 'OAP':
+    one CRF term per key present, on the final-level NLL term of that name, weighted w times that term's weight."""
     if model_name != '2G-GCN':
         raise NotImplementedError(f'{model_name}: only the 2G-GCN hot path is built (SURVEY section 8)')
     misc = _misc(cfg)
@@ -309,15 +480,27 @@ def select_loss(model_name: str, model_input_type: str, dataset_name: str, cfg):
     p = seg.get('positive_class_weight', 1)
     if p != 1:
         options['positive_class_weights'] = [float(p) if fn is binary_cross_entropy_loss else None for fn in fns]
+    first = len(fns) - (4 if cad else 2)
+    if misc.get('crf_loss', {}).get('add', False):
+        # one CRF term per module, on the final-level NLL term of that name and weighted relative to it, as the smoothing
+        # terms are; appended after them
+        if not crf:
+            raise ValueError('misc.crf_loss.add is set, but select_loss was given no CRF modules (crf={name: LinearChainCRF})')
+        c_weight = misc.get('crf_loss', {}).get('weight', 1.0)
+        index = {names[i][len('NLL_'):]: i for i in range(first, len(fns))}
+        keys = _crf_keys(dataset_name, cfg, crf)
+        options['crf'] = [(index[k], c_weight * weight[index[k]], crf[k]) for k in keys]
+        crf_names = ['CRF_' + k for k in keys]
+    else:
+        crf_names = []
     smooth = misc.get('smoothing_loss', {})
     if not smooth.get('add', False):
-        return partial(multi_task_loss, loss_functions=fns, weight=weight, **options), names
+        return partial(multi_task_loss, loss_functions=fns, weight=weight, **options), names + crf_names
     # one smoothing term per final-level NLL term (the last 2 or 4 of the list; not the frame-level _F ones), weighted
     # relative to it: the stage-1 pretraining zeros and the anticipation weight carry over
-    first = len(fns) - (4 if cad else 2)
     s_weight, tau = smooth.get('weight', 0.15), smooth.get('tau', 4.0)
     smoothing = [(i, s_weight * weight[i], tau) for i in range(first, len(fns))]
-    names = names + ['TMSE_' + names[i][len('NLL_'):] for i in range(first, len(fns))]
+    names = names + ['TMSE_' + names[i][len('NLL_'):] for i in range(first, len(fns))] + crf_names
     return partial(multi_task_loss, loss_functions=fns, weight=weight, smoothing=smoothing, **options), names
 
 
@@ -328,20 +511,20 @@ def _n_smoothing_terms(dataset_name, cfg):
     return 4 if dataset_name == 'cad120' else 2
 
 
-def select_loss_types(model_name: str, dataset_name: str, cfg):
-    """vhoi/losses.py:72-80."""
+def select_loss_types(model_name: str, dataset_name: str, cfg, *, crf=None):
+    """vhoi/losses.py:72-80. crf: the dict of modules given to select_loss (None: one CRF term per final-level NLL term)."""
     if model_name != '2G-GCN':
         raise ValueError(f'Multi-task learning option not implemented for {model_name}')
     types = ['budget'] * 2 + ['bce'] * 2 + ['softmax'] * 8 if dataset_name == 'cad120' else ['budget', 'bce'] + ['softmax'] * 4
-    return types + ['mse'] * _n_smoothing_terms(dataset_name, cfg)
+    return types + ['mse'] * _n_smoothing_terms(dataset_name, cfg) + ['crf'] * len(_crf_keys(dataset_name, cfg, crf))
 
 
-def select_loss_learning_mask(model_name: str, dataset_name: str, cfg):
-    """vhoi/losses.py:83-91."""
+def select_loss_learning_mask(model_name: str, dataset_name: str, cfg, *, crf=None):
+    """vhoi/losses.py:83-91. crf: as for select_loss_types."""
     if model_name != '2G-GCN':
         raise ValueError(f'Multi-task learning option not implemented for {model_name}')
     mask = [False] * 4 + [True] * 8 if dataset_name == 'cad120' else [False] * 2 + [True] * 4
-    return mask + [False] * _n_smoothing_terms(dataset_name, cfg)
+    return mask + [False] * (_n_smoothing_terms(dataset_name, cfg) + len(_crf_keys(dataset_name, cfg, crf)))
 
 
 def class_counts(targets, num_classes, ignore_index=-1, out=None):

@@ -1268,6 +1268,62 @@ int twog_viterbi_decode(const float* logp, int bs, int n_classes, int T, int E, 
 int twog_transition_counts(const int64_t* targets, int bs, int T_tgt, int E, int n_classes, int stride,
                            int64_t ignore_index, int64_t* counts, void* stream);
 
+/* ===============================================================================================================
+ * Linear-chain CRF loss: the sequence negative log-likelihood under learned transition scores (the
+ * reference project has no such term, tests/crf_ref.py at fp64 is the specification). The scores it trains go to
+ * twog_viterbi_decode unchanged.
+ *   input  fp32 [bs][C][T][E] log-probabilities (the model's outputs at the model's rate, as the NLL terms get them)
+ *   target int64 [bs][T][E]
+ *   A      fp32 [C][C] transition scores, row = from, column = to (the convention of twog_viterbi_decode); pi fp32 [C].
+ *          Finite A and pi are in contract; +-inf and NaN are not.
+ * A sequence is (clip b, entity e). Its kept steps t_0 < t_1 < ... < t_{K-1} are those with 0 <= target[b][t][e] < C and
+ * target != ignore_index (the NLL terms' rule); every other step is removed from the chain -- padding, an absent entity and
+ * a hole in the middle are the same case -- and transitions link consecutive kept steps. K = 0 contributes nothing.
+ * With x_k[c] = input[b][c][t_k][e] and y_k = target[b][t_k][e]:
+ *     alpha_0[c] = pi[c] + x_0[c]
+ *     alpha_k[c] = x_k[c] + logsumexp_{c'} (alpha_{k-1}[c'] + A[c'][c])          k = 1 .. K-1
+ *     logZ       = logsumexp_c alpha_{K-1}[c]
+ *     gold       = pi[y_0] + x_0[y_0] + sum_{k>=1} (A[y_{k-1}][y_k] + x_k[y_k])
+ *     nll_seq    = logZ - gold                                                    (>= 0)
+ *     loss       = weight * (sum over sequences of nll_seq) / (sum over sequences of K)      (0 when no step is kept)
+ * stats[0] = sum of nll_seq, stats[1] = sum of K (the count of the term: it is on the scale of the per-step NLL terms).
+ * Gradients, with g = dloss * weight / stats[1] (0 when stats[1] <= 0; the caller may have replaced stats[1] by a global
+ * count):
+ *     beta_{K-1}[c] = 0
+ *     beta_k[c']    = logsumexp_c (A[c'][c] + x_{k+1}[c] + beta_{k+1}[c])
+ *     gamma_k[c]    = exp(alpha_k[c] + beta_k[c] - logZ)
+ *     xi_k[c'][c]   = exp(alpha_{k-1}[c'] + A[c'][c] + x_k[c] + beta_k[c] - logZ)
+ *     dinput[b][c][t_k][e] = g * (gamma_k[c] - [c = y_k]); every removed step gets 0: the tensor is written completely, with
+ *                            no separate clear (accumulate != 0: the same values are ADDED to what the buffer holds)
+ *     dA[c'][c] = g * sum_seq sum_{k>=1} (xi_k[c'][c] - [y_{k-1} = c', y_k = c])
+ *     dpi[c]    = g * sum_seq (gamma_0[c] - [y_0 = c])
+ * Arithmetic: the per-sequence recursions run in fp32, every logsumexp in the log domain with the maximum subtracted.
+ * The sums over sequences (nll_seq, K, dA, dpi) are carried in fp64 in index order and rounded to fp32 once. No
+ * floating-point atomics: two runs on the same inputs give the same bits, and a sequence gives the same per-sequence
+ * values in any batch.
+ * Workspaces (twog_crf_workspace, launch-free; all device memory, 4-byte aligned):
+ *   alpha   bs * E * T * C floats: alpha of every kept step, written by the forward, read by the backward
+ *   seq     bs * E * TWOG_CRF_SEQ_WORDS floats per sequence: logZ, gold, nll_seq, K (the bits of an int32)
+ *   partials bs * E * (C + 1) * C floats: the backward's per-sequence sums for dA (C rows) and dpi (one row); needed only
+ *           when dA / dpi are asked for
+ * twog_crf_nll_fwd: two launches (recursion, sums). twog_crf_nll_bwd: the recursion (writes dinput when it is not NULL),
+ * then, when dA and dpi are not NULL (both or neither), the reduction over sequences, which stores (accumulate_params == 0)
+ * or adds. The time axis is staged through LDS in chunks of TWOG_CRF_CHUNK steps.
+ * twog_crf_limits: the largest C (64) and T (4096), those of twog_viterbi_limits. Returns: -1 for a bad size, -2 beyond
+ * the limits (or C * T * E >= 2^31, bs > 65535), -3 for a missing buffer.
+ * =============================================================================================================== */
+#define TWOG_CRF_CHUNK 16
+#define TWOG_CRF_SEQ_WORDS 4
+int twog_crf_limits(int* max_classes, int* max_steps);
+int twog_crf_workspace(int bs, int n_classes, int T, int E, size_t* alpha_bytes, size_t* seq_bytes, size_t* partial_bytes);
+int twog_crf_nll_fwd(const float* input, const int64_t* target, int bs, int n_classes, int T, int E, const float* A,
+                     const float* pi, int64_t ignore_index, float weight, float* alpha, float* seq, double* stats,
+                     float* loss, void* stream);
+int twog_crf_nll_bwd(const float* input, const int64_t* target, int bs, int n_classes, int T, int E, const float* A,
+                     int64_t ignore_index, float weight, const float* alpha, const float* seq, const double* stats,
+                     const float* dloss, float* dinput, int accumulate, float* partials, float* dA, float* dpi,
+                     int accumulate_params, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
