@@ -2,10 +2,8 @@
 // and backward. The reference project has no such term; the definition is the numpy specification
 // tests/crf_ref.py, restated at twog_crf_nll_fwd in include/twog_gcn.h.
 //
-// Shape of the recursion kernels, after viterbi.hip: serial in t, parallel in the class. One wave per sequence (clip b,
-// entity e), lane c owns class c. A workgroup is one clip and up to CRF_MAX_WAVES neighbouring entities; together its waves
-// stage time chunks of the clip's (C, chunk, E) slab through LDS, the loads of the next chunk in flight while this one is
-// consumed. The labels of a chunk are fetched the same way, one per lane, so a step reads its label from a register and the
+// The recursion kernels have the shape of label_chain.h (one wave per sequence, lane c owns class c, the slab staged in
+// chunks). The labels of a chunk are fetched the same way, one per lane, so a step reads its label from a register and the
 // kept / removed decision is wave-uniform.
 //   forward : lane c holds the column A[:, c]; alpha of the previous kept step comes from the other lanes by v_readlane.
 //   backward: lane c' holds the row A[c', :] and its row of sum_k (xi_k - indicator) in registers; u = x + beta of the next
@@ -16,32 +14,25 @@
 // fast forms): finite A and pi of any size are in contract, nothing can underflow as a whole.
 // No floating-point atomics: the sums over sequences are made by second-stage kernels in index order in fp64.
 #include "twog_common.h"
+#include "label_chain.h"
 
 namespace {
 
-constexpr int CRF_MAX_CLASSES = 64;     // one wave: lane c owns class c (the limits of viterbi.hip)
-constexpr int CRF_MAX_STEPS = 4096;
-constexpr int CRF_CHUNK = TWOG_CRF_CHUNK;
-constexpr int CRF_MAX_WAVES = 8;        // entities of one clip per workgroup ...
-constexpr int CRF_MAX_WAVES_WIDE = 4;   // ... and beyond 32 classes: one wave per SIMD, so that a lane's two rows of 64 values
-                                        // (backward: A[c', :] and its sums) stay in the register file with no scratch
-__host__ __device__ constexpr int crf_max_waves(int classes) { return classes > 32 ? CRF_MAX_WAVES_WIDE : CRF_MAX_WAVES; }
-constexpr size_t CRF_LDS_LIMIT = 160 * 1024;
+// Entities of one clip per workgroup: LC_MAX_WAVES, and beyond 32 classes one wave per SIMD, so that a lane's two rows of 64
+// values (backward: A[c', :] and its sums) stay in the register file with no scratch.
+constexpr int CRF_MAX_WAVES_WIDE = 4;
+__host__ __device__ constexpr int crf_max_waves(int classes) { return classes > 32 ? CRF_MAX_WAVES_WIDE : LC_MAX_WAVES; }
 constexpr int CRF_FINAL_THREADS = 256;
 
 struct CrfPlan {
-    int waves;             // entities per workgroup
-    int groups;            // workgroups per clip
-    size_t buf_floats;     // one LDS buffer: C rows of CRF_CHUNK * waves + 1 floats
+    LcGeometry g;
     size_t alpha_bytes, seq_bytes, partial_bytes;
 };
 
-// The one statement of the launch geometry and the workspaces: twog_crf_workspace reports it, the launchers use it.
+// The one statement of the workspaces: twog_crf_workspace reports it, the launchers use it.
 inline CrfPlan crf_plan(int bs, int C, int T, int E) {
     CrfPlan p;
-    p.waves = E < crf_max_waves(C) ? E : crf_max_waves(C);
-    p.groups = (E + p.waves - 1) / p.waves;
-    p.buf_floats = (size_t)C * (CRF_CHUNK * p.waves + 1);          // odd row stride: lanes c hit different banks
+    p.g = lc_geometry(C, E, crf_max_waves(C));
     const size_t n_seq = (size_t)bs * E;
     p.alpha_bytes = n_seq * T * C * sizeof(float);
     p.seq_bytes = n_seq * TWOG_CRF_SEQ_WORDS * sizeof(float);
@@ -51,33 +42,11 @@ inline CrfPlan crf_plan(int bs, int C, int T, int E) {
 
 // the label of a step as the chain sees it: the class of a kept step, -1 for a removed one (the NLL terms' rule)
 __device__ __forceinline__ int chain_label(long long y, long long ignore, int C) {
-    return (y != ignore && y >= 0 && y < C) ? (int)y : -1;
+    return twog_label_kept(y, ignore, C) ? (int)y : -1;
 }
 
-// What a thread stages of every chunk: elements k * nthreads + tid of the (C, chunk, EW) slab, k = 0 .. CMAX / 4 - 1. A class
-// row of the slab is CRF_CHUNK * EW = nthreads / 4 elements, so element k is class 4 k + c0 at the same (step, entity) for
-// every k: the offsets are one base and one stride each.
-struct Staging {
-    int c0, tt, soff0, sstep;
-    int64_t goff0, gstep;
-    bool column;              // the thread's entity exists
-    __device__ __forceinline__ void init(int tid, int C, int T, int E, int EW, int e0) {
-        const int per_class = CRF_CHUNK * EW, row = per_class + 1;
-        c0 = tid / per_class;
-        const int rem = tid - c0 * per_class;
-        tt = rem / EW;
-        const int ew = rem - tt * EW;
-        column = e0 + ew < E;
-        goff0 = ((int64_t)c0 * T + tt) * E + ew;
-        gstep = (int64_t)4 * T * E;
-        soff0 = c0 * row + rem;
-        sstep = 4 * row;
-    }
-    __device__ __forceinline__ bool has(int k, int C) const { return column && 4 * k + c0 < C; }
-};
-
 // grid (groups, bs), 64 * EW threads: wave w runs entity blockIdx.x * EW + w of clip blockIdx.y.
-// LDS: stage[2][C][CRF_CHUNK * EW + 1] floats.
+// LDS: stage[2][C][lc_row(EW)] floats.
 // alpha [bs * E][T][C]: written at the kept steps only. seq [bs * E][TWOG_CRF_SEQ_WORDS]: logZ, gold, nll, K (int bits).
 template <int CMAX>
 __global__ __launch_bounds__(64 * crf_max_waves(CMAX)) void crf_fwd_kernel(
@@ -88,27 +57,17 @@ __global__ __launch_bounds__(64 * crf_max_waves(CMAX)) void crf_fwd_kernel(
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int b = blockIdx.y, e0 = blockIdx.x * EW, e = e0 + w;
     const bool runs = e < E;                          // wave-uniform; a wave without an entity still stages
-    const int row = CRF_CHUNK * EW + 1;
+    const int row = lc_row(EW);
     const int buf_floats = C * row;
     float* stage = smem;
 
-    Staging S;
+    LcStager S;
     S.init(tid, C, T, E, EW, e0);
     const float* base = logp + (int64_t)b * C * T * E + e0;
     float pre[R];
-    auto fetch = [&](int t0) {
-#pragma unroll
-        for (int k = 0; k < R; ++k)
-            pre[k] = (S.has(k, C) && t0 + S.tt < T) ? base[(int64_t)t0 * E + S.goff0 + k * S.gstep] : 0.0f;
-    };
-    auto commit = [&](int buf) {
-#pragma unroll
-        for (int k = 0; k < R; ++k)
-            if (S.has(k, C)) stage[buf * buf_floats + S.soff0 + k * S.sstep] = pre[k];
-    };
     const long long* labels = target + (int64_t)b * T * E + (runs ? e : 0);
     auto fetch_label = [&](int t0) {
-        return (runs && lane < CRF_CHUNK && t0 + lane < T) ? chain_label(labels[(int64_t)(t0 + lane) * E], ignore, C) : -1;
+        return (runs && lane < LC_CHUNK && t0 + lane < T) ? chain_label(labels[(int64_t)(t0 + lane) * E], ignore, C) : -1;
     };
 
     const float NEG_INF = -__builtin_inff();
@@ -124,21 +83,22 @@ __global__ __launch_bounds__(64 * crf_max_waves(CMAX)) void crf_fwd_kernel(
 
     float alpha = NEG_INF, gold = 0.0f;
     int K = 0, y_prev = 0;
-    const int n_chunks = (T + CRF_CHUNK - 1) / CRF_CHUNK;
-    fetch(0);
+    const int n_chunks = (T + LC_CHUNK - 1) / LC_CHUNK;
+    S.fetch(base, 0, T, pre);
     int lab_pre = fetch_label(0);
     for (int ch = 0; ch < n_chunks; ++ch) {
-        const int buf = ch & 1, t0 = ch * CRF_CHUNK;
-        commit(buf);          // buffer `buf` was last read in chunk ch - 2, which every wave left before the barrier of ch - 1
+        const int buf = ch & 1, t0 = ch * LC_CHUNK;
+        // buffer `buf` was last read in chunk ch - 2, which every wave left before the barrier of ch - 1
+        S.commit(stage + buf * buf_floats, pre);
         __syncthreads();
         const int lab = lab_pre;
         if (ch + 1 < n_chunks) {                          // in flight while this chunk is consumed
-            fetch(t0 + CRF_CHUNK);
-            lab_pre = fetch_label(t0 + CRF_CHUNK);
+            S.fetch(base, t0 + LC_CHUNK, T, pre);
+            lab_pre = fetch_label(t0 + LC_CHUNK);
         }
         if (!runs) continue;
         const float* mine = stage + buf * buf_floats + my_row;
-        const int n_here = T - t0 < CRF_CHUNK ? T - t0 : CRF_CHUNK;
+        const int n_here = T - t0 < LC_CHUNK ? T - t0 : LC_CHUNK;
         for (int tt = 0; tt < n_here; ++tt) {
             const int y = __builtin_amdgcn_readlane(lab, tt);
             if (y < 0) continue;                          // a removed step: not part of the chain
@@ -223,7 +183,7 @@ __global__ __launch_bounds__(64 * crf_max_waves(CMAX)) void crf_bwd_kernel(
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int b = blockIdx.y, e0 = blockIdx.x * EW, e = e0 + w;
     const bool runs = e < E;
-    const int row = CRF_CHUNK * EW + 1;
+    const int row = lc_row(EW);
     const int buf_floats = C * row;
     float* stage = smem;
     float* out = smem + 2 * buf_floats;
@@ -231,25 +191,28 @@ __global__ __launch_bounds__(64 * crf_max_waves(CMAX)) void crf_bwd_kernel(
     const double cnt = stats[1];
     const float g = cnt > 0.0 ? weight * dloss[0] / (float)cnt : 0.0f;
 
-    Staging S;
+    LcStager S;
     S.init(tid, C, T, E, EW, e0);
     const float* base = logp + (int64_t)b * C * T * E + e0;
     float* dbase = dinput ? dinput + (int64_t)b * C * T * E + e0 : nullptr;
     float pre[R];
+    // The staging loops are written out here on the stager's index arithmetic, not called as its members: in this kernel the
+    // member form costs three SGPRs, the allocator then rebuilds the expf / logf constants inside the step loop, and the
+    // launches at 9 to 16 classes run 1 % longer.
     auto fetch = [&](int t0) {
 #pragma unroll
         for (int k = 0; k < R; ++k)
-            pre[k] = (S.has(k, C) && t0 + S.tt < T) ? base[(int64_t)t0 * E + S.goff0 + k * S.gstep] : 0.0f;
+            pre[k] = (S.has(k) && t0 + S.tt < T) ? base[(int64_t)t0 * E + S.goff0 + k * S.gstep] : 0.0f;
     };
     auto commit = [&](int buf) {
 #pragma unroll
         for (int k = 0; k < R; ++k)
-            if (S.has(k, C)) stage[buf * buf_floats + S.soff0 + k * S.sstep] = pre[k];
+            if (S.has(k)) stage[buf * buf_floats + S.soff0 + k * S.sstep] = pre[k];
     };
     auto flush = [&](int buf, int t0) {                   // the d input of a finished chunk, in the layout it was fetched in
 #pragma unroll
         for (int k = 0; k < R; ++k) {
-            if (!S.has(k, C) || t0 + S.tt >= T) continue;
+            if (!S.has(k) || t0 + S.tt >= T) continue;
             float* dst = dbase + (int64_t)t0 * E + S.goff0 + k * S.gstep;
             const float v = out[buf * buf_floats + S.soff0 + k * S.sstep];
             *dst = accumulate ? *dst + v : v;
@@ -257,7 +220,7 @@ __global__ __launch_bounds__(64 * crf_max_waves(CMAX)) void crf_bwd_kernel(
     };
     const long long* labels = target + (int64_t)b * T * E + (runs ? e : 0);
     auto fetch_label = [&](int t0) {
-        return (runs && lane < CRF_CHUNK && t0 + lane < T) ? chain_label(labels[(int64_t)(t0 + lane) * E], ignore, C) : -1;
+        return (runs && lane < LC_CHUNK && t0 + lane < T) ? chain_label(labels[(int64_t)(t0 + lane) * E], ignore, C) : -1;
     };
 
     const float NEG_INF = -__builtin_inff();
@@ -276,24 +239,24 @@ __global__ __launch_bounds__(64 * crf_max_waves(CMAX)) void crf_bwd_kernel(
 
     float u = NEG_INF, first_d = 0.0f;                    // u = x + beta of the next kept step; first_d = gamma_0 - indicator
     int y_next = -1;                                      // its label, -1: no kept step behind this one yet
-    const int n_chunks = (T + CRF_CHUNK - 1) / CRF_CHUNK;
-    fetch((n_chunks - 1) * CRF_CHUNK);
-    int lab_pre = fetch_label((n_chunks - 1) * CRF_CHUNK);
+    const int n_chunks = (T + LC_CHUNK - 1) / LC_CHUNK;
+    fetch((n_chunks - 1) * LC_CHUNK);
+    int lab_pre = fetch_label((n_chunks - 1) * LC_CHUNK);
     float alpha_pre = alpha_in[(int64_t)(T - 1) * C];     // one step ahead of its use; a removed step's slot is read, never used
     for (int it = 0; it < n_chunks; ++it) {
-        const int buf = it & 1, t0 = (n_chunks - 1 - it) * CRF_CHUNK;
+        const int buf = it & 1, t0 = (n_chunks - 1 - it) * LC_CHUNK;
         commit(buf);
         __syncthreads();      // stage[buf] is whole, and every wave has left the chunk before: out[buf ^ 1] is whole
-        if (dinput && it > 0) flush(buf ^ 1, t0 + CRF_CHUNK);
+        if (dinput && it > 0) flush(buf ^ 1, t0 + LC_CHUNK);
         const int lab = lab_pre;
         if (it + 1 < n_chunks) {
-            fetch(t0 - CRF_CHUNK);
-            lab_pre = fetch_label(t0 - CRF_CHUNK);
+            fetch(t0 - LC_CHUNK);
+            lab_pre = fetch_label(t0 - LC_CHUNK);
         }
         if (!runs) continue;
         const float* mine = stage + buf * buf_floats + my_row;
         float* mine_out = out + buf * buf_floats + my_row;
-        const int n_here = T - t0 < CRF_CHUNK ? T - t0 : CRF_CHUNK;
+        const int n_here = T - t0 < LC_CHUNK ? T - t0 : LC_CHUNK;
         for (int tt = n_here - 1; tt >= 0; --tt) {
             const int t = t0 + tt;
             const float alpha_t = owns ? alpha_pre : NEG_INF;
@@ -355,48 +318,18 @@ __global__ __launch_bounds__(256) void crf_param_kernel(const float* __restrict_
     *dst = accumulate ? *dst + v : v;
 }
 
-inline bool crf_shape_ok(int bs, int C, int T, int E) { return bs >= 0 && C >= 1 && T >= 1 && E >= 1; }
-inline bool crf_within_limits(int bs, int C, int T, int E) {
-    return C <= CRF_MAX_CLASSES && T <= CRF_MAX_STEPS && (int64_t)C * T * E <= INT32_MAX && bs <= 65535;
-}
-
-template <int CMAX>
-int launch_crf_fwd(const CrfPlan& p, const float* logp, int bs, int C, int T, int E, const float* A, const float* pi,
-                   const int64_t* target, int64_t ignore, float* alpha, float* seq, hipStream_t st) {
-    static std::atomic<uint32_t> lds_attr_done{0};
-    twog_allow_dynamic_lds(crf_fwd_kernel<CMAX>, (int)CRF_LDS_LIMIT, lds_attr_done);
-    hipLaunchKernelGGL(crf_fwd_kernel<CMAX>, dim3(p.groups, bs), dim3(64 * p.waves), 2 * p.buf_floats * sizeof(float), st,
-                       logp, C, T, E, A, pi, reinterpret_cast<const long long*>(target), (long long)ignore, alpha, seq, p.waves);
-    TWOG_CHECK_LAUNCH();
-    return 0;
-}
-
-template <int CMAX>
-int launch_crf_bwd(const CrfPlan& p, const float* logp, int bs, int C, int T, int E, const float* A, const int64_t* target,
-                   int64_t ignore, const float* alpha, const float* seq, const double* stats, const float* dloss,
-                   float weight, float* dinput, int accumulate, float* partials, hipStream_t st) {
-    static std::atomic<uint32_t> lds_attr_done{0};
-    twog_allow_dynamic_lds(crf_bwd_kernel<CMAX>, (int)CRF_LDS_LIMIT, lds_attr_done);
-    hipLaunchKernelGGL(crf_bwd_kernel<CMAX>, dim3(p.groups, bs), dim3(64 * p.waves),
-                       (dinput ? 4 : 2) * p.buf_floats * sizeof(float), st, logp, C, T, E, A,
-                       reinterpret_cast<const long long*>(target), (long long)ignore, alpha, seq, stats, dloss, weight, dinput,
-                       accumulate, partials, p.waves);
-    TWOG_CHECK_LAUNCH();
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int twog_crf_limits(int* max_classes, int* max_steps) {
-    if (max_classes) *max_classes = CRF_MAX_CLASSES;
-    if (max_steps) *max_steps = CRF_MAX_STEPS;
+    if (max_classes) *max_classes = LC_MAX_CLASSES;
+    if (max_steps) *max_steps = LC_MAX_STEPS;
     return 0;
 }
 
 extern "C" int twog_crf_workspace(int bs, int n_classes, int T, int E, size_t* alpha_bytes, size_t* seq_bytes,
                                   size_t* partial_bytes) {
-    if (!crf_shape_ok(bs, n_classes, T, E)) return -1;
-    if (!crf_within_limits(bs, n_classes, T, E)) return -2;
+    if (!lc_shape_ok(bs, n_classes, T, E)) return -1;
+    if (!lc_launchable(bs, n_classes, T, E)) return -2;
     const CrfPlan p = crf_plan(bs, n_classes, T, E);
     if (alpha_bytes) *alpha_bytes = p.alpha_bytes;
     if (seq_bytes) *seq_bytes = p.seq_bytes;
@@ -408,17 +341,17 @@ extern "C" int twog_crf_nll_fwd(const float* input, const int64_t* target, int b
                                 const float* A, const float* pi, int64_t ignore_index, float weight, float* alpha,
                                 float* seq, double* stats, float* loss, void* stream) {
     const int C = n_classes;
-    if (!crf_shape_ok(bs, C, T, E)) return -1;
-    if (!crf_within_limits(bs, C, T, E)) return -2;
+    if (!lc_shape_ok(bs, C, T, E)) return -1;
+    if (!lc_launchable(bs, C, T, E)) return -2;
     if (!A || !pi || !stats || !loss || (bs > 0 && (!input || !target || !alpha || !seq))) return -3;
     hipStream_t st = (hipStream_t)stream;
     if (bs > 0) {
         const CrfPlan p = crf_plan(bs, C, T, E);
-        int rc;
-        if (C <= 8) rc = launch_crf_fwd<8>(p, input, bs, C, T, E, A, pi, target, ignore_index, alpha, seq, st);
-        else if (C <= 16) rc = launch_crf_fwd<16>(p, input, bs, C, T, E, A, pi, target, ignore_index, alpha, seq, st);
-        else if (C <= 32) rc = launch_crf_fwd<32>(p, input, bs, C, T, E, A, pi, target, ignore_index, alpha, seq, st);
-        else rc = launch_crf_fwd<64>(p, input, bs, C, T, E, A, pi, target, ignore_index, alpha, seq, st);
+        const int rc = lc_dispatch_classes(C, [&](auto cmax) {
+            return lc_launch<crf_fwd_kernel<decltype(cmax)::value>>(
+                p.g, bs, 2 * p.g.buf_floats * sizeof(float), stream, input, C, T, E, A, pi,
+                reinterpret_cast<const long long*>(target), (long long)ignore_index, alpha, seq, p.g.waves);
+        });
         if (rc) return rc;
     }
     hipLaunchKernelGGL(crf_final_kernel, dim3(1), dim3(CRF_FINAL_THREADS), 0, st, seq, (int64_t)bs * E, weight, stats, loss);
@@ -431,8 +364,8 @@ extern "C" int twog_crf_nll_bwd(const float* input, const int64_t* target, int b
                                 const double* stats, const float* dloss, float* dinput, int accumulate, float* partials,
                                 float* dA, float* dpi, int accumulate_params, void* stream) {
     const int C = n_classes;
-    if (!crf_shape_ok(bs, C, T, E)) return -1;
-    if (!crf_within_limits(bs, C, T, E)) return -2;
+    if (!lc_shape_ok(bs, C, T, E)) return -1;
+    if (!lc_launchable(bs, C, T, E)) return -2;
     if (!A || !stats || !dloss || (bs > 0 && (!input || !target || !alpha || !seq))) return -3;
     if ((dA == nullptr) != (dpi == nullptr) || (dA && bs > 0 && !partials)) return -3;
     if (!dinput && !dA) return 0;
@@ -440,15 +373,12 @@ extern "C" int twog_crf_nll_bwd(const float* input, const int64_t* target, int b
     if (bs > 0) {
         const CrfPlan p = crf_plan(bs, C, T, E);
         float* part = dA ? partials : nullptr;
-        int rc;
-        if (C <= 8)
-            rc = launch_crf_bwd<8>(p, input, bs, C, T, E, A, target, ignore_index, alpha, seq, stats, dloss, weight, dinput, accumulate, part, st);
-        else if (C <= 16)
-            rc = launch_crf_bwd<16>(p, input, bs, C, T, E, A, target, ignore_index, alpha, seq, stats, dloss, weight, dinput, accumulate, part, st);
-        else if (C <= 32)
-            rc = launch_crf_bwd<32>(p, input, bs, C, T, E, A, target, ignore_index, alpha, seq, stats, dloss, weight, dinput, accumulate, part, st);
-        else
-            rc = launch_crf_bwd<64>(p, input, bs, C, T, E, A, target, ignore_index, alpha, seq, stats, dloss, weight, dinput, accumulate, part, st);
+        const int rc = lc_dispatch_classes(C, [&](auto cmax) {
+            return lc_launch<crf_bwd_kernel<decltype(cmax)::value>>(
+                p.g, bs, (dinput ? 4 : 2) * p.g.buf_floats * sizeof(float), stream, input, C, T, E, A,
+                reinterpret_cast<const long long*>(target), (long long)ignore_index, alpha, seq, stats, dloss, weight, dinput,
+                accumulate, part, p.g.waves);
+        });
         if (rc) return rc;
     }
     if (dA) {

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void loss_partial_kernel(const Terms T, double
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
         if (L.kind == 0) {
             const int64_t tgt = reinterpret_cast<const int64_t*>(L.target)[e];
-            if (tgt != (int64_t)L.ignore_value && tgt >= 0 && tgt < L.n_classes) {
+            if (twog_label_kept(tgt, (int64_t)L.ignore_value, L.n_classes)) {
                 const int64_t o = e / L.inner, i = e - o * L.inner;
                 sum -= (double)L.input[(o * L.n_classes + tgt) * L.inner + i];
                 cnt += 1.0;
@@ -57,7 +57,8 @@ __global__ __launch_bounds__(256) void loss_partial_kernel(const Terms T, double
 // One thread per term adds the term's block partials in block order: {sum, count} (weighted criterion: {sum, kept weight})
 // into stats, weight * mean into losses. Shared by loss_final_kernel and wloss_final_kernel (TermT = twog_loss_t / twog_wloss_t);
 // it holds no multiply that feeds an add, so it reads the same on either side of the contraction pragma below.
-template <class TermT>
+// SOFT_ONLY (smooth_final_kernel, whose terms have no kind): every term takes the branch of the BCE / budget terms.
+template <bool SOFT_ONLY = false, class TermT>
 __device__ __forceinline__ void final_body(const TermT* terms, int n_terms, int n_blocks, const double* partials, double* stats,
                                            float* losses) {
     const int term = blockIdx.x * blockDim.x + threadIdx.x;
@@ -70,9 +71,10 @@ __device__ __forceinline__ void final_body(const TermT* terms, int n_terms, int 
     stats[term * 2] = sum;
     stats[term * 2 + 1] = cnt;
     const TermT& L = terms[term];
-    double v;
-    if (L.kind == 0) v = sum / cnt;  // 0 / 0 -> NaN like torch's mean over an empty selection (F.nll_loss(weight=): no kept weight)
-    else v = cnt > 0.0 ? sum / cnt : 0.0;
+    bool soft = true;
+    if constexpr (!SOFT_ONLY) soft = L.kind != 0;
+    // NLL: 0 / 0 -> NaN like torch's mean over an empty selection (F.nll_loss(weight=): no kept weight)
+    const double v = soft ? (cnt > 0.0 ? sum / cnt : 0.0) : sum / cnt;
     losses[term] = L.weight * (float)v;
 }
 
@@ -90,7 +92,7 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const Terms T, const doub
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
         if (L.kind == 0) {
             const int64_t tgt = reinterpret_cast<const int64_t*>(L.target)[e];
-            const bool valid = tgt != (int64_t)L.ignore_value && tgt >= 0 && tgt < L.n_classes;
+            const bool valid = twog_label_kept(tgt, (int64_t)L.ignore_value, L.n_classes);
             const int64_t o = e / L.inner, i = e - o * L.inner;
             float* d = L.dinput + o * L.n_classes * L.inner + i;
             for (int c = 0; c < L.n_classes; ++c) d[(int64_t)c * L.inner] = (valid && c == tgt) ? -g : 0.f;
@@ -110,7 +112,8 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const Terms T, const doub
     }
 }
 
-inline bool terms_ok(const twog_loss_t* t, int n) {
+template <class TermT>   // twog_loss_t, and the part of twog_wloss_t it shares
+inline bool terms_ok(const TermT* t, int n) {
     if (n < 0 || n > TWOG_LOSS_MAX_TERMS) return false;
     for (int i = 0; i < n; ++i) {
         if (t[i].kind < 0 || t[i].kind > 2 || t[i].outer < 0 || t[i].inner < 0) return false;
@@ -130,7 +133,7 @@ inline bool terms_ok(const twog_loss_t* t, int n) {
 struct SmoothTerms { twog_smooth_loss_t t[TWOG_LOSS_MAX_TERMS]; };
 
 __device__ __forceinline__ bool smooth_step_kept(const twog_smooth_loss_t& L, int64_t y) {
-    return y != (int64_t)L.ignore_value && y >= 0 && y < L.n_classes;
+    return twog_label_kept(y, (int64_t)L.ignore_value, L.n_classes);
 }
 
 __global__ __launch_bounds__(256) void smooth_partial_kernel(const SmoothTerms T, double* partials) {
@@ -154,16 +157,7 @@ __global__ __launch_bounds__(256) void smooth_partial_kernel(const SmoothTerms T
 
 __global__ void smooth_final_kernel(const SmoothTerms T, int n_terms, int n_blocks, const double* partials, double* stats,
                                     float* losses) {
-    const int term = blockIdx.x * blockDim.x + threadIdx.x;
-    if (term >= n_terms) return;
-    double sum = 0.0, cnt = 0.0;
-    for (int b = 0; b < n_blocks; ++b) {
-        sum += partials[((int64_t)term * n_blocks + b) * 2];
-        cnt += partials[((int64_t)term * n_blocks + b) * 2 + 1];
-    }
-    stats[term * 2] = sum;
-    stats[term * 2 + 1] = cnt;
-    losses[term] = T.t[term].weight * (float)(cnt > 0.0 ? sum / cnt : 0.0);
+    final_body<true>(T.t, n_terms, n_blocks, partials, stats, losses);
 }
 
 __global__ __launch_bounds__(256) void smooth_bwd_kernel(const SmoothTerms T, const double* stats, const float* dlosses) {
@@ -217,7 +211,7 @@ __global__ __launch_bounds__(256) void wloss_partial_kernel(const WTerms T, doub
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
         if (L.kind == 0) {
             const int64_t tgt = reinterpret_cast<const int64_t*>(L.target)[e];
-            if (tgt != (int64_t)L.ignore_value && tgt >= 0 && tgt < L.n_classes) {
+            if (twog_label_kept(tgt, (int64_t)L.ignore_value, L.n_classes)) {
                 const int64_t o = e / L.inner, i = e - o * L.inner;
                 const double cw = L.class_weight ? (double)L.class_weight[tgt] : 1.0;
                 sum += cw * (double)(-L.input[(o * L.n_classes + tgt) * L.inner + i]);
@@ -253,7 +247,7 @@ __global__ __launch_bounds__(256) void wloss_bwd_kernel(const WTerms T, const do
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
         if (L.kind == 0) {
             const int64_t tgt = reinterpret_cast<const int64_t*>(L.target)[e];
-            const bool valid = tgt != (int64_t)L.ignore_value && tgt >= 0 && tgt < L.n_classes;
+            const bool valid = twog_label_kept(tgt, (int64_t)L.ignore_value, L.n_classes);
             const int64_t o = e / L.inner, i = e - o * L.inner;
             float v = 0.f;
             if (valid) v = L.class_weight ? -(g * L.class_weight[tgt]) : -g;
@@ -277,12 +271,9 @@ __global__ __launch_bounds__(256) void wloss_bwd_kernel(const WTerms T, const do
 }
 
 inline bool wterms_ok(const twog_wloss_t* t, int n) {
-    if (n < 0 || n > TWOG_LOSS_MAX_TERMS) return false;
-    for (int i = 0; i < n; ++i) {
-        if (t[i].kind < 0 || t[i].kind > 2 || t[i].outer < 0 || t[i].inner < 0) return false;
-        if (t[i].kind == 0 && t[i].n_classes < 1) return false;
+    if (!terms_ok(t, n)) return false;
+    for (int i = 0; i < n; ++i)
         if (!(t[i].positive_class_weight >= 0.f) || !(t[i].positive_class_weight <= 3.402823466e38f)) return false;
-    }
     return true;
 }
 

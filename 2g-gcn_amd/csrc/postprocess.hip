@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void confusion_counts_kernel(const long long* 
     flush_hist(hist, C, counts, flags);
 }
 
-// Class counts of a label tensor under the NLL term's rule (label != ignore && 0 <= label < C), for losses.class_counts:
+// Class counts of a label tensor under the NLL terms' rule (twog_label_kept), for losses.class_counts:
 // hist[C] 32-bit counters per workgroup (a workgroup sees far fewer than 2^32 positions), flushed like the cells above.
 __global__ __launch_bounds__(256) void class_counts_kernel(const long long* targets, int64_t n, int C, long long ignore,
                                                            long long* counts) {
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void class_counts_kernel(const long long* targ
     __syncthreads();
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const long long y = targets[i];
-        if (y != ignore && y >= 0 && y < C) atomicAdd(&hist[(int)y], 1u);
+        if (twog_label_kept(y, ignore, C)) atomicAdd(&hist[(int)y], 1u);
     }
     __syncthreads();
     for (int k = threadIdx.x; k < C; k += 256) {

@@ -134,4 +134,10 @@ __device__ __forceinline__ float lane_value(float v, int lane) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 
+// The NLL terms' rule: a label takes part when it is not the ignore value and names a class. The criterion, the smoothing
+// and CRF losses and the count kernels all keep or drop a label by this one test.
+__device__ __forceinline__ bool twog_label_kept(int64_t y, int64_t ignore, int n_classes) {
+    return y != ignore && y >= 0 && y < n_classes;
+}
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }

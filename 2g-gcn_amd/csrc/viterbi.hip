@@ -2,55 +2,43 @@
 // (DESIGN section 4.14). The reference project decodes with a per-step argmax only; the definition is the numpy
 // specification tests/viterbi_ref.py, restated at twog_viterbi_decode in include/twog_gcn.h.
 //
-// Shape of the decode kernel. The recurrence is serial in t and parallel in c: one wave per sequence (clip b, entity e),
-// lane c owns class c. The column A[:, c] lives in registers; d[t-1][c'] is taken from lane c' by v_readlane (a constant
-// lane per unrolled iteration), so a step needs no LDS exchange and no barrier. A workgroup is one clip and up to
-// VIT_MAX_WAVES neighbouring entities: together its waves stage time chunks of the clip's (C, chunk, E) slab into LDS,
-// so that the E floats of a step that sit side by side in memory are fetched once, and the loads of chunk n + 1 are in
-// flight (in registers) while chunk n is consumed. Back-pointers are one byte per (t, c), four steps packed into the
-// 32-bit word of lane c; the words sit in LDS when the whole sequence fits beside the staging buffers and in the
-// caller's workspace otherwise. The backtrace reads a word with the lane that wrote it and follows the path with
-// v_readlane, so the only dependent chain is scalar.
+// The decode kernel has the shape of label_chain.h (one wave per sequence, lane c owns class c, the slab staged in chunks).
+// The column A[:, c] lives in registers; d[t-1][c'] is taken from lane c' by v_readlane (a constant lane per unrolled
+// iteration), so a step needs no LDS exchange and no barrier. Back-pointers are one byte per (t, c), four steps packed into
+// the 32-bit word of lane c; the words sit in LDS when the whole sequence fits beside the staging buffers and in the caller's
+// workspace otherwise. The backtrace reads a word with the lane that wrote it and follows the path with v_readlane, so the
+// only dependent chain is scalar.
 //
 // All arithmetic is one fp32 add per operation in the order of the specification, comparisons are strict, and nothing
 // depends on the launch geometry: the same sequence gives the same bits in any batch.
 #include "twog_common.h"
+#include "label_chain.h"
 
 namespace {
 
-constexpr int VIT_MAX_CLASSES = 64;     // one wave: lane c owns class c (EVAL_MAX_CLASSES of postprocess.hip)
-constexpr int VIT_MAX_STEPS = 4096;     // SEGF1_MAX_STEPS of postprocess.hip: what the segment metrics take
-constexpr int VIT_CHUNK = TWOG_VITERBI_CHUNK;
-constexpr int VIT_MAX_WAVES = 8;        // entities of one clip per workgroup
-constexpr size_t VIT_LDS_LIMIT = 160 * 1024;
-
 struct VitPlan {
-    int waves;            // entities per workgroup
-    int groups;           // workgroups per clip
+    LcGeometry g;
     int route;            // TWOG_VITERBI_ROUTE_*
-    size_t stage_bytes;   // the two staging buffers
     size_t lds_bytes;     // dynamic LDS of the launch
     int64_t seq_words;    // back-pointer words of one sequence
     size_t ws_bytes;      // caller's workspace (0 on the LDS route)
 };
 
-// The one statement of the launch geometry and of the route: twog_viterbi_workspace reports it, the launcher uses it.
+// The one statement of the route: twog_viterbi_workspace reports it, the launcher uses it.
 inline VitPlan vit_plan(int bs, int C, int T, int E) {
     VitPlan p;
-    p.waves = E < VIT_MAX_WAVES ? E : VIT_MAX_WAVES;
-    p.groups = (E + p.waves - 1) / p.waves;
-    const int row = VIT_CHUNK * p.waves + 1;                       // odd row stride: lanes c hit different banks
-    p.stage_bytes = (size_t)2 * C * row * sizeof(float);
+    p.g = lc_geometry(C, E, LC_MAX_WAVES);
+    const size_t stage_bytes = 2 * p.g.buf_floats * sizeof(float);
     const int64_t words = (int64_t)((T + 3) / 4) * C;
-    const size_t with_bp = p.stage_bytes + (size_t)p.waves * words * 4;
-    if (with_bp <= VIT_LDS_LIMIT) {
+    const size_t with_bp = stage_bytes + (size_t)p.g.waves * words * 4;
+    if (with_bp <= LC_LDS_LIMIT) {
         p.route = TWOG_VITERBI_ROUTE_LDS;
         p.lds_bytes = with_bp;
         p.seq_words = words;
         p.ws_bytes = 0;
     } else {
         p.route = TWOG_VITERBI_ROUTE_WORKSPACE;
-        p.lds_bytes = p.stage_bytes;
+        p.lds_bytes = stage_bytes;
         p.seq_words = (words + 63) / 64 * 64;                      // whole 256-byte pieces: no line is shared by two waves
         p.ws_bytes = (size_t)bs * E * p.seq_words * 4;
     }
@@ -83,18 +71,18 @@ __device__ __forceinline__ void best_predecessor(float d, const float (&a)[CMAX]
 }
 
 // grid (groups, bs), 64 * EW threads: wave w decodes entity blockIdx.x * EW + w of clip blockIdx.y.
-// LDS: stage[2][C][VIT_CHUNK * EW + 1] floats, then on the LDS route EW * seq_words back-pointer words.
+// LDS: stage[2][C][lc_row(EW)] floats, then on the LDS route EW * seq_words back-pointer words.
 template <int CMAX>
-__global__ __launch_bounds__(64 * VIT_MAX_WAVES) void viterbi_kernel(
+__global__ __launch_bounds__(64 * LC_MAX_WAVES) void viterbi_kernel(
     const float* __restrict__ logp, int C, int T, int E, const float* __restrict__ A, const float* __restrict__ pi,
     const long long* __restrict__ lengths, int ds, int T_out, long long* __restrict__ labels, float* __restrict__ score,
     unsigned* __restrict__ ws, long long seq_words, int EW, int bp_in_lds) {
     extern __shared__ float smem[];
-    constexpr int R = CMAX / 4;                       // staged elements per thread and chunk: C * VIT_CHUNK * EW / (64 * EW)
+    constexpr int R = CMAX / 4;                       // staged elements per thread and chunk: C * LC_CHUNK * EW / (64 * EW)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nthreads = 64 * EW;
     const int b = blockIdx.y, e0 = blockIdx.x * EW, e = e0 + w;
     const bool decodes = e < E;                       // wave-uniform; a wave without an entity still stages
-    const int row = VIT_CHUNK * EW + 1, per_class = VIT_CHUNK * EW;
+    const int row = lc_row(EW), per_class = LC_CHUNK * EW;
     float* stage = smem;
     unsigned* bpw = bp_in_lds ? reinterpret_cast<unsigned*>(smem + 2 * C * row) + (int64_t)w * seq_words
                               : ws + ((int64_t)b * E + (decodes ? e : 0)) * seq_words;
@@ -112,8 +100,10 @@ __global__ __launch_bounds__(64 * VIT_MAX_WAVES) void viterbi_kernel(
         return;
     }
 
-    // what this thread stages of every chunk: element k * nthreads + tid of the (C, chunk, EW) slab. goff: its offset from
-    // logp[b][0][t0][e0] (-1: nothing), soff: its place in a staging buffer, tt: its step within the chunk
+    // What this thread stages of every chunk: element k * nthreads + tid of the (C, chunk, EW) slab. goff: its offset from
+    // logp[b][0][t0][e0] (-1: nothing), soff: its place in a staging buffer, tt: its step within the chunk. The mapping is
+    // LcStager's (label_chain.h); the decode keeps it as arrays and its own loops because its 64-class instance measured 1 %
+    // slower on the stager's members.
     int goff[R], soff[R], tt_of[R];
 #pragma unroll
     for (int k = 0; k < R; ++k) {
@@ -148,16 +138,16 @@ __global__ __launch_bounds__(64 * VIT_MAX_WAVES) void viterbi_kernel(
 
     float d = NEG_INF;
     unsigned pack = 0u;
-    const int n_chunks = (L + VIT_CHUNK - 1) / VIT_CHUNK;
+    const int n_chunks = (L + LC_CHUNK - 1) / LC_CHUNK;
     fetch(0);
     for (int ch = 0; ch < n_chunks; ++ch) {
-        const int buf = ch & 1, t0 = ch * VIT_CHUNK;
+        const int buf = ch & 1, t0 = ch * LC_CHUNK;
         commit(buf);          // buffer `buf` was last read in chunk ch - 2, which every wave left before the barrier of ch - 1
         __syncthreads();
-        if (ch + 1 < n_chunks) fetch(t0 + VIT_CHUNK);   // in flight while this chunk is consumed
+        if (ch + 1 < n_chunks) fetch(t0 + LC_CHUNK);   // in flight while this chunk is consumed
         if (!decodes) continue;
         const float* mine = stage + buf * C * row + my_row;
-        const int n_here = L - t0 < VIT_CHUNK ? L - t0 : VIT_CHUNK;
+        const int n_here = L - t0 < LC_CHUNK ? L - t0 : LC_CHUNK;
         float x = mine[0];
         for (int tt = 0; tt < n_here; ++tt) {
             const int t = t0 + tt;
@@ -245,7 +235,7 @@ __global__ __launch_bounds__(256) void transition_counts_kernel(const long long*
         const int64_t b = bk / n_pairs;
         const long long from = targets[(b * T_tgt + (int64_t)k * stride) * E + e];
         const long long to = targets[(b * T_tgt + (int64_t)(k + 1) * stride) * E + e];
-        if (from != ignore && to != ignore && from >= 0 && from < C && to >= 0 && to < C)
+        if (twog_label_kept(from, ignore, C) && twog_label_kept(to, ignore, C))
             atomicAdd(&hist[(int)from * C + (int)to], 1u);
     }
     __syncthreads();
@@ -255,30 +245,17 @@ __global__ __launch_bounds__(256) void transition_counts_kernel(const long long*
     }
 }
 
-template <int CMAX>
-int launch_viterbi(const VitPlan& p, const float* logp, int bs, int C, int T, int E, const float* A, const float* pi,
-                   const int64_t* lengths, int ds, int T_out, int64_t* labels, float* score, void* ws, void* stream) {
-    static std::atomic<uint32_t> lds_attr_done{0};
-    twog_allow_dynamic_lds(viterbi_kernel<CMAX>, (int)VIT_LDS_LIMIT, lds_attr_done);
-    hipLaunchKernelGGL(viterbi_kernel<CMAX>, dim3(p.groups, bs), dim3(64 * p.waves), p.lds_bytes, (hipStream_t)stream,
-                       logp, C, T, E, A, pi, reinterpret_cast<const long long*>(lengths), ds, T_out,
-                       reinterpret_cast<long long*>(labels), score, reinterpret_cast<unsigned*>(ws), (long long)p.seq_words,
-                       p.waves, p.route == TWOG_VITERBI_ROUTE_LDS ? 1 : 0);
-    TWOG_CHECK_LAUNCH();
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int twog_viterbi_limits(int* max_classes, int* max_steps) {
-    if (max_classes) *max_classes = VIT_MAX_CLASSES;
-    if (max_steps) *max_steps = VIT_MAX_STEPS;
+    if (max_classes) *max_classes = LC_MAX_CLASSES;
+    if (max_steps) *max_steps = LC_MAX_STEPS;
     return 0;
 }
 
 extern "C" int twog_viterbi_workspace(int bs, int n_classes, int T, int E, size_t* bytes) {
-    if (bs < 0 || n_classes < 1 || T < 1 || E < 1) return -1;
-    if (n_classes > VIT_MAX_CLASSES || T > VIT_MAX_STEPS) return -2;
+    if (!lc_shape_ok(bs, n_classes, T, E)) return -1;
+    if (!lc_within_limits(n_classes, T)) return -2;
     const VitPlan p = vit_plan(bs, n_classes, T, E);
     if (bytes) *bytes = p.ws_bytes;
     return p.route;
@@ -287,25 +264,23 @@ extern "C" int twog_viterbi_workspace(int bs, int n_classes, int T, int E, size_
 extern "C" int twog_viterbi_decode(const float* logp, int bs, int n_classes, int T, int E, const float* A, const float* pi,
                                    const int64_t* lengths, int downsampling, int T_out, int64_t* labels, float* score,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-    if (bs < 0 || n_classes < 1 || T < 1 || E < 1 || downsampling < 1 || T_out < 0) return -1;
-    if (n_classes > VIT_MAX_CLASSES || T > VIT_MAX_STEPS) return -2;
-    if ((int64_t)n_classes * T * E > INT32_MAX || bs > 65535) return -2;
+    if (!lc_shape_ok(bs, n_classes, T, E) || downsampling < 1 || T_out < 0) return -1;
+    if (!lc_launchable(bs, n_classes, T, E)) return -2;
     if (bs == 0) return 0;
     const VitPlan p = vit_plan(bs, n_classes, T, E);
     if (p.route == TWOG_VITERBI_ROUTE_WORKSPACE && (workspace == nullptr || workspace_bytes < p.ws_bytes)) return -3;
-    if (n_classes <= 8)
-        return launch_viterbi<8>(p, logp, bs, n_classes, T, E, A, pi, lengths, downsampling, T_out, labels, score, workspace, stream);
-    if (n_classes <= 16)
-        return launch_viterbi<16>(p, logp, bs, n_classes, T, E, A, pi, lengths, downsampling, T_out, labels, score, workspace, stream);
-    if (n_classes <= 32)
-        return launch_viterbi<32>(p, logp, bs, n_classes, T, E, A, pi, lengths, downsampling, T_out, labels, score, workspace, stream);
-    return launch_viterbi<64>(p, logp, bs, n_classes, T, E, A, pi, lengths, downsampling, T_out, labels, score, workspace, stream);
+    return lc_dispatch_classes(n_classes, [&](auto cmax) {
+        return lc_launch<viterbi_kernel<decltype(cmax)::value>>(
+            p.g, bs, p.lds_bytes, stream, logp, n_classes, T, E, A, pi, reinterpret_cast<const long long*>(lengths), downsampling,
+            T_out, reinterpret_cast<long long*>(labels), score, reinterpret_cast<unsigned*>(workspace), (long long)p.seq_words,
+            p.g.waves, p.route == TWOG_VITERBI_ROUTE_LDS ? 1 : 0);
+    });
 }
 
 extern "C" int twog_transition_counts(const int64_t* targets, int bs, int T_tgt, int E, int n_classes, int stride,
                                       int64_t ignore_index, int64_t* counts, void* stream) {
     if (bs < 0 || T_tgt < 0 || E < 1 || n_classes < 1 || stride < 1) return -1;
-    if (n_classes > VIT_MAX_CLASSES) return -2;
+    if (n_classes > LC_MAX_CLASSES) return -2;
     const int n_pairs = T_tgt > 0 ? (T_tgt - 1) / stride : 0;
     const int64_t n = (int64_t)bs * n_pairs * E;
     if (n == 0) return 0;

@@ -1524,49 +1524,51 @@ class HipKernels:
             a.weight, a.ignore_value = float(t['weight']), float(t['ignore'])
         return arr
 
+    def _criterion_fwd(self, entry, struct, terms, room):
+        n, dev = len(terms), terms[0]['input'].device
+        if n > L.LOSS_MAX_TERMS:
+            raise ValueError(f'at most {L.LOSS_MAX_TERMS} loss terms per call')
+        losses = torch.empty(n + room, dtype=torch.float32, device=dev)
+        stats = torch.empty(n + room, 2, dtype=torch.float64, device=dev)
+        partials = self.workspace(n * L.LOSS_BLOCKS * 2 * 8, dev, 'loss')
+        self._check(getattr(self.lib, entry)(self._loss_terms(terms, struct=struct), n, partials.data_ptr(), stats.data_ptr(),
+                                             losses.data_ptr(), self._stream()), entry)
+        return losses, stats
+
+    def _criterion_bwd(self, entry, struct, terms, stats, dlosses, need):
+        dins = [torch.empty_like(t['input']) if nd else None for t, nd in zip(terms, need)]
+        self._check(getattr(self.lib, entry)(self._loss_terms(terms, dins, struct=struct), len(terms), stats.data_ptr(),
+                                             dlosses.contiguous().data_ptr(), self._stream()), entry)
+        return dins
+
     def multitask_loss_fwd(self, terms, room=0):
         """All loss terms in one launch. Returns (losses [n + room] fp32, stats [n + room][2] fp64 = sum, count): the first n
         rows are written here, the `room` rows behind them are left to smooth_loss_fwd, so the criterion's losses stay ONE
         tensor (multi_task._loss_tensor reads it in place) without a copy."""
-        n, dev = len(terms), terms[0]['input'].device
-        if n > L.LOSS_MAX_TERMS:
-            raise ValueError(f'at most {L.LOSS_MAX_TERMS} loss terms per call')
-        losses = torch.empty(n + room, dtype=torch.float32, device=dev)
-        stats = torch.empty(n + room, 2, dtype=torch.float64, device=dev)
-        partials = self.workspace(n * L.LOSS_BLOCKS * 2 * 8, dev, 'loss')
-        self._check(self.lib.twog_multitask_loss_fwd(self._loss_terms(terms), n, partials.data_ptr(), stats.data_ptr(),
-                                                     losses.data_ptr(), self._stream()), 'twog_multitask_loss_fwd')
-        return losses, stats
+        return self._criterion_fwd('twog_multitask_loss_fwd', L.Loss, terms, room)
 
     def multitask_loss_bwd(self, terms, stats, dlosses, need):
         """d(input) of every term with need[i] (others None), scaled by the upstream gradient dlosses [n]."""
-        dins = [torch.empty_like(t['input']) if nd else None for t, nd in zip(terms, need)]
-        self._check(self.lib.twog_multitask_loss_bwd(self._loss_terms(terms, dins), len(terms), stats.data_ptr(),
-                                                     dlosses.contiguous().data_ptr(), self._stream()),
-                    'twog_multitask_loss_bwd')
-        return dins
+        return self._criterion_bwd('twog_multitask_loss_bwd', L.Loss, terms, stats, dlosses, need)
 
     def weighted_loss_fwd(self, terms, room=0):
         """multitask_loss_fwd for terms that may carry `class_weight` (NLL) and `positive_class_weight` (BCE), through
         twog_weighted_loss_fwd: same returns, stats = (sum, den) with den the sum of the kept class weights of an NLL term."""
-        n, dev = len(terms), terms[0]['input'].device
-        if n > L.LOSS_MAX_TERMS:
-            raise ValueError(f'at most {L.LOSS_MAX_TERMS} loss terms per call')
-        losses = torch.empty(n + room, dtype=torch.float32, device=dev)
-        stats = torch.empty(n + room, 2, dtype=torch.float64, device=dev)
-        partials = self.workspace(n * L.LOSS_BLOCKS * 2 * 8, dev, 'loss')
-        self._check(self.lib.twog_weighted_loss_fwd(self._loss_terms(terms, struct=L.WLoss), n, partials.data_ptr(),
-                                                    stats.data_ptr(), losses.data_ptr(), self._stream()),
-                    'twog_weighted_loss_fwd')
-        return losses, stats
+        return self._criterion_fwd('twog_weighted_loss_fwd', L.WLoss, terms, room)
 
     def weighted_loss_bwd(self, terms, stats, dlosses, need):
         """multitask_loss_bwd for the terms of weighted_loss_fwd."""
-        dins = [torch.empty_like(t['input']) if nd else None for t, nd in zip(terms, need)]
-        self._check(self.lib.twog_weighted_loss_bwd(self._loss_terms(terms, dins, struct=L.WLoss), len(terms),
-                                                    stats.data_ptr(), dlosses.contiguous().data_ptr(), self._stream()),
-                    'twog_weighted_loss_bwd')
-        return dins
+        return self._criterion_bwd('twog_weighted_loss_bwd', L.WLoss, terms, stats, dlosses, need)
+
+    @staticmethod
+    def _check_tail(m, losses, stats, dins=None, shared=None):
+        """The views of a tail family of m terms: losses (or dlosses) [m] fp32 and stats [m][2] fp64, contiguous; and no two
+        of its gradient buffers `dins` the same (`shared`: the assertion text)."""
+        assert losses.shape == (m,) and losses.dtype == torch.float32 and losses.is_contiguous()
+        assert stats.shape == (m, 2) and stats.dtype == torch.float64 and stats.is_contiguous()
+        if dins is not None:
+            ptrs = [d.data_ptr() for d in dins if d is not None]
+            assert len(set(ptrs)) == len(ptrs), shared
 
     def _smooth_terms(self, terms, dinputs=None, accumulate=None):
         """terms: list of dict(input (outer, C, T, E) log-probabilities, target int64 (outer, T, E), weight, tau, ignore)."""
@@ -1591,8 +1593,7 @@ class HipKernels:
         """The temporal smoothing terms (twog_smooth_loss_t) in one launch pair, written into the given views: losses_out
         [m] fp32 and stats_out [m][2] fp64, the tail of the tensors multitask_loss_fwd(..., room=m) returned."""
         m, dev = len(terms), terms[0]['input'].device
-        assert losses_out.shape == (m,) and losses_out.dtype == torch.float32 and losses_out.is_contiguous()
-        assert stats_out.shape == (m, 2) and stats_out.dtype == torch.float64 and stats_out.is_contiguous()
+        self._check_tail(m, losses_out, stats_out)
         assert losses_out.device == dev and stats_out.device == dev
         partials = self.workspace(m * L.LOSS_BLOCKS * 2 * 8, dev, 'smooth_loss')
         self._check(self.lib.twog_smooth_loss_fwd(self._smooth_terms(terms), m, partials.data_ptr(), stats_out.data_ptr(),
@@ -1602,10 +1603,7 @@ class HipKernels:
         """d(input) of every smoothing term with a buffer in dins (None: skipped), scaled by dlosses [m]: stored into dins[i]
         (every element), or with accumulate[i] added where it is not zero. No two terms may share a buffer."""
         m = len(terms)
-        assert stats.shape == (m, 2) and stats.dtype == torch.float64 and stats.is_contiguous()
-        assert dlosses.shape == (m,) and dlosses.dtype == torch.float32 and dlosses.is_contiguous()
-        ptrs = [d.data_ptr() for d in dins if d is not None]
-        assert len(set(ptrs)) == len(ptrs), 'two smoothing terms of one launch share a gradient buffer'
+        self._check_tail(m, dlosses, stats, dins, 'two smoothing terms of one launch share a gradient buffer')
         self._check(self.lib.twog_smooth_loss_bwd(self._smooth_terms(terms, dins, accumulate), m, stats.data_ptr(),
                                                   dlosses.data_ptr(), self._stream()), 'twog_smooth_loss_bwd')
 
@@ -1643,8 +1641,7 @@ class HipKernels:
         seq (bs * E, 4) fp32 holds logZ, gold, nll_seq and K (the bits of an int32) per sequence."""
         m = len(terms)
         shapes = [self._crf_term(t) for t in terms]   # every refusal before the first launch
-        assert losses_out.shape == (m,) and losses_out.dtype == torch.float32 and losses_out.is_contiguous()
-        assert stats_out.shape == (m, 2) and stats_out.dtype == torch.float64 and stats_out.is_contiguous()
+        self._check_tail(m, losses_out, stats_out)
         for j, (t, (bs, Cn, T, E)) in enumerate(zip(terms, shapes)):
             x = t['input']
             assert losses_out.device == x.device and stats_out.device == x.device
@@ -1664,10 +1661,7 @@ class HipKernels:
         (every element), or with accumulate[j] added to it; dins[j] None: not asked for. need_params[j]: also (dA, dpi) of
         the term, new tensors. Returns the list of (dA, dpi) or None per term. A term that asks for neither is skipped."""
         m = len(terms)
-        assert stats.shape == (m, 2) and stats.dtype == torch.float64 and stats.is_contiguous()
-        assert dlosses.shape == (m,) and dlosses.dtype == torch.float32 and dlosses.is_contiguous()
-        ptrs = [d.data_ptr() for d in dins if d is not None]
-        assert len(set(ptrs)) == len(ptrs), 'two CRF terms share a gradient buffer'
+        self._check_tail(m, dlosses, stats, dins, 'two CRF terms share a gradient buffer')
         out = []
         for j, t in enumerate(terms):
             d, want = dins[j], bool(need_params[j])

@@ -24,6 +24,7 @@ emissions and the (C, C) scores jointly; the scores then go to `postprocess.Vite
 follow the smoothing terms in the same loss tensor, one launch pair per term and direction (`twog_crf_nll_fwd/bwd`;
 definition in include/twog_gcn.h and at `crf_loss`); off by default.
 """
+from collections import namedtuple
 from functools import partial
 
 import torch
@@ -186,103 +187,119 @@ def get_count_reducer():
     return _count_reducer
 
 
+# What _run hands to _MultiTaskLoss beside the tensors. smoothing: [(index, weight, tau)], crf: [(index, weight)], options: None
+# or ([class weight], [positive-class weight]) per term.
+_Spec = namedtuple('_Spec', 'kinds targets weights ignore reducer smoothing options crf')
+
+
+class _Tail:
+    """One family of terms that follow the zipped ones in the loss tensor (the smoothing terms, the CRF terms). They take their
+    inputs by index: index[j] is the zipped term whose input and gradient buffer term j shares. `name` gives the two launchers
+    of the kernel layer, name_fwd and name_bwd; a term of the family owns n_params parameter tensors (CRF: A and pi)."""
+
+    def __init__(self, name, index, terms, n_params=0):
+        self.name, self.index, self.terms, self.n_params = name, index, terms, n_params
+
+    def fwd(self, K, losses, stats):
+        """Writes the family's part of the tail (views of the loss and stats tensors) in place."""
+        getattr(K, self.name + '_fwd')(self.terms, losses, stats)
+
+    def bwd(self, K, stats, dlosses, dins, accumulate, need_params):
+        """Stores d(input) into dins[j] or adds to it; per term, the gradients of its parameter tensors or None."""
+        launch = getattr(K, self.name + '_bwd')
+        if self.n_params:
+            return launch(self.terms, stats, dlosses, dins, accumulate, need_params)
+        launch(self.terms, stats, dlosses, dins, accumulate)
+        return [None] * len(self.terms)
+
+
 class _MultiTaskLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec, *inputs):
-        kinds, targets, weights, ignore, reducer, smoothing, options, crf = spec
+        kinds, ignore = spec.kinds, spec.ignore
         # behind the n inputs: (transitions, initial) of every CRF term, so that autograd hands their gradients to the modules
         inputs, crf_params = inputs[:len(kinds)], inputs[len(kinds):]
         K = get_kernels()
         terms = []
-        for x, y, k, w in zip(inputs, targets, kinds, weights):
+        for x, y, k, w in zip(inputs, spec.targets, kinds, spec.weights):
             x = x.detach().contiguous()
             y = (y.to(torch.int64) if k == _NLL else y.to(torch.float32)).contiguous()
             terms.append(dict(kind=k, input=x, target=y, weight=w, ignore=ignore))
         # class weights / a positive-class weight on ANY term: all terms of the call go through twog_weighted_loss_*, still
         # one launch per direction; none: the plain entry points, exactly as before (same launches, same bits)
-        ctx.weighted = options is not None
+        ctx.weighted = spec.options is not None
         if ctx.weighted:
-            for t, cw, p in zip(terms, *options):
+            for t, cw, p in zip(terms, *spec.options):
                 t['class_weight'], t['positive_class_weight'] = cw, p
         fwd = K.weighted_loss_fwd if ctx.weighted else K.multitask_loss_fwd
         smooth = [dict(input=terms[i]['input'], target=terms[i]['target'], weight=w, tau=tau, ignore=ignore)
-                  for i, w, tau in smoothing]
+                  for i, w, tau in spec.smoothing]
         chains = [dict(input=terms[i]['input'], target=terms[i]['target'], weight=w, ignore=ignore,
                        transitions=crf_params[2 * j].detach().contiguous(), initial=crf_params[2 * j + 1].detach().contiguous())
-                  for j, (i, w) in enumerate(crf)]
-        if smooth or chains:
-            # the smoothing terms, then the CRF terms, follow the n zipped ones in the same tensors: one more launch (pair)
-            # each writes its part of the tail in place
-            n, ns = len(terms), len(smooth)
-            losses, stats = fwd(terms, room=ns + len(chains))
-            if smooth:
-                K.smooth_loss_fwd(smooth, losses[n:n + ns], stats[n:n + ns])
-            if chains:
-                K.crf_nll_fwd(chains, losses[n + ns:], stats[n + ns:])
-        else:
-            losses, stats = fwd(terms)
-        if reducer is not None:
+                  for j, (i, w) in enumerate(spec.crf)]
+        # the smoothing terms, then the CRF terms, follow the n zipped ones in the same tensors: one more launch (pair) each
+        # writes its part of the tail in place
+        tails = []
+        if smooth:
+            tails.append(_Tail('smooth_loss', [i for i, _, _ in spec.smoothing], smooth))
+        if chains:
+            tails.append(_Tail('crf_nll', [i for i, _ in spec.crf], chains, n_params=2))
+        tail_terms = smooth + chains
+        losses, stats = fwd(terms, room=len(tail_terms)) if tail_terms else fwd(terms)
+        at = len(terms)
+        for f in tails:
+            f.fwd(K, losses[at:at + len(f.terms)], stats[at:at + len(f.terms)])
+            at += len(f.terms)
+        if spec.reducer is not None:
             # six to twelve scalars: sum_rank / (count_global / W) per term, 0 / 0 -> NaN for NLL like torch's mean over an
             # empty selection, 0 for the BCE / budget terms (pyrutils/torch/losses.py:15-16, :32-33). Same arithmetic as
             # loss_final_kernel (csrc/loss.hip): the fp64 quotient rounded to fp32, then the fp32 product with the weight
             # -- with a reducer that returns the counts unchanged (one rank) the losses are bit-identical to the plain path.
             # With class weights the column handed over is den, the sum of the kept weights: the global WEIGHTED mean.
-            eff = reducer(stats[:, 1].clone())
+            eff = spec.reducer(stats[:, 1].clone())
             val = stats[:, 0] / eff
-            soft = torch.tensor([k != _NLL for k in kinds] + [True] * (len(smooth) + len(chains)), device=val.device)
+            soft = torch.tensor([k != _NLL for k in kinds] + [True] * len(tail_terms), device=val.device)
             val = torch.where(soft & (eff <= 0), torch.zeros_like(val), val)
-            w = torch.tensor([float(x) for x in weights] + [t['weight'] for t in smooth + chains], dtype=torch.float32,
+            w = torch.tensor([float(x) for x in spec.weights] + [t['weight'] for t in tail_terms], dtype=torch.float32,
                              device=val.device)
             losses = w * val.to(torch.float32)
             stats = torch.stack([stats[:, 0], eff], 1).contiguous()
-        ctx.terms, ctx.stats = terms, stats
-        ctx.smooth, ctx.smooth_index = smooth, [i for i, _, _ in smoothing]
-        ctx.chains, ctx.chain_index = chains, [i for i, _ in crf]
+        ctx.terms, ctx.stats, ctx.tails = terms, stats, tails
         return losses
 
     @staticmethod
     def backward(ctx, dlosses):
-        need = [ctx.needs_input_grad[i + 1] and t['weight'] != 0 for i, t in enumerate(ctx.terms)]
-        need_smooth = [ctx.needs_input_grad[i + 1] and t['weight'] != 0 for i, t in zip(ctx.smooth_index, ctx.smooth)]
-        n, ns = len(ctx.terms), len(ctx.smooth)
-        # a CRF term asks for d(input) and for (dA, dpi) separately; weight 0 or nothing to differentiate: no backward work
-        need_chain_x = [ctx.needs_input_grad[i + 1] and t['weight'] != 0 for i, t in zip(ctx.chain_index, ctx.chains)]
-        need_chain_p = [(ctx.needs_input_grad[1 + n + 2 * j] or ctx.needs_input_grad[2 + n + 2 * j]) and t['weight'] != 0
-                        for j, t in enumerate(ctx.chains)]
-        no_params = (None,) * (2 * len(ctx.chains))
-        if not any(need) and not any(need_smooth) and not any(need_chain_x) and not any(need_chain_p):
-            return (None,) + tuple(None for _ in ctx.terms) + no_params
-        K = get_kernels()
-        bwd = K.weighted_loss_bwd if ctx.weighted else K.multitask_loss_bwd
-        dins = bwd(ctx.terms, ctx.stats, dlosses, need) if any(need) else [None] * n
-        if any(need_smooth):
-            # one gradient per input: the smoothing launch adds into the buffer the NLL launch just wrote on this stream, or
-            # stores into a buffer of its own where the NLL term of that input has no backward work
-            dins, sdins, acc = list(dins), [None] * len(ctx.smooth), [False] * len(ctx.smooth)
-            for j, (i, nd) in enumerate(zip(ctx.smooth_index, need_smooth)):
-                if nd:
-                    acc[j] = dins[i] is not None
-                    if not acc[j]:
-                        dins[i] = torch.empty_like(ctx.terms[i]['input'])
-                    sdins[j] = dins[i]
-            K.smooth_loss_bwd(ctx.smooth, ctx.stats[n:n + ns], dlosses.contiguous()[n:n + ns], sdins, acc)
-        if not any(need_chain_x) and not any(need_chain_p):
-            return (None,) + tuple(dins) + no_params
-        # the CRF launch adds into the buffer the NLL or smoothing launch of that input wrote on this stream, or stores into
-        # one of its own
-        dins, cdins, acc = list(dins), [None] * len(ctx.chains), [False] * len(ctx.chains)
-        for j, (i, nd) in enumerate(zip(ctx.chain_index, need_chain_x)):
-            if nd:
-                acc[j] = dins[i] is not None
-                if not acc[j]:
-                    dins[i] = torch.empty_like(ctx.terms[i]['input'])
-                cdins[j] = dins[i]
-        grads = K.crf_nll_bwd(ctx.chains, ctx.stats[n + ns:], dlosses.contiguous()[n + ns:], cdins, acc, need_chain_p)
-        params = []
-        for j, gr in enumerate(grads):
-            dA, dpi = gr if need_chain_p[j] else (None, None)
-            params += [dA if ctx.needs_input_grad[1 + n + 2 * j] else None, dpi if ctx.needs_input_grad[2 + n + 2 * j] else None]
-        return (None,) + tuple(dins) + tuple(params)
+        wanted, n, K = ctx.needs_input_grad, len(ctx.terms), get_kernels()
+        out = [None] * len(wanted)   # of spec, of the n inputs, then of the parameters of the tail terms in term order
+        # weight 0 or nothing to differentiate: no backward work
+        need = [wanted[i + 1] and t['weight'] != 0 for i, t in enumerate(ctx.terms)]
+        dins = [None] * n
+        if any(need):
+            dins = list((K.weighted_loss_bwd if ctx.weighted else K.multitask_loss_bwd)(ctx.terms, ctx.stats, dlosses, need))
+        at, p0 = n, 1 + n
+        for f in ctx.tails:
+            m = len(f.terms)
+            slots = [range(p0 + f.n_params * j, p0 + f.n_params * (j + 1)) for j in range(m)]
+            # a term asks for d(input) and for its parameters' gradients separately
+            need_x = [wanted[i + 1] and t['weight'] != 0 for i, t in zip(f.index, f.terms)]
+            need_p = [any(wanted[q] for q in s) and t['weight'] != 0 for s, t in zip(slots, f.terms)]
+            if any(need_x) or any(need_p):
+                # one gradient per input: the launch adds into the buffer an earlier launch (NLL, or a family before this one)
+                # wrote on this stream, or stores into a buffer of its own where none of them had backward work for that input
+                fdins, acc = [None] * m, [False] * m
+                for j, (i, nd) in enumerate(zip(f.index, need_x)):
+                    if nd:
+                        acc[j] = dins[i] is not None
+                        if not acc[j]:
+                            dins[i] = torch.empty_like(ctx.terms[i]['input'])
+                        fdins[j] = dins[i]
+                grads = f.bwd(K, ctx.stats[at:at + m], dlosses.contiguous()[at:at + m], fdins, acc, need_p)
+                for s, gr in zip(slots, grads):
+                    for q, g in zip(s, gr or ()):
+                        out[q] = g if wanted[q] else None
+            at, p0 = at + m, p0 + f.n_params * m
+        out[1:1 + n] = dins
+        return tuple(out)
 
 
 _uploaded_weights = {}   # (values, device) -> fp32 tensor: a host sequence of class weights is uploaded once per device
@@ -379,8 +396,8 @@ def _run(inputs, targets, kinds, weights, ignore_value, reduction, smoothing=(),
     crf_params = [p for m in modules for p in (m.transitions, m.initial)]
     # the scope's reducer, and only while autograd records (read here: grad mode is off inside Function.forward)
     reducer = _count_reducer if torch.is_grad_enabled() else None
-    losses = _MultiTaskLoss.apply((list(kinds), list(targets), [float(w) for w in weights], ignore_value, reducer,
-                                   smoothing, options, crf), *inputs, *crf_params)
+    losses = _MultiTaskLoss.apply(_Spec(list(kinds), list(targets), [float(w) for w in weights], ignore_value, reducer,
+                                        smoothing, options, crf), *inputs, *crf_params)
     return list(losses.unbind(0))
 
 

@@ -68,6 +68,17 @@ def test_two_runs_give_the_same_bits():
             assert np.array_equal(getattr(a, q).view(np.uint32), getattr(b, q).view(np.uint32)), (name, q)
 
 
+@pytest.mark.parametrize('name', ['small-bs3-C40-T18-E5-tail-softmax', 'small-bs1-C4-T35-E9-holes-softmax'])
+def test_a_rerun_is_byte_identical(name):
+    """Forward + backward twice where the shared staging does the most: a second workgroup per clip with idle waves (E = 5
+    beyond 32 classes, E = 9 below) and a last chunk that is not whole. Every output of the kernel layer, byte for byte."""
+    K = twog_kernels.get_kernels()
+    first, again = (run_kernel_layer(K, make(BY_NAME[name]), DEV) for _ in range(2))
+    assert first.loss == again.loss and first.count == again.count
+    for q in ('nll', 'logZ', 'gold', 'K', 'dinput', 'dA', 'dpi'):
+        assert getattr(first, q).tobytes() == getattr(again, q).tobytes(), q
+
+
 @pytest.mark.parametrize('name,b,e', [('small-bs3-C6-T20-E3-holes-softmax', 1, 2), ('small-bs3-C6-T20-E9-tail-softmax', 2, 8),
                                       ('small-bs3-C40-T18-E5-tail-softmax', 1, 4)])
 def test_a_sequence_alone_and_inside_a_batch(name, b, e):
