@@ -242,6 +242,28 @@ def bigru_persistent_plan(lib, Es, bs, h, n_cus=0):
                 bwd_served=bool(out[6]), n_cus=out[7], combos=combos)
 
 
+SEGRNN_PLAN_INTS = 16   # TWOG_SEGRNN_PLAN_INTS
+SEGRNN_PLAN_FIELDS = ('served', 'cpc', 'n_chunks', 'last', 'mh', 'mo', 'pair_mask', 'grid', 'lds_fwd', 'lds_bwd', 'x3q1', 'dw_pad',
+                      'sync_words')   # out[0 .. 12]
+
+
+def segrnn_persistent_plan(lib, bs, T, H, O, h, n_cus=0, msg_segment=True, rels=(True, True, True, True)):
+    """twog_segrnn_persistent_plan of the loaded library `lib` as a dict (include/twog_gcn.h states every field); with n_cus > 0
+    no device is touched. A shape query: the descriptor carries no buffer. served False: the shape is refused, the other fields
+    but n_cus are 0."""
+    s = SegRnn()
+    s.bs, s.T, s.H, s.O, s.hidden, s.msg_segment = int(bs), int(T), int(H), int(O), int(h), int(bool(msg_segment))
+    s.rel_hh, s.rel_ho, s.rel_oh, s.rel_oo = (int(bool(r)) for r in rels)
+    out = (C.c_int32 * SEGRNN_PLAN_INTS)()
+    rc = lib.twog_segrnn_persistent_plan(C.byref(s), int(n_cus), out)
+    if rc != 0:
+        raise RuntimeError(f'twog_segrnn_persistent_plan failed with code {rc}')
+    p = dict(zip(SEGRNN_PLAN_FIELDS, out[:13]))
+    p.update(served=bool(out[0]), x3q1=bool(out[10]), pair_mask=out[6] & 0xffffffff, scratch_bytes=out[13] + (out[14] << 31),
+             n_cus=out[15])
+    return p
+
+
 MTL_PASS, MTL_SOFTMAX, MTL_MSE, MTL_MAE = 0, 1, 2, 3   # TWOG_MTL_*
 MTL_MAX_TERMS = 16   # TWOG_MTL_MAX_TERMS
 
@@ -336,6 +358,7 @@ SIGNATURES = {
     'twog_segrnn_fwd_persistent': [C.POINTER(SegRnn), _P, _P],
     'twog_segrnn_bwd_persistent_scratch_bytes': [C.POINTER(SegRnn)],
     'twog_segrnn_bwd_persistent': [C.POINTER(SegRnn), C.POINTER(SegRnnBwd), _P, C.c_size_t, _P, _P],
+    'twog_segrnn_persistent_plan': [C.POINTER(SegRnn), _I, C.POINTER(C.c_int32)],
     'twog_graph_cache_stats': [c_int64_p, c_int64_p],
     'twog_pos_embed_fwd': [_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, Rows, _P, _P],
     'twog_periodic_embed_bwd': [Rows, _P, _I, _I, _P, _P],

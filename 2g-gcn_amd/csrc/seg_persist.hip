@@ -1323,7 +1323,45 @@ bool make_plan(const twog_segrnn_t& S, int n_cus, SegPlan& pl) {
     return pl.grid <= n_cus && pl.grid % 8 == 0;
 }
 
+// counters of a launch: four roles per (direction, chunk) group, a 128-byte line each; they must end below the error word
+size_t sync_words_used(const SegPlan& pl) { return (size_t)2 * pl.n_chunks * 4 * CNT_STRIDE; }
+
+int bwd_dw_pad(const twog_segrnn_t& S, int cpc);
+size_t bwd_lds(const twog_segrnn_t& S, const SegPlan& pl);
+size_t bwd_scratch_bytes(const twog_segrnn_t& S, const SegPlan& pl);
+// backward instance: Q1's products with the 3 x bf16 split at the wide reductions (see q1_step)
+bool bwd_x3q1(const twog_segrnn_t& S) { return S.hidden >= 256; }
+
 }  // namespace
+
+// What the two persistent launches would launch with for the SHAPE of *desc (bs, T, H, O, hidden, msg_segment, rel_*) on n_cus
+// compute units (<= 0: those of the current device), without a launch; with n_cus > 0 without any device call. The numbers
+// are those of make_plan(), bwd_lds(), bwd_dw_pad() and bwd_scratch_bytes(): what the launches and
+// twog_segrnn_persistent_supported use. A pure shape query: no pointer of the descriptor is read or tested -- the four that
+// make_plan() requires (gi_*, u_*) are set on a copy --, so the report says what a launch with valid buffers does. Layout of
+// `out`: include/twog_gcn.h.
+extern "C" int twog_segrnn_persistent_plan(const twog_segrnn_t* desc, int n_cus, int32_t* out) {
+    if (!desc || !out) return -2;
+    if (n_cus <= 0) {
+        const hipError_t e = twog_device_cus(&n_cus);
+        if (e != hipSuccess) return -(int)e;
+    }
+    for (int i = 0; i < TWOG_SEGRNN_PLAN_INTS; ++i) out[i] = 0;
+    out[15] = n_cus;
+    static const float given = 0.f;
+    twog_segrnn_t S = *desc;
+    S.gi_h = S.gi_o = S.u_h = S.u_o = &given;
+    SegPlan pl;
+    if (!make_plan(S, n_cus, pl)) return 0;
+    const size_t lds_b = bwd_lds(S, pl), words = sync_words_used(pl), scratch = bwd_scratch_bytes(S, pl);
+    if (lds_b > 160 * 1024 || words > (size_t)ERR_WORD) return 0;   // (the launches' own refusals; not reached by a planned shape)
+    out[0] = 1; out[1] = pl.cpc; out[2] = pl.n_chunks; out[3] = S.bs - (pl.n_chunks - 1) * pl.cpc;
+    out[4] = pl.mh; out[5] = pl.mo; out[6] = (int32_t)pl.pair_mask; out[7] = pl.grid;
+    out[8] = (int32_t)pl.lds; out[9] = (int32_t)lds_b; out[10] = bwd_x3q1(S) ? 1 : 0; out[11] = bwd_dw_pad(S, pl.cpc);
+    out[12] = (int32_t)words;
+    out[13] = (int32_t)(scratch & 0x7fffffffu); out[14] = (int32_t)(scratch >> 31);
+    return 0;
+}
 
 // 2 if twog_segrnn_fwd_persistent serves this shape on the current device (and is the faster path: it is only served
 // where a chunk's rows fit three 16-row tiles, i.e. small batches), 0 if not.
@@ -1370,7 +1408,7 @@ extern "C" int twog_segrnn_fwd_persistent(const twog_segrnn_t* desc, void* sync,
     P.att = S.att;
     P.cnt = static_cast<unsigned*>(sync);
     P.error = P.cnt + ERR_WORD;
-    if ((size_t)2 * pl.n_chunks * 4 * CNT_STRIDE > (size_t)ERR_WORD) return -2;
+    if (sync_words_used(pl) > (size_t)ERR_WORD) return -2;
     hipStream_t st = (hipStream_t)stream;
 #define TWOG_SP_LAUNCH(MH_, MO_)                                                                              \
     do {                                                                                                      \
@@ -1402,6 +1440,13 @@ size_t bwd_lds(const twog_segrnn_t& S, const SegPlan& pl) {
     if (lds < 84 * 1024) lds = 84 * 1024;
     return lds;
 }
+// the slices' dL/dw shares [2][T][ns][2 n_chunks][dw_pad] and the parked d_u partial sums [2][T][ns][bs (H + O)]
+size_t bwd_scratch_bytes(const twog_segrnn_t& S, const SegPlan& pl) {
+    const int ns = S.hidden / 16;
+    const size_t dw = (size_t)2 * S.T * ns * 2 * pl.n_chunks * bwd_dw_pad(S, pl.cpc);
+    const size_t du = (size_t)2 * S.T * ns * ((size_t)S.bs * S.H + (size_t)S.bs * S.O);
+    return (dw + du) * 4 + 256;
+}
 }  // namespace
 
 // bytes of the caller-owned scratch of twog_segrnn_bwd_persistent (the slices' dL/dw shares and d_u partial sums); 0 if the
@@ -1411,11 +1456,7 @@ extern "C" size_t twog_segrnn_bwd_persistent_scratch_bytes(const twog_segrnn_t* 
     if (!desc || twog_device_cus(&n_cus) != hipSuccess) return 0;
     SegPlan pl;
     if (!make_plan(*desc, n_cus, pl)) return 0;
-    const twog_segrnn_t& S = *desc;
-    const int ns = S.hidden / 16;
-    const size_t dw = (size_t)2 * S.T * ns * 2 * pl.n_chunks * bwd_dw_pad(S, pl.cpc);
-    const size_t du = (size_t)2 * S.T * ns * ((size_t)S.bs * S.H + (size_t)S.bs * S.O);
-    return (dw + du) * 4 + 256;
+    return bwd_scratch_bytes(*desc, pl);
 }
 
 // Same outputs as twog_segrnn_bwd (d_gi_*, d_gh_*, d_pre_*, d_u_* +=; carry_*, tmp_dmg_*, trash, du_part_* unused).
@@ -1459,7 +1500,7 @@ extern "C" int twog_segrnn_bwd_persistent(const twog_segrnn_t* desc, const twog_
     P.du_part[1] = P.du_part[0] + (size_t)2 * S.T * ns * S.bs * S.H;
     P.cnt = static_cast<unsigned*>(sync);
     P.error = P.cnt + ERR_WORD;
-    if ((size_t)2 * pl.n_chunks * 4 * CNT_STRIDE > (size_t)ERR_WORD) return -2;
+    if (sync_words_used(pl) > (size_t)ERR_WORD) return -2;
     const size_t lds = bwd_lds(S, pl);
     if (lds > 160 * 1024) return -2;
     hipStream_t st = (hipStream_t)stream;
@@ -1471,7 +1512,7 @@ extern "C" int twog_segrnn_bwd_persistent(const twog_segrnn_t* desc, const twog_
             return TWOG_PERSIST_NOT_RESIDENT;                                                                 \
         hipLaunchKernelGGL((seg_persist_bwd_kernel<MH_, MO_, X3_>), dim3(pl.grid), dim3(256), lds, st, P);    \
     } while (0)
-    const bool x3q1 = S.hidden >= 256;   // (see q1_step)
+    const bool x3q1 = bwd_x3q1(S);
     if (pl.mo == 1) { if (x3q1) TWOG_SPB_LAUNCH(1, 1, true); else TWOG_SPB_LAUNCH(1, 1, false); }
     else { if (x3q1) TWOG_SPB_LAUNCH(1, 2, true); else TWOG_SPB_LAUNCH(1, 2, false); }
 #undef TWOG_SPB_LAUNCH

@@ -999,6 +999,12 @@ class HipKernels:
             self._check(self.lib.twog_segrnn_bwd(C.byref(s), C.byref(b), *self.chain_workspace(dev), self._stream()), 'twog_segrnn_bwd')
         return out
 
+    def segrnn_persistent_plan(self, bs, T, H, O, h, n_cus=0, msg_segment=True, rels=(True, True, True, True)):
+        """What segrnn_fwd / segrnn_bwd would launch persistently for this shape on n_cus compute units (0: the current
+        device's): whether it is served, clips per chunk, chunks, the (mh, mo) instance, pair mask, grid, LDS bytes, the
+        backward's x3q1 / dw_pad / scratch bytes. Host arithmetic of the library (twog_segrnn_persistent_plan), nothing launched."""
+        return L.segrnn_persistent_plan(self.lib, bs, T, H, O, h, n_cus, msg_segment, rels)
+
     def graph_cache_stats(self):
         """(captured loops, hash-bucket hits resolved by the descriptor compare) of the library's hipGraph cache."""
         n, c = C.c_int64(0), C.c_int64(0)

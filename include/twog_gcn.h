@@ -543,6 +543,31 @@ int twog_segrnn_bwd(const twog_segrnn_t* desc, const twog_segrnn_bwd_t* bdesc, v
 size_t twog_segrnn_bwd_persistent_scratch_bytes(const twog_segrnn_t* desc);
 int twog_segrnn_bwd_persistent(const twog_segrnn_t* desc, const twog_segrnn_bwd_t* bdesc, void* scratch, size_t scratch_bytes,
                                void* sync, void* stream);
+/* What the two persistent launches would launch with for the SHAPE of *desc -- bs, T, H, O, hidden, msg_segment, rel_* -- on
+ * n_cus compute units (n_cus <= 0: those of the current device): host arithmetic only, nothing is launched, and with n_cus > 0
+ * no device is touched. The launchers, twog_segrnn_persistent_supported and twog_segrnn_bwd_persistent_scratch_bytes take their
+ * numbers from the same code. A pure shape query: no pointer of *desc is read or tested (they may all be NULL); the report says
+ * what a launch with valid buffers does, where the launchers themselves also refuse a descriptor without gi_* / u_*.
+ * out: int32 [TWOG_SEGRNN_PLAN_INTS], written whole:
+ *   out[0]  1 = served, 0 = not served (hidden not 64 / 128 / 256 / 512, message_segment or a relation off, H not 1 .. 4, O not
+ *           1 .. 12, a chunk of clips beyond one 16-row tile of humans or two of objects, fewer than 8 x hidden / 16 compute
+ *           units); every field below except out[15] is then 0
+ *   out[1]  cpc, clips per chunk; out[2] n_chunks, chunks per direction: chunk c holds clips [c cpc, min(bs, (c + 1) cpc));
+ *           out[3] clips of the last chunk (< cpc: ragged)
+ *   out[4]  mh, out[5] mo: 16-row tiles of a chunk's human / object rows -- the forward launch runs seg_persist_fwd_kernel
+ *           <mh, mo>, the backward seg_persist_bwd_kernel<mh, mo, x3q1>
+ *   out[6]  pair_mask: bit (8 i + j), i <= j, set when Gram tile (i, j) of the chunk's row tiles (humans first) holds two rows
+ *           of one clip; the other tiles are not computed
+ *   out[7]  grid of either launch: 2 directions x n_chunks x 4 roles x hidden / 16 workgroups of 256 threads
+ *   out[8]  dynamic LDS bytes of the forward launch, out[9] of the backward launch
+ *   out[10] x3q1: 1 when the backward instance multiplies Q1's products with the 3 x bf16 split (hidden >= 256)
+ *   out[11] dw_pad: floats of a slice's parked dL/dw share per (direction, step, chunk, kind)
+ *   out[12] uint32 words of `sync` the counters use (2 x n_chunks x 4 lines of 32); they end below the error word
+ *   out[13], out[14] bytes of the backward launch's scratch (twog_segrnn_bwd_persistent_scratch_bytes): out[13] + 2^31 out[14]
+ *   out[15] the compute-unit count the plan was made for
+ * Returns 0 (also for a shape that is not served), -2 for a NULL argument, or the negative HIP error of the device query. */
+#define TWOG_SEGRNN_PLAN_INTS 16
+int twog_segrnn_persistent_plan(const twog_segrnn_t* desc, int n_cus, int32_t* out);
 /* hipGraph cache of the time loops (twog_bigru_*, twog_segrnn_*): number of captured loops and of hash-bucket hits whose
  * descriptor bytes differed (each was resolved by the byte compare; see csrc/graph_cache.h). Diagnostics / tests. */
 int twog_graph_cache_stats(int64_t* entries, int64_t* collisions);

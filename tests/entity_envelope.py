@@ -262,6 +262,10 @@ def judge(hip, s32, s64, factor=FACTOR, row_factor=None):
 
 
 # ------------------------------------------------------------------------------------------------ segment recurrence
+def seg_factor(h):
+    return FACTOR_X3 if h >= 256 else FACTOR   # wide reductions multiply on the bf16 matrix cores (X3)
+
+
 @functools.lru_cache(maxsize=2)
 def seg_spec(bs, T, H, O, h):
     """(forward buffers fp32 / fp64, incoming gradients, backward outputs fp32 / fp64); both backward runs read the fp32

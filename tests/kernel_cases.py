@@ -30,9 +30,12 @@ def _attn_case(dev, H, O, D, h, n_inst, ipc, geo, recv_mask, seed=0):
     return d
 
 
-def _seg_params(dev, bs, T, H, O, h, rels, msg_segment=True, seed=0):
+def _seg_params(dev, bs, T, H, O, h, rels, msg_segment=True, seed=0, b_hh=True, b_smsg=True, obj_mask='two_clips', gates='random'):
+    """b_hh / b_smsg False: the descriptor carries no such bias (None). obj_mask: 'two_clips' (the last object of clip 0 and every
+    object of clip 1 virtual), None (no mask: every object valid), 'all' (every object of every clip virtual), 'one_valid' (object
+    b % O of clip b is the only valid one). gates: 'random' 0 / 1, 'closed' (u = 0: no state ever changes), 'open' (u = 1)."""
     w_sc = 0.3 if h <= 64 else 0.3 * math.sqrt(64.0 / h)   # keep pre-activations O(1) at full width
-    if T > 50:
+    if T > 32:
         w_sc = 0.4 / math.sqrt(h)   # long chains: contractive dynamics, so rounding differences do not amplify over T
     t = lambda *s, sd=0, sc=None: rnd(*s, seed=seed + sd, scale=w_sc if sc is None else sc).to(dev)
     rel_hh, rel_ho, rel_oh, rel_oo = rels
@@ -41,20 +44,31 @@ def _seg_params(dev, bs, T, H, O, h, rels, msg_segment=True, seed=0):
     fw_h, fw_o = 3 * h, 4 * h
     wih_h = [t(3 * h, fw_h + nmh * h, sd=1 + d) for d in range(2)]
     wih_o = [t(3 * h, fw_o + nmo * h, sd=3 + d) for d in range(2)]
-    mask = torch.ones(bs, O)
-    mask[0, O - 1] = 0
-    if bs > 1:
-        mask[1] = 0
+    if obj_mask == 'two_clips':
+        mask = torch.ones(bs, O)
+        mask[0, O - 1] = 0
+        if bs > 1:
+            mask[1] = 0
+    elif obj_mask == 'all':
+        mask = torch.zeros(bs, O)
+    elif obj_mask == 'one_valid':
+        mask = torch.zeros(bs, O)
+        mask[torch.arange(bs), torch.arange(bs) % O] = 1
+    else:
+        assert obj_mask is None, obj_mask
+        mask = None
+    gate = {'random': lambda g: g, 'closed': torch.zeros_like, 'open': torch.ones_like}[gates]
+    bias = lambda on, *s, sd: [t(*s, sd=sd + d) if on else None for d in range(2)]
     p = dict(bs=bs, T=T, H=H, O=O, hidden=h, msg_segment=msg_segment, rel_hh=rel_hh, rel_ho=rel_ho, rel_oh=rel_oh,
              rel_oo=rel_oo, att_scale=1 / math.sqrt(h), gi_h=t(bs, T, H, 6 * h, sd=5, sc=1.0), gi_o=t(bs, T, O, 6 * h, sd=6, sc=1.0),
-             u_h=(rnd(bs, T, H, seed=seed + 7) > 0).float().to(dev), u_o=(rnd(bs, T, O, seed=seed + 8) > 0).float().to(dev),
-             obj_mask=mask.to(dev),
-             w_hh_h=[t(3 * h, h, sd=9 + d) for d in range(2)], b_hh_h=[t(3 * h, sd=11 + d) for d in range(2)],
-             w_hh_o=[t(3 * h, h, sd=13 + d) for d in range(2)], b_hh_o=[t(3 * h, sd=15 + d) for d in range(2)],
+             u_h=gate((rnd(bs, T, H, seed=seed + 7) > 0).float()).to(dev), u_o=gate((rnd(bs, T, O, seed=seed + 8) > 0).float()).to(dev),
+             obj_mask=None if mask is None else mask.to(dev),
+             w_hh_h=[t(3 * h, h, sd=9 + d) for d in range(2)], b_hh_h=bias(b_hh, 3 * h, sd=11),
+             w_hh_o=[t(3 * h, h, sd=13 + d) for d in range(2)], b_hh_o=bias(b_hh, 3 * h, sd=15),
              w_ihm_h=[w[:, fw_h:] for w in wih_h], w_ihm_o=[w[:, fw_o:] for w in wih_o],
              ld_ih_h=fw_h + nmh * h, ld_ih_o=fw_o + nmo * h,
-             w_smsg_h=t(max(nsh, 1) * h, h, sd=17)[:nsh * h], b_smsg_h=t(max(nsh, 1) * h, sd=18)[:nsh * h],
-             w_smsg_o=t(max(nso, 1) * h, h, sd=19)[:nso * h], b_smsg_o=t(max(nso, 1) * h, sd=20)[:nso * h])
+             w_smsg_h=t(max(nsh, 1) * h, h, sd=17)[:nsh * h], b_smsg_h=t(max(nsh, 1) * h, sd=18)[:nsh * h] if b_smsg else None,
+             w_smsg_o=t(max(nso, 1) * h, h, sd=19)[:nso * h], b_smsg_o=t(max(nso, 1) * h, sd=20)[:nso * h] if b_smsg else None)
     p['_keep'] = (wih_h, wih_o)
     return p
 

@@ -15,7 +15,7 @@ import torch
 import twog_gcn_amd  # noqa: F401
 from twog_gcn_amd import kernels as twog_kernels
 from tests import entity_envelope as EE
-from tests.entity_envelope import F, FACTOR, FACTOR_X3
+from tests.entity_envelope import F, FACTOR
 from tests.kernel_cases import _seg_params, attn_bwd_case
 
 pytestmark = pytest.mark.gpu
@@ -199,10 +199,6 @@ def test_sender_side_gather_at_the_segment_level_placement_with_4_humans_and_12_
 
 
 # ------------------------------------------------------------------------------------------------ segment recurrence
-def _seg_factor(h):
-    return FACTOR_X3 if h >= 256 else FACTOR   # wide reductions multiply on the bf16 matrix cores (X3)
-
-
 def _seg_backward_inputs(b32, own):
     bg = {k: v.to(DEV) for k, v in b32.items()}   # the specification's forward buffers: isolates the backward kernels
     for k in own:
@@ -223,14 +219,14 @@ def test_segment_recurrence_launch_per_step_over_the_entity_range(K, bs, T, H, O
     g2 = K.segrnn_fwd(pg)
     V = Verdict(f'segrnn_stepwise_f{fusion}_bs{bs}_T{T}_H{H}_O{O}_h{h}')
     for k in EE.SEG_FWD_KEYS:
-        V.add('fwd ' + k, g1[k], b32[k], b64[k], _seg_factor(h))
+        V.add('fwd ' + k, g1[k], b32[k], b64[k], EE.seg_factor(h))
         V.same('fwd ' + k, g1[k], g2[k])
     bg = _seg_backward_inputs(b32, g1)
     o1 = K.segrnn_bwd(pg, bg, dh_h.to(DEV), dh_o.to(DEV))
     assert not K.last_segrnn_bwd_persistent
     o2 = K.segrnn_bwd(pg, bg, dh_h.to(DEV), dh_o.to(DEV))
     for k in o32:
-        V.add('bwd ' + k, o1[k], o32[k], o64[k], _seg_factor(h))
+        V.add('bwd ' + k, o1[k], o32[k], o64[k], EE.seg_factor(h))
         V.same('bwd ' + k, o1[k], o2[k])
     V.check()
 
@@ -256,7 +252,7 @@ def test_segment_recurrence_persistent_launch_over_the_entity_range(K, bs, T, H,
     V = Verdict(f'segrnn_persistent_bs{bs}_T{T}_H{H}_O{O}_h{h}')
     for k in EE.SEG_FWD_KEYS:
         close(g1[k], gs[k], rtol=5e-5, atol=5e-6, what='persistent vs stepwise: ' + k)
-        V.add('fwd ' + k, g1[k], b32[k], b64[k], _seg_factor(h))
+        V.add('fwd ' + k, g1[k], b32[k], b64[k], EE.seg_factor(h))
         V.same('fwd ' + k, g1[k], g2[k])
     bg = _seg_backward_inputs(b32, g1)
     monkeypatch.setenv('TWOG_SEG_PERSIST', '0')
@@ -269,6 +265,6 @@ def test_segment_recurrence_persistent_launch_over_the_entity_range(K, bs, T, H,
     torch.cuda.synchronize()
     for k in o32:
         close(o1[k], o0[k], rtol=1e-4, atol=1e-5, what='persistent vs stepwise bwd: ' + k)
-        V.add('bwd ' + k, o1[k], o32[k], o64[k], _seg_factor(h))
+        V.add('bwd ' + k, o1[k], o32[k], o64[k], EE.seg_factor(h))
         V.same('bwd ' + k, o1[k], o2[k])
     V.check()
