@@ -210,6 +210,25 @@ def viterbi_workspace(lib, bs, n_classes, T, E):
     return VITERBI_ROUTES[rc], nbytes.value
 
 
+SEGDEC_MAX_DURATION = 128   # TWOG_SEGDEC_MAX_DURATION
+SEGDEC_ROUTES = ('lds', 'workspace')   # TWOG_SEGDEC_ROUTE_LDS, TWOG_SEGDEC_ROUTE_WORKSPACE
+
+
+def segdecode_plan(lib, bs, n_classes, T, E, D):
+    """twog_segdecode_plan of the loaded library `lib` as a dict: class_template, waves (per workgroup), groups (workgroups
+    per clip), route 'lds' or 'workspace', workspace_bytes. No device is touched. ValueError beyond the limits of
+    twog_segdecode_limits."""
+    out, nbytes = (C.c_int32 * 4)(), C.c_size_t(0)
+    rc = lib.twog_segdecode_plan(int(bs), int(n_classes), int(T), int(E), int(D), out, C.byref(nbytes))
+    if rc == -2:
+        raise ValueError(f'the segmental decode takes up to 64 classes, 4096 model steps and durations up to '
+                         f'{SEGDEC_MAX_DURATION}, not {n_classes}, {T} and {D}')
+    if rc < 0:
+        raise RuntimeError(f'twog_segdecode_plan failed with code {rc}')
+    return {'class_template': out[0], 'waves': out[1], 'groups': out[2], 'route': SEGDEC_ROUTES[out[3]],
+            'workspace_bytes': nbytes.value}
+
+
 CRF_CHUNK, CRF_SEQ_WORDS = 16, 4   # TWOG_CRF_CHUNK, TWOG_CRF_SEQ_WORDS
 
 
@@ -424,6 +443,10 @@ SIGNATURES = {
     'twog_viterbi_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
     'twog_viterbi_decode': [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, C.c_size_t, _P],
     'twog_transition_counts': [_P, _I, _I, _I, _I, _I, _L, _P, _P],
+    'twog_segdecode_limits': [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    'twog_segdecode_plan': [_I, _I, _I, _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)],
+    'twog_segdecode': [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, C.c_size_t, _P],
+    'twog_duration_counts': [_P, _I, _I, _I, _I, _I, _I, _L, _P, _P],
     'twog_crf_limits': [C.POINTER(C.c_int), C.POINTER(C.c_int)],
     'twog_crf_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
     'twog_crf_nll_fwd': [_P, _P, _I, _I, _I, _I, _P, _P, _L, _F, _P, _P, _P, _P, _P],

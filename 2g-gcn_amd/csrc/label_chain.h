@@ -1,4 +1,5 @@
-// What the label-chain kernels share: viterbi.hip (decode) and crf.hip (CRF loss, forward and backward). DESIGN section 4.14.
+// What the label-chain kernels share: viterbi.hip (decode), crf.hip (CRF loss, forward and backward) and segdecode.hip
+// (segmental decode). DESIGN sections 4.14 to 4.16.
 //
 // Shape of a recursion kernel. The recurrence is serial in t and parallel in the class: one wave per sequence (clip b,
 // entity e), lane c owns class c, values of other classes come by v_readlane. A workgroup is one clip and up to LC_MAX_WAVES
@@ -71,6 +72,44 @@ inline int lc_launch(const LcGeometry& g, int bs, size_t lds_bytes, void* stream
     hipLaunchKernelGGL(Kernel, dim3(g.groups, bs), dim3(64 * g.waves), lds_bytes, (hipStream_t)stream, args...);
     TWOG_CHECK_LAUNCH();
     return 0;
+}
+
+// The max-plus step over the classes (viterbi.hip, segdecode.hip): m = max over c' of (d[c'] + a[c']), arg = the smallest c'
+// that attains it: a candidate replaces the running best only when it is strictly greater. d[c'] comes from lane c' by
+// v_readlane. Four independent runs over ascending ranges, merged in ascending order under the same rule, give what one run
+// over 0 .. CMAX - 1 gives. Rows c' >= C hold -inf in `a` and in d: they never win.
+template <int CMAX>
+__device__ __forceinline__ void lc_best_predecessor(float d, const float (&a)[CMAX], float& m, int& arg) {
+    constexpr int Q = CMAX / 4;
+    float bq[4];
+    int aq[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        bq[j] = lane_value(d, j * Q) + a[j * Q];
+        aq[j] = j * Q;
+#pragma unroll
+        for (int i = 1; i < Q; ++i) {
+            const float cand = lane_value(d, j * Q + i) + a[j * Q + i];
+            if (cand > bq[j]) { bq[j] = cand; aq[j] = j * Q + i; }
+        }
+    }
+    m = bq[0];
+    arg = aq[0];
+#pragma unroll
+    for (int j = 1; j < 4; ++j)
+        if (bq[j] > m) { m = bq[j]; arg = aq[j]; }
+}
+
+// top = max over the lanes of d, y = the smallest lane that attains it: a scalar run over the lanes, strict comparison.
+template <int CMAX>
+__device__ __forceinline__ void lc_best_class(float d, float& top, int& y) {
+    top = lane_value(d, 0);
+    y = 0;
+#pragma unroll
+    for (int cp = 1; cp < CMAX; ++cp) {
+        const float v = lane_value(d, cp);
+        if (v > top) { top = v; y = cp; }
+    }
 }
 #endif
 

@@ -45,31 +45,6 @@ inline VitPlan vit_plan(int bs, int C, int T, int E) {
     return p;
 }
 
-// m = max over c' of (d[c'] + a[c']), arg = the smallest c' that attains it: a candidate replaces the running best only
-// when it is strictly greater. Four independent runs over ascending ranges, merged in ascending order under the same rule,
-// give what one run over 0 .. CMAX - 1 gives. Rows c' >= C hold -inf in `a` and in d: they never win.
-template <int CMAX>
-__device__ __forceinline__ void best_predecessor(float d, const float (&a)[CMAX], float& m, int& arg) {
-    constexpr int Q = CMAX / 4;
-    float bq[4];
-    int aq[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        bq[j] = lane_value(d, j * Q) + a[j * Q];
-        aq[j] = j * Q;
-#pragma unroll
-        for (int i = 1; i < Q; ++i) {
-            const float cand = lane_value(d, j * Q + i) + a[j * Q + i];
-            if (cand > bq[j]) { bq[j] = cand; aq[j] = j * Q + i; }
-        }
-    }
-    m = bq[0];
-    arg = aq[0];
-#pragma unroll
-    for (int j = 1; j < 4; ++j)
-        if (bq[j] > m) { m = bq[j]; arg = aq[j]; }
-}
-
 // grid (groups, bs), 64 * EW threads: wave w decodes entity blockIdx.x * EW + w of clip blockIdx.y.
 // LDS: stage[2][C][lc_row(EW)] floats, then on the LDS route EW * seq_words back-pointer words.
 template <int CMAX>
@@ -157,7 +132,7 @@ __global__ __launch_bounds__(64 * LC_MAX_WAVES) void viterbi_kernel(
             } else {
                 float m;
                 int arg;
-                best_predecessor<CMAX>(d, a, m, arg);
+                lc_best_predecessor<CMAX>(d, a, m, arg);      // label_chain.h
                 d = m + x;
                 pack |= (unsigned)arg << (8 * (t & 3));
             }
@@ -171,7 +146,8 @@ __global__ __launch_bounds__(64 * LC_MAX_WAVES) void viterbi_kernel(
     }
     if (!decodes) return;
 
-    // y[L-1] = the smallest c attaining max d[L-1][.]: a scalar run over the lanes, strict comparison
+    // y[L-1] = the smallest c attaining max d[L-1][.]: a scalar run over the lanes, strict comparison (lc_best_class of
+    // label_chain.h is this run; called here it reorders the kernel's code, so the measured form stays written out)
     float top = lane_value(d, 0);
     int y = 0;
 #pragma unroll

@@ -1897,6 +1897,72 @@ class HipKernels:
                         'twog_transition_counts')
         return counts
 
+    # ---------------------------------------------------------------- segmental decode under a duration model
+    def segdecode_limits(self):
+        """(largest class count, most model steps, longest duration) segment_decode takes."""
+        max_classes, max_steps, max_duration = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self.lib.twog_segdecode_limits(C.byref(max_classes), C.byref(max_steps), C.byref(max_duration)),
+                    'twog_segdecode_limits')
+        return max_classes.value, max_steps.value, max_duration.value
+
+    def segdecode_plan(self, bs, num_classes, T, E, D):
+        """The launch of a segmental decode of this shape as a dict: class_template, waves per workgroup, groups per clip,
+        route ('lds' keeps the back-pointers in LDS, 'workspace' in device memory) and workspace_bytes. Launch-free;
+        ValueError beyond segdecode_limits."""
+        return L.segdecode_plan(self.lib, bs, num_classes, T, E, D)
+
+    def segment_decode(self, logp, transitions, durations, initial=None, lengths=None, downsampling=1, target_steps=None):
+        """The best segmentation of every (clip, entity) sequence of (bs, C, T, E) log-probabilities under fp32 (C, C)
+        segment-transition scores (row = from), fp32 (C, D) duration scores (column l - 1: a segment of l steps) and
+        optional (C,) initial scores, as include/twog_gcn.h defines it at twog_segdecode. lengths: int64 (bs,) on the
+        device, in model steps, or None. Returns (labels int64 (bs, target_steps, E), upsampled like predict_labels, and
+        score fp32 (bs, E)). ValueError beyond segdecode_limits, before any launch."""
+        assert logp.dim() == 4 and logp.dtype == torch.float32
+        logp = logp.contiguous()
+        bs, Cn, T, E = logp.shape
+        assert durations.dim() == 2 and durations.shape[0] == Cn and durations.shape[1] >= 1 \
+            and durations.dtype == torch.float32 and durations.is_contiguous() and durations.device == logp.device, \
+            (tuple(durations.shape), durations.dtype)
+        D = durations.shape[1]
+        max_classes, max_steps, max_duration = self.segdecode_limits()
+        if Cn > max_classes or T > max_steps or D > max_duration:
+            raise ValueError(f'segment_decode takes up to {max_classes} classes, {max_steps} model steps and durations up to '
+                             f'{max_duration}, not {Cn}, {T} and {D}')
+        assert transitions.shape == (Cn, Cn) and transitions.dtype == torch.float32 and transitions.is_contiguous() \
+            and transitions.device == logp.device, (tuple(transitions.shape), transitions.dtype)
+        if initial is not None:
+            assert initial.shape == (Cn,) and initial.dtype == torch.float32 and initial.is_contiguous() \
+                and initial.device == logp.device
+        if lengths is not None:
+            assert lengths.shape == (bs,) and lengths.dtype == torch.int64 and lengths.is_contiguous() \
+                and lengths.device == logp.device, (tuple(lengths.shape), lengths.dtype, lengths.device)
+        target_steps = T * int(downsampling) if target_steps is None else int(target_steps)
+        labels = torch.empty(bs, target_steps, E, dtype=torch.int64, device=logp.device)
+        score = torch.empty(bs, E, dtype=torch.float32, device=logp.device)
+        if bs == 0 or E == 0 or T == 0:
+            return labels, score
+        ws_bytes = self.segdecode_plan(bs, Cn, T, E, D)['workspace_bytes']
+        ws = self.workspace(ws_bytes, logp.device, 'segdecode') if ws_bytes else None
+        self._check(self.lib.twog_segdecode(logp.data_ptr(), bs, Cn, T, E, transitions.data_ptr(), _ptr(initial),
+                                            durations.data_ptr(), D, _ptr(lengths), max(1, int(downsampling)), target_steps,
+                                            labels.data_ptr(), score.data_ptr(), _ptr(ws), ws_bytes, self._stream()),
+                    'twog_segdecode')
+        return labels, score
+
+    def duration_counts(self, targets, num_classes, max_duration, stride, ignore_index, counts):
+        """ADDS to counts int64 (C, D) the maximal runs of equal labels of an int64 (bs, T_tgt, E) tensor read at every
+        `stride`-th step, in place: a run of n labels c adds one to counts[c, min(n, D) - 1]; a label equal to ignore_index
+        or outside [0, C) ends a run and starts none."""
+        assert targets.dim() == 3 and targets.dtype == torch.int64 and targets.is_contiguous()
+        assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.shape == (num_classes, max_duration)
+        assert counts.device == targets.device
+        bs, T_tgt, E = targets.shape
+        if bs and E:
+            self._check(self.lib.twog_duration_counts(targets.data_ptr(), bs, T_tgt, E, int(num_classes), int(max_duration),
+                                                      int(stride), int(ignore_index), counts.data_ptr(), self._stream()),
+                        'twog_duration_counts')
+        return counts
+
 
 def viterbi_decode(logp, transitions, initial=None, lengths=None, downsampling=1, target_steps=None):
     """`get_kernels().viterbi_decode`: see HipKernels.viterbi_decode."""
@@ -1916,6 +1982,26 @@ def crf_limits():
 def transition_counts(targets, num_classes, stride, ignore_index, counts):
     """`get_kernels().transition_counts`: see HipKernels.transition_counts."""
     return get_kernels().transition_counts(targets, num_classes, stride, ignore_index, counts)
+
+
+def segment_decode(logp, transitions, durations, initial=None, lengths=None, downsampling=1, target_steps=None):
+    """`get_kernels().segment_decode`: see HipKernels.segment_decode."""
+    return get_kernels().segment_decode(logp, transitions, durations, initial, lengths, downsampling, target_steps)
+
+
+def segdecode_limits():
+    """`get_kernels().segdecode_limits()`: (largest class count, most model steps, longest duration)."""
+    return get_kernels().segdecode_limits()
+
+
+def segdecode_plan(bs, num_classes, T, E, D):
+    """`get_kernels().segdecode_plan`: see HipKernels.segdecode_plan."""
+    return get_kernels().segdecode_plan(bs, num_classes, T, E, D)
+
+
+def duration_counts(targets, num_classes, max_duration, stride, ignore_index, counts):
+    """`get_kernels().duration_counts`: see HipKernels.duration_counts."""
+    return get_kernels().duration_counts(targets, num_classes, max_duration, stride, ignore_index, counts)
 
 
 def segment_f1_words(n_seq, K):

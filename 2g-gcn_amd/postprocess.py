@@ -19,7 +19,12 @@ reference does not compute it, so its definition is stated at `edit_score_per_ex
 `ViterbiDecoder` replaces the per-step argmax by the best label path under a label-transition model (twog_viterbi_decode;
 the reference has no such decode either, `viterbi_labels` states the definition); `transition_counts`,
 `transition_log_probs` and `switch_penalty` make the model. `process_output` and `EvaluationAccumulator` take a decoder.
+
+`SegmentalDecoder` stands in the same slot and scores whole segments: emission sum + per-class duration score +
+segment-to-segment transition (twog_segdecode; `segment_decode_labels` states the definition). `duration_counts`,
+`duration_log_probs` and `segment_transition_log_probs` make its model from label tensors.
 """
+import math
 from collections import namedtuple
 
 import numpy as np
@@ -55,9 +60,10 @@ def predict_labels(output: torch.Tensor, target: torch.Tensor = None, downsampli
 
 def process_output(outputs, downsampling: int = 1, targets=None, index_to_name=None, decoder=None, lengths=None):
     """predict.py:186-202 for predictions: list over batches of lists of (bs, C, T, E) outputs -> {index: int64 labels
-    (N, T, E) on the device} (the reference returns numpy arrays of the same values). decoder: a `ViterbiDecoder` (one for
-    every output, or a dict {key: decoder}; an output without one keeps the argmax) that replaces the per-step argmax;
-    lengths: with a decoder, one int64 (bs,) device tensor of model steps per batch, or None."""
+    (N, T, E) on the device} (the reference returns numpy arrays of the same values). decoder: a `ViterbiDecoder` or a
+    `SegmentalDecoder` (one for every output, or a dict {key: decoder}; an output without one keeps the argmax) that
+    replaces the per-step argmax; lengths: with a decoder, one int64 (bs,) device tensor of model steps per batch, or
+    None."""
     per_index = {}
     for bi, output in enumerate(outputs):
         for i, tensor in enumerate(output):
@@ -186,6 +192,169 @@ class ViterbiDecoder:
             lengths = lengths.to(device=output.device, dtype=torch.int64).contiguous()
         labels, self.last_score = get_kernels().viterbi_decode(output, self.transitions, self.initial, lengths,
                                                                int(downsampling), int(steps))
+        return labels
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# Segmental decode under a duration model (twog_segdecode) and the statistics such a model is made from
+def duration_counts(targets, num_classes: int, max_duration: int, stride: int = 1, ignore_index: int = -1,
+                    out=None) -> torch.Tensor:
+    """int64 (C, D) counts of the run lengths of a (bs, T, E) or (bs, T) label tensor on the device, read at the model's
+    rate (targets[b, k * stride, e], k = 0, 1, ...; `stride` is the loader's downsampling): a maximal run of n equal
+    labels c adds one to [c, min(n, D) - 1], D = max_duration. A label counts only if it is in [0, C) and is not
+    `ignore_index`; a run ends at a change of label, at a label that does not count and at the end of the sequence. With
+    `out` the counts are ADDED to it, so that a pass over a loader accumulates (as `transition_counts` does); no host
+    synchronisation either way."""
+    K = get_kernels()
+    targets = targets.to(torch.int64)
+    if targets.ndim == 2:
+        targets = targets.unsqueeze(-1)
+    if targets.ndim != 3:
+        raise ValueError(f'labels (bs, T) or (bs, T, E) expected, not {tuple(targets.shape)}')
+    if int(stride) < 1:
+        raise ValueError(f'stride must be at least 1, not {stride}')
+    if int(max_duration) < 1:
+        raise ValueError(f'max_duration must be at least 1, not {max_duration}')
+    max_classes, _, longest = K.segdecode_limits()
+    if num_classes > max_classes or max_duration > longest:
+        raise ValueError(f'duration_counts takes up to {max_classes} classes and durations up to {longest}, '
+                         f'not {num_classes} and {max_duration}')
+    if out is None:
+        out = K.zeros(num_classes, max_duration, dtype=torch.int64, device=targets.device)
+    return K.duration_counts(targets.contiguous(), int(num_classes), int(max_duration), int(stride), int(ignore_index), out)
+
+
+def _counts_on_host(counts):
+    device = counts.device if isinstance(counts, torch.Tensor) else None
+    n = (counts.cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)).astype(np.float64)
+    return n, device
+
+
+def duration_log_probs(counts, smoothing: float = 1.0, scheme: str = 'empirical') -> torch.Tensor:
+    """fp32 (C, D) duration scores of `duration_counts`, column l - 1 for a segment of l steps, computed in fp64 on the host
+    from ONE copy of the counts and rounded to fp32 once; returned on the device of `counts`.
+    'empirical': log((n + s) / (row sum + D * s)); with smoothing 0 an unseen duration is -inf (forbidden).
+    'poisson': l * log(lambda_c) - lambda_c - lgamma(l + 1) with lambda_c the mean run length of class c in the counts (a
+    run of D or more counts as D); `smoothing` is not used.
+    A class without runs is all zeros either way: nothing is known about how long it lasts."""
+    if scheme not in ('empirical', 'poisson'):
+        raise ValueError(f"scheme must be 'empirical' or 'poisson', not {scheme!r}")
+    n, device = _counts_on_host(counts)
+    if n.ndim != 2 or n.shape[1] < 1:
+        raise ValueError(f'(C, D) counts expected, not {n.shape}')
+    D = n.shape[1]
+    total = n.sum(1, keepdims=True)
+    lengths = np.arange(1, D + 1, dtype=np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        if scheme == 'empirical':
+            s = float(smoothing)
+            logp = np.log((n + s) / (total + D * s))
+        else:
+            lam = (n * lengths).sum(1, keepdims=True) / total
+            lgamma = np.asarray([math.lgamma(l + 1.0) for l in lengths])
+            logp = lengths * np.log(lam) - lam - lgamma
+    logp = np.where(total > 0, logp, 0.0).astype(np.float32)
+    out = torch.from_numpy(logp)
+    return out.to(device) if device is not None else out
+
+
+def segment_transition_log_probs(counts, smoothing: float = 1.0, self_transition=None) -> torch.Tensor:
+    """fp32 (C, C) scores between consecutive SEGMENTS from the frame-level `transition_counts`: the diagonal (a label
+    that stays) is removed before normalising, log((n + s) / (row sum without the diagonal + (C - 1) * s)) off the
+    diagonal, in fp64 on the host from ONE copy of the counts and rounded to fp32 once; a row without any count (and no
+    smoothing) is all zeros. The diagonal is set to `self_transition`; None means -inf: a segment is never followed by one
+    of its own class, so the decoder's `max_duration` D must then cover the longest run, since a run longer than D can only
+    be composed of several segments of the class."""
+    n, device = _counts_on_host(counts)
+    if n.ndim != 2 or n.shape[0] != n.shape[1]:
+        raise ValueError(f'square counts expected, not {n.shape}')
+    Cn = n.shape[0]
+    np.fill_diagonal(n, 0.0)
+    s = float(smoothing)
+    den = n.sum(1, keepdims=True) + (Cn - 1) * s
+    with np.errstate(divide='ignore', invalid='ignore'):
+        logp = np.log((n + s) / den)
+    logp = np.where(den > 0, logp, 0.0)
+    np.fill_diagonal(logp, -np.inf if self_transition is None else float(self_transition))
+    out = torch.from_numpy(logp.astype(np.float32))
+    return out.to(device) if device is not None else out
+
+
+def segment_decode_labels(output, transitions, durations, initial=None, target=None, downsampling: int = 1, lengths=None):
+    """(labels int64 (bs, T_target, E), score fp32 (bs, E)): the best segmentation of every sequence = (clip b, entity e) of
+    (bs, C, T, E) log-probabilities, with T_target as `predict_labels` has it. `transitions` A fp32 (C, C) scores between
+    consecutive segments (row = from, column = to), `durations` dur fp32 (C, D): dur[c, l-1] is the score of a class-c
+    segment that lasts l steps, `initial` pi fp32 (C,) or None (all zero), `lengths` int64 (bs,) on the device in model
+    steps (clamped to [0, T]; None means T), all on the output's device. With logp[t, c] = output[b, c, t, e] and L the
+    length, in fp32, each add rounding once in the order written, nothing fused or reordered:
+
+        e[0][c] = pi[c]
+        e[t][c] = max over c' of (d[t-1][c'] + A[c',c])      prev[t][c] = the SMALLEST c' that attains it   (t >= 1)
+        for l = 1 .. min(D, t+1), ascending:   acc_l = acc_(l-1) + logp[t-l+1,c]   (acc_0 = 0)
+                                               cand_l = (e[t-l+1][c] + dur[c,l-1]) + acc_l
+        d[t][c] = max over l of cand_l         len[t][c] = the SMALLEST l that attains it
+        end:  c = the smallest class attaining max d[L-1][.];  score = that maximum;  t = L-1
+        back: l = len[t][c];  y[t-l+1 .. t] = c;  stop if t-l+1 == 0;  c = prev[t-l+1][c];  t = t - l
+
+    A candidate replaces the running best only when it is strictly greater. The diagonal of A is used like any other
+    entry: a segment may be followed by one of its own class at A[c,c], which is how runs longer than D are composed;
+    -inf forbids it. -inf in A, pi and dur (forbidden transitions, minimum durations) is in contract, NaN is not (it still
+    gives labels in [0, C)). labels[b, t', e] = y[min(t' // downsampling, L - 1)]; a length of 0 gives label 0 everywhere
+    and score 0.0. tests/segdecode_ref.py is this definition in numpy, and the kernel (twog_segdecode) meets it bit for
+    bit. ValueError beyond `kernels.segdecode_limits()`."""
+    if output.ndim != 4:
+        raise RuntimeError(f'Number of dimensions for output is {output.ndim}')  # predict.py:66-67
+    downsampling = max(1, int(downsampling))
+    steps = output.shape[-2] if (downsampling <= 1 or target is None) else target.shape[-2]   # as predict_labels
+    return get_kernels().segment_decode(output, transitions, durations, initial, lengths, downsampling, steps)
+
+
+class SegmentalDecoder:
+    """`ViterbiDecoder` with a duration model: the best segmentation of every (clip, entity) under fp32 (C, C) scores
+    between consecutive segments (row = from, column = to; -inf forbids), fp32 (C, D) duration scores (column l - 1: a
+    segment of l steps; -inf forbids a duration) and optional (C,) initial scores, decoded on the device by twog_segdecode
+    (`segment_decode_labels` states the recurrence and its tie-break). `num_classes` is C and `max_duration` D. The tensors
+    are kept in fp32 and moved once to the device of the first output decoded.
+
+    decoder(output, target=None, downsampling=1, lengths=None) and decode(output, downsampling, steps, lengths=None) are
+    those of `ViterbiDecoder`, so `process_output` and `EvaluationAccumulator` take either. `last_score` holds the fp32
+    (bs, E) scores of the last call."""
+
+    def __init__(self, transitions, durations, initial=None):
+        as_f32 = lambda v: torch.as_tensor(v).detach().to(torch.float32).contiguous()
+        self.transitions = as_f32(transitions)
+        if self.transitions.ndim != 2 or self.transitions.shape[0] != self.transitions.shape[1]:
+            raise ValueError(f'transitions must be (C, C), not {tuple(self.transitions.shape)}')
+        self.num_classes = self.transitions.shape[0]
+        self.durations = as_f32(durations)
+        if self.durations.ndim != 2 or self.durations.shape[0] != self.num_classes or self.durations.shape[1] < 1:
+            raise ValueError(f'durations must be ({self.num_classes}, D) with D >= 1, not {tuple(self.durations.shape)}')
+        self.max_duration = self.durations.shape[1]
+        self.initial = None if initial is None else as_f32(initial)
+        if self.initial is not None and self.initial.shape != (self.num_classes,):
+            raise ValueError(f'initial must be ({self.num_classes},), not {tuple(self.initial.shape)}')
+        self.last_score = None
+
+    def __call__(self, output: torch.Tensor, target: torch.Tensor = None, downsampling: int = 1, lengths=None):
+        if output.ndim != 4:
+            raise RuntimeError(f'Number of dimensions for output is {output.ndim}')  # predict.py:66-67
+        downsampling = max(1, int(downsampling))
+        steps = output.shape[-2] if (downsampling <= 1 or target is None) else target.shape[-2]   # as predict_labels
+        return self.decode(output, downsampling, steps, lengths)
+
+    def decode(self, output, downsampling, steps, lengths=None):
+        """The labels at `steps` target steps, int64 (bs, steps, E): step t' reads model step t' // downsampling, as
+        twog_eval_update evaluates it."""
+        if output.shape[1] != self.num_classes:
+            raise ValueError(f'the output has {output.shape[1]} classes, the transition model {self.num_classes}')
+        if self.transitions.device != output.device:
+            self.transitions = self.transitions.to(output.device)
+            self.durations = self.durations.to(output.device)
+            self.initial = None if self.initial is None else self.initial.to(output.device)
+        if lengths is not None:
+            lengths = lengths.to(device=output.device, dtype=torch.int64).contiguous()
+        labels, self.last_score = get_kernels().segment_decode(output, self.transitions, self.durations, self.initial,
+                                                               lengths, int(downsampling), int(steps))
         return labels
 
 
@@ -573,8 +742,9 @@ class EvaluationAccumulator:
     update ran. edit: also keep, per name, the sum of the per-sequence segmental edit scores (twog_segment_edit on the same
     labels, `bg_label` as in `edit_score_per_example`) and of its valid sequences; `result()[name]['edit']` is their
     ratio. That metric has one route: a batch with more steps than `segment_edit_limits()` is a ValueError.
-    decoder: a `ViterbiDecoder` for every name, or a list with one (or None) per name. A name with a decoder is evaluated on
-    the decoded labels instead of the per-step argmax: twog_viterbi_decode, `_select_steps`, twog_confusion_counts, and
+    decoder: a `ViterbiDecoder` or `SegmentalDecoder` for every name, or a list with one (or None) per name. A name with a
+    decoder is evaluated on the decoded labels instead of the per-step argmax: its decode kernel (twog_viterbi_decode or
+    twog_segdecode), `_select_steps`, twog_confusion_counts, and
     the F1 and edit kernels on those labels; `update(..., lengths=)` passes the valid model steps of the clips to it. A
     step_index entry beyond the last target step is counted in the second error counter and evaluated as padding, as
     twog_eval_update does. Without a decoder nothing changes."""

@@ -1294,6 +1294,57 @@ int twog_transition_counts(const int64_t* targets, int bs, int T_tgt, int E, int
                            int64_t ignore_index, int64_t* counts, void* stream);
 
 /* ===============================================================================================================
+ * Segmental (semi-Markov) decoding: Viterbi over whole segments with a per-class duration score (DESIGN section 4.16;
+ * the reference project has no such decode, tests/segdecode_ref.py is the specification). One sequence = one (clip b,
+ * entity e), with logp[t][c] = logp[b][c][t][e], L the decoded length, A fp32 [C][C] scores between consecutive
+ * segments (row = from, column = to), pi fp32 [C] (NULL: all zero) and dur fp32 [C][D]: dur[c][l-1] is the score of a
+ * class-c segment that lasts l steps, l = 1 .. D. All arithmetic is fp32, each add rounds once in the order written,
+ * nothing is fused or reordered, and a candidate replaces the running best only when it is strictly greater:
+ *     e[0][c] = pi[c]
+ *     e[t][c] = max over c' = 0..C-1 of (d[t-1][c'] + A[c'][c]),  prev[t][c] = the smallest c' attaining it    (t >= 1)
+ *     for l = 1 .. min(D, t+1), ascending:   acc_l = acc_(l-1) + logp[t-l+1][c]   (acc_0 = 0)
+ *                                            cand_l = (e[t-l+1][c] + dur[c][l-1]) + acc_l
+ *     d[t][c] = max over l of cand_l,        len[t][c] = the smallest l attaining it (the running best starts as cand_1)
+ *     end:  c = the smallest class attaining max d[L-1][.];  score = that maximum;  t = L-1
+ *     back: l = len[t][c];  y[t-l+1 .. t] = c;  stop if t-l+1 == 0;  c = prev[t-l+1][c];  t = t - l
+ * The diagonal of A is used like any other entry: a segment may be followed by one of the same class at A[c][c], which
+ * is how runs longer than D are composed; a caller forbids it with -inf. -inf in A, pi and dur is in contract
+ * (forbidden transitions, minimum durations). NaN is out of contract, but never gives a label outside [0, C) or an
+ * access outside the buffers; the same holds when every path scores -inf.
+ * lengths, downsampling, T_out, labels and score are those of twog_viterbi_decode: labels[b][t'][e] = y[min(t' /
+ *   downsampling, L - 1)], and a length of 0 writes label 0 everywhere and score 0.0.
+ * The working set of a wave is a ring of the last min(D, T) steps of (e, logp) in LDS, dur once per workgroup, and
+ * back-pointers of two bytes per (t, c). twog_segdecode_plan (launch-free) states the launch of a shape: out[0] the class
+ * template (8, 16, 32 or 64), out[1] the waves (= entities) per workgroup, out[2] the workgroups per clip, out[3] the
+ * route:
+ *   TWOG_SEGDEC_ROUTE_LDS, *workspace_bytes = 0: the back-pointers of at least one wave fit in LDS beside the rest; the
+ *   waves are as many (up to 8) as the LDS budget holds rings and back-pointers for, `workspace` is not touched;
+ *   TWOG_SEGDEC_ROUTE_WORKSPACE: they go to `workspace`, *workspace_bytes of device memory (256-byte aligned) that the
+ *   call may overwrite and whose content means nothing afterwards; the waves are as many as the budget holds rings for.
+ * The result does not depend on the route, the waves per workgroup, the chunking or the batch a sequence is decoded in,
+ * bit for bit.
+ * twog_segdecode_limits: the largest C (64), T (4096) and D (TWOG_SEGDEC_MAX_DURATION). Returns: -1 for a bad size
+ * (D < 1 included), -2 beyond the limits (or C * T * E >= 2^31, bs > 65535), -3 for a workspace that is NULL or too
+ * small on the workspace route.
+ *
+ * twog_duration_counts: ADDS to counts int64 [C][D] the run lengths of targets (int64 [bs][T_tgt][E]) read at the
+ *   model's rate, targets[b][k * stride][e] for k = 0, 1, ... while k * stride < T_tgt: a maximal run of n equal labels c
+ *   adds one to counts[c][min(n, D) - 1]. A label counts only if it is in [0, C) and != ignore_index; a run ends at a
+ *   change of label, at a label that does not count, and at the end of the sequence. LDS histograms and integer atomics:
+ *   the totals do not depend on the order. -2 for C > 64 or D > TWOG_SEGDEC_MAX_DURATION.
+ * =============================================================================================================== */
+#define TWOG_SEGDEC_MAX_DURATION 128
+#define TWOG_SEGDEC_ROUTE_LDS 0
+#define TWOG_SEGDEC_ROUTE_WORKSPACE 1
+int twog_segdecode_limits(int* max_classes, int* max_steps, int* max_duration);
+int twog_segdecode_plan(int bs, int n_classes, int T, int E, int D, int32_t* out, size_t* workspace_bytes);
+int twog_segdecode(const float* logp, int bs, int n_classes, int T, int E, const float* A, const float* pi,
+                   const float* dur, int D, const int64_t* lengths, int downsampling, int T_out,
+                   int64_t* labels, float* score, void* workspace, size_t workspace_bytes, void* stream);
+int twog_duration_counts(const int64_t* targets, int bs, int T_tgt, int E, int n_classes, int D, int stride,
+                         int64_t ignore_index, int64_t* counts, void* stream);
+
+/* ===============================================================================================================
  * Linear-chain CRF loss: the sequence negative log-likelihood under learned transition scores (the
  * reference project has no such term, tests/crf_ref.py at fp64 is the specification). The scores it trains go to
  * twog_viterbi_decode unchanged.
