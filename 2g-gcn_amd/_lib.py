@@ -230,6 +230,7 @@ def segdecode_plan(lib, bs, n_classes, T, E, D):
 
 
 CRF_CHUNK, CRF_SEQ_WORDS = 16, 4   # TWOG_CRF_CHUNK, TWOG_CRF_SEQ_WORDS
+SEMICRF_SEQ_WORDS = 4   # TWOG_SEMICRF_SEQ_WORDS
 
 
 def crf_workspace(lib, bs, n_classes, T, E):
@@ -242,6 +243,21 @@ def crf_workspace(lib, bs, n_classes, T, E):
     if rc < 0:
         raise RuntimeError(f'twog_crf_workspace failed with code {rc}')
     return alpha.value, seq.value, partials.value
+
+
+def semicrf_plan(lib, bs, n_classes, T, E, D):
+    """twog_semicrf_plan of the loaded library `lib` as a dict: class_template, fwd_waves / fwd_groups and bwd_waves /
+    bwd_groups (waves per workgroup, workgroups per clip), and the bytes of the workspaces ed_bytes, marks_bytes, seq_bytes,
+    partial_bytes. No device is touched. ValueError beyond the limits of twog_semicrf_limits."""
+    out, nbytes = (C.c_int32 * 5)(), (C.c_size_t * 4)()
+    rc = lib.twog_semicrf_plan(int(bs), int(n_classes), int(T), int(E), int(D), out, nbytes)
+    if rc == -2:
+        raise ValueError(f'the semi-Markov CRF loss takes up to 64 classes, 4096 model steps and durations up to '
+                         f'{SEGDEC_MAX_DURATION}, not {n_classes}, {T} and {D}')
+    if rc < 0:
+        raise RuntimeError(f'twog_semicrf_plan failed with code {rc}')
+    return {'class_template': out[0], 'fwd_waves': out[1], 'fwd_groups': out[2], 'bwd_waves': out[3], 'bwd_groups': out[4],
+            'ed_bytes': nbytes[0], 'marks_bytes': nbytes[1], 'seq_bytes': nbytes[2], 'partial_bytes': nbytes[3]}
 
 
 BIGRU_PLAN_HEAD, BIGRU_PLAN_MAX_COMBOS = 8, 32   # TWOG_BIGRU_PLAN_HEAD, TWOG_BIGRU_PLAN_MAX_COMBOS
@@ -451,6 +467,10 @@ SIGNATURES = {
     'twog_crf_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
     'twog_crf_nll_fwd': [_P, _P, _I, _I, _I, _I, _P, _P, _L, _F, _P, _P, _P, _P, _P],
     'twog_crf_nll_bwd': [_P, _P, _I, _I, _I, _I, _P, _L, _F, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P],
+    'twog_semicrf_limits': [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    'twog_semicrf_plan': [_I, _I, _I, _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_size_t)],
+    'twog_semicrf_nll_fwd': [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _L, _F, _P, _P, _P, _P, _P, _P],
+    'twog_semicrf_nll_bwd': [_P, _P, _I, _I, _I, _I, _P, _P, _I, _L, _F, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P],
 }
 
 _lib = None

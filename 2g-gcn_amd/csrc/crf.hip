@@ -22,7 +22,6 @@ namespace {
 // values (backward: A[c', :] and its sums) stay in the register file with no scratch.
 constexpr int CRF_MAX_WAVES_WIDE = 4;
 __host__ __device__ constexpr int crf_max_waves(int classes) { return classes > 32 ? CRF_MAX_WAVES_WIDE : LC_MAX_WAVES; }
-constexpr int CRF_FINAL_THREADS = 256;
 
 struct CrfPlan {
     LcGeometry g;
@@ -38,11 +37,6 @@ inline CrfPlan crf_plan(int bs, int C, int T, int E) {
     p.seq_bytes = n_seq * TWOG_CRF_SEQ_WORDS * sizeof(float);
     p.partial_bytes = n_seq * C * (C + 1) * sizeof(float);
     return p;
-}
-
-// the label of a step as the chain sees it: the class of a kept step, -1 for a removed one (the NLL terms' rule)
-__device__ __forceinline__ int chain_label(long long y, long long ignore, int C) {
-    return twog_label_kept(y, ignore, C) ? (int)y : -1;
 }
 
 // grid (groups, bs), 64 * EW threads: wave w runs entity blockIdx.x * EW + w of clip blockIdx.y.
@@ -67,7 +61,7 @@ __global__ __launch_bounds__(64 * crf_max_waves(CMAX)) void crf_fwd_kernel(
     float pre[R];
     const long long* labels = target + (int64_t)b * T * E + (runs ? e : 0);
     auto fetch_label = [&](int t0) {
-        return (runs && lane < LC_CHUNK && t0 + lane < T) ? chain_label(labels[(int64_t)(t0 + lane) * E], ignore, C) : -1;
+        return (runs && lane < LC_CHUNK && t0 + lane < T) ? lc_chain_label(labels[(int64_t)(t0 + lane) * E], ignore, C) : -1;
     };
 
     const float NEG_INF = -__builtin_inff();
@@ -141,33 +135,6 @@ __global__ __launch_bounds__(64 * crf_max_waves(CMAX)) void crf_fwd_kernel(
     }
 }
 
-// One workgroup: sum of nll_seq and of K over the sequences in fp64, thread i taking sequences i, i + 256, ... and the
-// threads' sums added in a fixed tree; {sum, count} into stats, weight * sum / count (0 when nothing is kept) into loss.
-__global__ __launch_bounds__(CRF_FINAL_THREADS) void crf_final_kernel(const float* __restrict__ seq, int64_t n_seq,
-                                                                       float weight, double* stats, float* loss) {
-    __shared__ double red[2][CRF_FINAL_THREADS];
-    double sum = 0.0, cnt = 0.0;
-    for (int64_t s = threadIdx.x; s < n_seq; s += CRF_FINAL_THREADS) {
-        sum += (double)seq[s * TWOG_CRF_SEQ_WORDS + 2];
-        cnt += (double)__float_as_int(seq[s * TWOG_CRF_SEQ_WORDS + 3]);
-    }
-    red[0][threadIdx.x] = sum;
-    red[1][threadIdx.x] = cnt;
-    __syncthreads();
-    for (int o = CRF_FINAL_THREADS / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + o];
-            red[1][threadIdx.x] += red[1][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        stats[0] = red[0][0];
-        stats[1] = red[1][0];
-        loss[0] = weight * (float)(red[1][0] > 0.0 ? red[0][0] / red[1][0] : 0.0);
-    }
-}
-
 // Same geometry as crf_fwd_kernel, the kept steps walked from the last to the first.
 // LDS: stage[2][C][row] floats, then (dinput != NULL) out[2][C][row] floats.
 // partials (NULL: the parameters need no gradient) [bs * E][C + 1][C]: rows 0 .. C-1 = sum_k (xi_k - indicator) of the
@@ -220,7 +187,7 @@ __global__ __launch_bounds__(64 * crf_max_waves(CMAX)) void crf_bwd_kernel(
     };
     const long long* labels = target + (int64_t)b * T * E + (runs ? e : 0);
     auto fetch_label = [&](int t0) {
-        return (runs && lane < LC_CHUNK && t0 + lane < T) ? chain_label(labels[(int64_t)(t0 + lane) * E], ignore, C) : -1;
+        return (runs && lane < LC_CHUNK && t0 + lane < T) ? lc_chain_label(labels[(int64_t)(t0 + lane) * E], ignore, C) : -1;
     };
 
     const float NEG_INF = -__builtin_inff();
@@ -354,7 +321,7 @@ extern "C" int twog_crf_nll_fwd(const float* input, const int64_t* target, int b
         });
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(crf_final_kernel, dim3(1), dim3(CRF_FINAL_THREADS), 0, st, seq, (int64_t)bs * E, weight, stats, loss);
+    hipLaunchKernelGGL(lc_nll_final_kernel, dim3(1), dim3(LC_FINAL_THREADS), 0, st, seq, (int64_t)bs * E, weight, stats, loss);
     TWOG_CHECK_LAUNCH();
     return 0;
 }

@@ -1,5 +1,5 @@
-// What the label-chain kernels share: viterbi.hip (decode), crf.hip (CRF loss, forward and backward) and segdecode.hip
-// (segmental decode). DESIGN sections 4.14 to 4.16.
+// What the label-chain kernels share: viterbi.hip (decode), crf.hip (CRF loss, forward and backward), segdecode.hip
+// (segmental decode) and semicrf.hip (semi-Markov CRF loss, forward and backward). DESIGN sections 4.14 to 4.17.
 //
 // Shape of a recursion kernel. The recurrence is serial in t and parallel in the class: one wave per sequence (clip b,
 // entity e), lane c owns class c, values of other classes come by v_readlane. A workgroup is one clip and up to LC_MAX_WAVES
@@ -111,6 +111,45 @@ __device__ __forceinline__ void lc_best_class(float d, float& top, int& y) {
         if (v > top) { top = v; y = cp; }
     }
 }
+
+// The loss kernels (crf.hip, semicrf.hip). A sequence's forward result is LC_SEQ_WORDS floats: logZ, gold, nll, K (int bits).
+constexpr int LC_SEQ_WORDS = 4;
+constexpr int LC_FINAL_THREADS = 256;
+static_assert(TWOG_CRF_SEQ_WORDS == LC_SEQ_WORDS && TWOG_SEMICRF_SEQ_WORDS == LC_SEQ_WORDS, "one layout of the per-sequence words");
+
+// the label of a step as the chain sees it: the class of a kept step, -1 for a removed one (the NLL terms' rule)
+__device__ __forceinline__ int lc_chain_label(long long y, long long ignore, int C) {
+    return twog_label_kept(y, ignore, C) ? (int)y : -1;
+}
+
+namespace {
+// One workgroup: sum of nll_seq and of K over the sequences in fp64, thread i taking sequences i, i + 256, ... and the
+// threads' sums added in a fixed tree; {sum, count} into stats, weight * sum / count (0 when nothing is kept) into loss.
+__global__ __launch_bounds__(LC_FINAL_THREADS) void lc_nll_final_kernel(const float* __restrict__ seq, int64_t n_seq,
+                                                                         float weight, double* stats, float* loss) {
+    __shared__ double red[2][LC_FINAL_THREADS];
+    double sum = 0.0, cnt = 0.0;
+    for (int64_t s = threadIdx.x; s < n_seq; s += LC_FINAL_THREADS) {
+        sum += (double)seq[s * LC_SEQ_WORDS + 2];
+        cnt += (double)__float_as_int(seq[s * LC_SEQ_WORDS + 3]);
+    }
+    red[0][threadIdx.x] = sum;
+    red[1][threadIdx.x] = cnt;
+    __syncthreads();
+    for (int o = LC_FINAL_THREADS / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + o];
+            red[1][threadIdx.x] += red[1][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        stats[0] = red[0][0];
+        stats[1] = red[1][0];
+        loss[0] = weight * (float)(red[1][0] > 0.0 ? red[0][0] / red[1][0] : 0.0);
+    }
+}
+}  // namespace
 #endif
 
 // What thread tid of 64 * EW stages of every chunk: elements k * 64 * EW + tid of the (C, chunk, EW) slab, k = 0 .. R - 1 with

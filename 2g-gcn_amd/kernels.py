@@ -1693,6 +1693,98 @@ class HipKernels:
             out.append((dA, dpi) if want else None)
         return out
 
+    # ---------------------------------------------------------------- semi-Markov CRF loss
+    def semicrf_limits(self):
+        """(largest class count, most model steps, longest duration) the semi-Markov CRF loss takes: those of
+        segdecode_limits."""
+        max_classes, max_steps, max_duration = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self.lib.twog_semicrf_limits(C.byref(max_classes), C.byref(max_steps), C.byref(max_duration)),
+                    'twog_semicrf_limits')
+        return max_classes.value, max_steps.value, max_duration.value
+
+    def semicrf_plan(self, bs, num_classes, T, E, D):
+        """The launches and workspaces of a semi-Markov CRF term of this shape (twog_semicrf_plan) as a dict: class_template,
+        fwd_waves, fwd_groups, bwd_waves, bwd_groups, ed_bytes, marks_bytes, seq_bytes, partial_bytes. Launch-free;
+        ValueError beyond semicrf_limits."""
+        return L.semicrf_plan(self.lib, bs, num_classes, T, E, D)
+
+    def _semicrf_term(self, t):
+        """A semi-Markov CRF term: a CRF term's dict with durations fp32 (C, D) beside transitions and initial. Returns its
+        shape and D; ValueError beyond semicrf_limits."""
+        x, y, A, pi, dur = t['input'], t['target'], t['transitions'], t['initial'], t['durations']
+        assert x.is_contiguous() and y.is_contiguous() and x.dtype == torch.float32 and y.dtype == torch.int64
+        assert x.dim() == 4 and y.shape == (x.shape[0], x.shape[2], x.shape[3]), (tuple(x.shape), tuple(y.shape))
+        bs, Cn, T, E = x.shape
+        assert dur.dim() == 2 and dur.shape[1] >= 1, tuple(dur.shape)
+        D = dur.shape[1]
+        max_classes, max_steps, max_duration = self.semicrf_limits()
+        if Cn > max_classes or T > max_steps or D > max_duration:
+            raise ValueError(f'the semi-Markov CRF loss takes up to {max_classes} classes, {max_steps} model steps and '
+                             f'durations up to {max_duration}, not {Cn}, {T} and {D}')
+        for p, shape in ((A, (Cn, Cn)), (pi, (Cn,)), (dur, (Cn, D))):
+            assert p.shape == shape and p.dtype == torch.float32 and p.is_contiguous() and p.device == x.device, \
+                (tuple(p.shape), p.dtype, p.device)
+        return bs, Cn, T, E, D
+
+    def semicrf_nll_fwd(self, terms, losses_out, stats_out):
+        """The semi-Markov CRF terms (twog_semicrf_nll_fwd in include/twog_gcn.h), one launch pair each, written into the
+        given views as crf_nll_fwd writes them. Every term keeps its 'ed', 'marks' and 'seq' workspaces for semicrf_nll_bwd;
+        seq (bs * E, 4) fp32 holds logZ, gold, nll_seq and K (the bits of an int32) per sequence."""
+        m = len(terms)
+        shapes = [self._semicrf_term(t) for t in terms]   # every refusal before the first launch
+        self._check_tail(m, losses_out, stats_out)
+        for j, (t, (bs, Cn, T, E, D)) in enumerate(zip(terms, shapes)):
+            x = t['input']
+            assert losses_out.device == x.device and stats_out.device == x.device
+            if T == 0 or E == 0:
+                bs = 0   # no sequence: the sums alone, over nothing
+            plan = self.semicrf_plan(bs, Cn, max(T, 1), max(E, 1), D)
+            t['ed'] = torch.empty(plan['ed_bytes'] // 4, dtype=torch.float32, device=x.device)
+            t['marks'] = torch.empty(plan['marks_bytes'] // 4, dtype=torch.int32, device=x.device)
+            t['seq'] = torch.empty(plan['seq_bytes'] // 4 // L.SEMICRF_SEQ_WORDS, L.SEMICRF_SEQ_WORDS, dtype=torch.float32,
+                                   device=x.device)
+            self._check(self.lib.twog_semicrf_nll_fwd(x.data_ptr(), t['target'].data_ptr(), bs, Cn, max(T, 1), max(E, 1),
+                                                      t['transitions'].data_ptr(), t['initial'].data_ptr(),
+                                                      t['durations'].data_ptr(), D, int(t['ignore']), float(t['weight']),
+                                                      t['ed'].data_ptr(), t['marks'].data_ptr(), t['seq'].data_ptr(),
+                                                      stats_out[j].data_ptr(), losses_out[j:].data_ptr(), self._stream()),
+                        'twog_semicrf_nll_fwd')
+
+    def semicrf_nll_bwd(self, terms, stats, dlosses, dins, accumulate, need_params):
+        """The gradients of the terms of semicrf_nll_fwd, scaled by dlosses [m]: as crf_nll_bwd, with (dA, dpi, ddur) per
+        term whose parameters are asked for."""
+        m = len(terms)
+        self._check_tail(m, dlosses, stats, dins, 'two semi-Markov CRF terms share a gradient buffer')
+        out = []
+        for j, t in enumerate(terms):
+            d, want = dins[j], bool(need_params[j])
+            if d is None and not want:
+                out.append(None)
+                continue
+            x = t['input']
+            bs, Cn, T, E = x.shape
+            D = t['durations'].shape[1]
+            if d is not None:
+                assert d.is_contiguous() and d.dtype == torch.float32 and d.shape == x.shape and d.device == x.device
+            if T == 0 or E == 0:
+                bs = 0
+            dA = dpi = ddur = partials = None
+            if want:
+                dA = torch.empty(Cn, Cn, dtype=torch.float32, device=x.device)
+                dpi = torch.empty(Cn, dtype=torch.float32, device=x.device)
+                ddur = torch.empty(Cn, D, dtype=torch.float32, device=x.device)
+                partials = self.workspace(self.semicrf_plan(bs, Cn, max(T, 1), max(E, 1), D)['partial_bytes'], x.device,
+                                          'semicrf_partials')
+            self._check(self.lib.twog_semicrf_nll_bwd(x.data_ptr(), t['target'].data_ptr(), bs, Cn, max(T, 1), max(E, 1),
+                                                      t['transitions'].data_ptr(), t['durations'].data_ptr(), D,
+                                                      int(t['ignore']), float(t['weight']), t['ed'].data_ptr(),
+                                                      t['marks'].data_ptr(), t['seq'].data_ptr(), stats[j].data_ptr(),
+                                                      dlosses[j:].data_ptr(), _ptr(d), int(bool(accumulate[j])), _ptr(partials),
+                                                      _ptr(dA), _ptr(dpi), _ptr(ddur), 0, self._stream()),
+                        'twog_semicrf_nll_bwd')
+            out.append((dA, dpi, ddur) if want else None)
+        return out
+
 
     # ---------------------------------------------------------------- inference post-processing
     def predict_labels(self, logp, downsampling, target_steps):
@@ -1997,6 +2089,16 @@ def segdecode_limits():
 def segdecode_plan(bs, num_classes, T, E, D):
     """`get_kernels().segdecode_plan`: see HipKernels.segdecode_plan."""
     return get_kernels().segdecode_plan(bs, num_classes, T, E, D)
+
+
+def semicrf_limits():
+    """`get_kernels().semicrf_limits()`: (largest class count, most model steps, longest duration) of the semi-Markov CRF loss."""
+    return get_kernels().semicrf_limits()
+
+
+def semicrf_plan(bs, num_classes, T, E, D):
+    """`get_kernels().semicrf_plan`: see HipKernels.semicrf_plan."""
+    return get_kernels().semicrf_plan(bs, num_classes, T, E, D)
 
 
 def duration_counts(targets, num_classes, max_duration, stride, ignore_index, counts):

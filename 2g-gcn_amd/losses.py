@@ -22,7 +22,9 @@ For sequence decoding: the linear-chain CRF loss (`LinearChainCRF`, `crf_loss`, 
 `misc.crf_loss` of `select_loss`), the sequence negative log-likelihood under learned transition scores, which trains the
 emissions and the (C, C) scores jointly; the scores then go to `postprocess.ViterbiDecoder` (`module.decoder()`). Its terms
 follow the smoothing terms in the same loss tensor, one launch pair per term and direction (`twog_crf_nll_fwd/bwd`;
-definition in include/twog_gcn.h and at `crf_loss`); off by default.
+definition in include/twog_gcn.h and at `crf_loss`); off by default. A `SemiMarkovCRF` module takes the place of a
+`LinearChainCRF` wherever one is accepted: the loss over whole segments with learned duration scores (`semi_crf_loss`,
+`twog_semicrf_nll_fwd/bwd`), whose three tables go to `postprocess.SegmentalDecoder` (`module.decoder()`).
 """
 from collections import namedtuple
 from functools import partial
@@ -149,6 +151,107 @@ def crf_loss(input, target, crf, ignore_index=-1):
     return _run([input], [target], [_NLL], [0.0], ignore_index, 'mean', crf=[(0, 1.0, crf)])[1]
 
 
+class SemiMarkovCRF(torch.nn.Module):
+    """The parameters of a semi-Markov CRF over `num_classes` labels and segments of up to `max_duration` steps: `transitions`
+    A fp32 (C, C) between consecutive segments, row = from, column = to (the diagonal is an entry like any other: a segment may
+    be followed by one of its own class), `durations` dur fp32 (C, D) with dur[c, l-1] the score of a class-c segment of l
+    steps, and `initial` pi fp32 (C,): the conventions of `postprocess.SegmentalDecoder`, to which `decoder()` hands them
+    unchanged. All zero-initialised. Trained beside the model: `DataParallel(model, extra_modules=[scrf])` + `FusedAdam`, as
+    `LinearChainCRF` is. The state_dict is the three tensors.
+
+    -inf entries (a forbidden self-transition, an unseen duration) are in contract and get gradient exactly 0, so Adam leaves
+    them where they are. Coupled (non-decoupled) weight decay does not: it adds decay * p to the gradient, and -inf then
+    turns into NaN at the first step. Use AdamW (decoupled decay) or no decay for a module that holds -inf."""
+
+    def __init__(self, num_classes: int, max_duration: int):
+        super().__init__()
+        self.num_classes, self.max_duration = int(num_classes), int(max_duration)
+        if self.num_classes < 1 or self.max_duration < 1:
+            raise ValueError(f'num_classes and max_duration must be positive, got {num_classes} and {max_duration}')
+        C, D = self.num_classes, self.max_duration
+        self.transitions = torch.nn.Parameter(torch.zeros(C, C, dtype=torch.float32))
+        self.durations = torch.nn.Parameter(torch.zeros(C, D, dtype=torch.float32))
+        self.initial = torch.nn.Parameter(torch.zeros(C, dtype=torch.float32))
+
+    @classmethod
+    def from_counts(cls, transition_counts, duration_counts, smoothing: float = 1.0, scheme: str = 'empirical',
+                    self_transition=None, initial_counts=None):
+        """Start from label statistics, exactly as a `SegmentalDecoder` is built from them: transitions =
+        `postprocess.segment_transition_log_probs(transition_counts, smoothing, self_transition)` (self_transition None: a
+        -inf diagonal, so max_duration must cover the longest labelled run), durations =
+        `postprocess.duration_log_probs(duration_counts, smoothing, scheme)` (smoothing 0: -inf for unseen durations);
+        initial = log((n + s) / (sum + C s)) of (C,) first-label counts, zeros without them."""
+        from .postprocess import duration_log_probs, segment_transition_log_probs
+        import numpy as np
+        A = segment_transition_log_probs(transition_counts, smoothing, self_transition)
+        dur = duration_log_probs(duration_counts, smoothing, scheme)
+        if dur.shape[0] != A.shape[0]:
+            raise ValueError(f'duration counts of {dur.shape[0]} classes for transition counts of {A.shape[0]}')
+        scrf = cls(A.shape[0], dur.shape[1])
+        with torch.no_grad():
+            scrf.transitions.copy_(A)
+            scrf.durations.copy_(dur)
+            if initial_counts is not None:
+                n = np.asarray(initial_counts.cpu() if torch.is_tensor(initial_counts) else initial_counts).astype(np.float64)
+                if n.shape != (scrf.num_classes,):
+                    raise ValueError(f'initial counts must be ({scrf.num_classes},), not {n.shape}')
+                s = float(smoothing)
+                with np.errstate(divide='ignore'):
+                    scrf.initial.copy_(torch.from_numpy(np.log((n + s) / (n.sum() + n.size * s)).astype(np.float32)))
+        return scrf
+
+    def decoder(self):
+        """A `postprocess.SegmentalDecoder` over detached copies of the current parameters (for `process_output(decoder=)` /
+        `EvaluationAccumulator(decoder=)`); later training steps do not change it."""
+        from .postprocess import SegmentalDecoder
+        return SegmentalDecoder(self.transitions.detach().clone(), self.durations.detach().clone(),
+                                self.initial.detach().clone())
+
+    def extra_repr(self):
+        return f'num_classes={self.num_classes}, max_duration={self.max_duration}'
+
+
+def semi_crf_loss(input, target, scrf, ignore_index=-1):
+    """The semi-Markov CRF loss of (bs, C, T, E) fp32 log-probabilities `input` and int64 (bs, T, E) `target` under the
+    SemiMarkovCRF `scrf`: A fp32 (C, C), pi fp32 (C,), dur fp32 (C, D). It is the sum-product twin of the segmental decode.
+
+    A sequence is (clip b, entity e); its kept steps t_0 < ... < t_{K-1} follow the NLL terms' rule exactly as for `crf_loss`:
+    removed steps drop out of the chain, K = 0 contributes nothing. With x_k[c] = input[b, c, t_k, e], y_k = target[b, t_k, e]
+    and S_c(s, l) = x_s[c] + ... + x_{s+l-1}[c]:
+
+        e_0[c]   = pi[c]
+        e_k[c]   = logsumexp_{c'} (d_{k-1}[c'] + A[c', c])                                   k >= 1
+        d_k[c]   = logsumexp_{l = 1 .. min(D, k+1)} (e_{k-l+1}[c] + dur[c, l-1] + S_c(k-l+1, l))
+        logZ     = logsumexp_c d_{K-1}[c]
+        gold     = the score of the gold segmentation: the maximal runs of equal y over the kept steps; a run of n > D steps is
+                   cut into pieces of D steps from its start with the remainder (1 .. D steps) last, consecutive pieces joined
+                   by A[c, c]:  pi[c_1] + sum_j (dur[c_j, l_j - 1] + S_{c_j}(s_j, l_j)) + sum_{j >= 2} A[c_{j-1}, c_j]
+        nll_seq  = logZ - gold                                                                (>= 0)
+        loss     = (sum over sequences of nll_seq) / (sum over sequences of K)
+
+    The loss is 0 when no step is kept, and the count of the term is the total number of kept steps, as for `crf_loss`.
+    Gradients, with g = dloss / count:
+
+        bd_{K-1}[c] = 0;   bd_k[c] = logsumexp_{c'} (A[c, c'] + be_{k+1}[c'])
+        be_s[c]     = logsumexp_{l = 1 .. min(D, K-s)} (dur[c, l-1] + S_c(s, l) + bd_{s+l-1}[c])
+        mu(s, l, c) = exp(e_s[c] + dur[c, l-1] + S_c(s, l) + bd_{s+l-1}[c] - logZ)           the segment marginal
+        d input[b, c, t_k, e] = g (sum of mu over the segments of class c that cover k - [y_k = c]), 0 at every removed step
+        ddur[c, l-1] = g sum_seq (sum_s mu(s, l, c) - #gold pieces of class c and length l)
+        dA[c', c]    = g sum_seq (sum_{k>=1} exp(d_{k-1}[c'] + A[c', c] + be_k[c] - logZ) - #gold joins c' -> c)
+        dpi[c]       = g sum_seq (exp(pi[c] + be_0[c] - logZ) - [c_1 = c])
+
+    -inf is in contract in A, pi and dur: a logsumexp whose terms are all -inf is -inf, never NaN, and a -inf entry gets
+    gradient exactly 0. Out of contract: +inf and NaN anywhere, and a sequence whose own gold score is -inf, such as a gold run
+    longer than D under A[c, c] = -inf: choose D at least the longest labelled run, or keep the diagonal finite.
+
+    The per-sequence recursions run in fp32, in the log domain with the maximum subtracted; the sums over sequences are carried
+    in fp64 in index order and rounded once; no floating-point atomics, so two runs give the same bits. tests/semicrf_ref.py at
+    fp64 is this definition in numpy. ValueError beyond `kernels.semicrf_limits()` (64 classes, 4096 steps, durations up to
+    128), before any launch. (The input rides on an NLL term of weight 0, whose value is dropped and which gets no backward
+    work.)"""
+    return _run([input], [target], [_NLL], [0.0], ignore_index, 'mean', crf=[(0, 1.0, scrf)])[1]
+
+
 _KIND = {nll_loss: _NLL, F.nll_loss: _NLL, binary_cross_entropy_loss: _BCE, budget_loss: _BUDGET}
 
 # Data-parallel normalisation (SURVEY 8e (b)): every term is a sum over the valid (non-ignored) targets divided by their
@@ -187,15 +290,16 @@ def get_count_reducer():
     return _count_reducer
 
 
-# What _run hands to _MultiTaskLoss beside the tensors. smoothing: [(index, weight, tau)], crf: [(index, weight)], options: None
-# or ([class weight], [positive-class weight]) per term.
-_Spec = namedtuple('_Spec', 'kinds targets weights ignore reducer smoothing options crf')
+# What _run hands to _MultiTaskLoss beside the tensors. smoothing: [(index, weight, tau)], crf and scrf: [(index, weight)] of
+# the linear-chain and of the semi-Markov terms, options: None or ([class weight], [positive-class weight]) per term.
+_Spec = namedtuple('_Spec', 'kinds targets weights ignore reducer smoothing options crf scrf')
 
 
 class _Tail:
-    """One family of terms that follow the zipped ones in the loss tensor (the smoothing terms, the CRF terms). They take their
-    inputs by index: index[j] is the zipped term whose input and gradient buffer term j shares. `name` gives the two launchers
-    of the kernel layer, name_fwd and name_bwd; a term of the family owns n_params parameter tensors (CRF: A and pi)."""
+    """One family of terms that follow the zipped ones in the loss tensor (the smoothing terms, the CRF terms, the semi-Markov
+    CRF terms). They take their inputs by index: index[j] is the zipped term whose input and gradient buffer term j shares.
+    `name` gives the two launchers of the kernel layer, name_fwd and name_bwd; a term of the family owns n_params parameter
+    tensors (CRF: A and pi; semi-Markov CRF: A, pi and dur)."""
 
     def __init__(self, name, index, terms, n_params=0):
         self.name, self.index, self.terms, self.n_params = name, index, terms, n_params
@@ -217,8 +321,10 @@ class _MultiTaskLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec, *inputs):
         kinds, ignore = spec.kinds, spec.ignore
-        # behind the n inputs: (transitions, initial) of every CRF term, so that autograd hands their gradients to the modules
+        # behind the n inputs: (transitions, initial) of every CRF term, then (transitions, initial, durations) of every
+        # semi-Markov one, so that autograd hands their gradients to the modules
         inputs, crf_params = inputs[:len(kinds)], inputs[len(kinds):]
+        scrf_params = crf_params[2 * len(spec.crf):]
         K = get_kernels()
         terms = []
         for x, y, k, w in zip(inputs, spec.targets, kinds, spec.weights):
@@ -237,14 +343,20 @@ class _MultiTaskLoss(torch.autograd.Function):
         chains = [dict(input=terms[i]['input'], target=terms[i]['target'], weight=w, ignore=ignore,
                        transitions=crf_params[2 * j].detach().contiguous(), initial=crf_params[2 * j + 1].detach().contiguous())
                   for j, (i, w) in enumerate(spec.crf)]
-        # the smoothing terms, then the CRF terms, follow the n zipped ones in the same tensors: one more launch (pair) each
-        # writes its part of the tail in place
+        segs = [dict(input=terms[i]['input'], target=terms[i]['target'], weight=w, ignore=ignore,
+                     transitions=scrf_params[3 * j].detach().contiguous(), initial=scrf_params[3 * j + 1].detach().contiguous(),
+                     durations=scrf_params[3 * j + 2].detach().contiguous())
+                for j, (i, w) in enumerate(spec.scrf)]
+        # the smoothing terms, then the CRF terms, then the semi-Markov ones follow the n zipped ones in the same tensors: one
+        # more launch (pair) each writes its part of the tail in place
         tails = []
         if smooth:
             tails.append(_Tail('smooth_loss', [i for i, _, _ in spec.smoothing], smooth))
         if chains:
             tails.append(_Tail('crf_nll', [i for i, _ in spec.crf], chains, n_params=2))
-        tail_terms = smooth + chains
+        if segs:
+            tails.append(_Tail('semicrf_nll', [i for i, _ in spec.scrf], segs, n_params=3))
+        tail_terms = smooth + chains + segs
         losses, stats = fwd(terms, room=len(tail_terms)) if tail_terms else fwd(terms)
         at = len(terms)
         for f in tails:
@@ -362,11 +474,17 @@ def _crf_terms(crf, inputs, kinds):
         x = inputs[i]
         if x.dim() != 4:
             raise ValueError(f'CRF term on input {i}: (bs, C, T, E) log-probabilities are expected, got {tuple(x.shape)}')
-        if not isinstance(module, LinearChainCRF):
-            raise ValueError(f'CRF term on input {i}: a LinearChainCRF module is expected, got {type(module).__name__}')
+        if not isinstance(module, (LinearChainCRF, SemiMarkovCRF)):
+            raise ValueError(f'CRF term on input {i}: a LinearChainCRF or SemiMarkovCRF module is expected, got '
+                             f'{type(module).__name__}')
         if module.num_classes != x.shape[1]:
             raise ValueError(f'CRF term on input {i}: a module of {module.num_classes} classes for an input of {x.shape[1]}')
-        max_classes, max_steps = get_kernels().crf_limits()
+        if isinstance(module, SemiMarkovCRF):
+            max_classes, max_steps, max_duration = get_kernels().semicrf_limits()
+            if module.max_duration > max_duration:
+                raise ValueError(f'CRF term on input {i}: durations up to {max_duration} are taken, not {module.max_duration}')
+        else:
+            max_classes, max_steps = get_kernels().crf_limits()
         if x.shape[1] > max_classes or x.shape[2] > max_steps:
             raise ValueError(f'CRF term on input {i}: up to {max_classes} classes and {max_steps} model steps are taken, '
                              f'not {x.shape[1]} and {x.shape[2]}')
@@ -393,11 +511,16 @@ def _run(inputs, targets, kinds, weights, ignore_value, reduction, smoothing=(),
         # (both would write the gradient buffer of that input in the same launch)
         raise ValueError('more than one smoothing term on the same input')
     crf, modules = _crf_terms(crf, inputs, kinds)
-    crf_params = [p for m in modules for p in (m.transitions, m.initial)]
+    # the linear-chain terms, then the semi-Markov ones, each in list order
+    semi = [isinstance(m, SemiMarkovCRF) for m in modules]
+    scrf = [t for t, s in zip(crf, semi) if s]
+    crf = [t for t, s in zip(crf, semi) if not s]
+    crf_params = [p for m, s in zip(modules, semi) if not s for p in (m.transitions, m.initial)]
+    crf_params += [p for m, s in zip(modules, semi) if s for p in (m.transitions, m.initial, m.durations)]
     # the scope's reducer, and only while autograd records (read here: grad mode is off inside Function.forward)
     reducer = _count_reducer if torch.is_grad_enabled() else None
     losses = _MultiTaskLoss.apply(_Spec(list(kinds), list(targets), [float(w) for w in weights], ignore_value, reducer,
-                                        smoothing, options, crf), *inputs, *crf_params)
+                                        smoothing, options, crf, scrf), *inputs, *crf_params)
     return list(losses.unbind(0))
 
 
@@ -416,11 +539,13 @@ def multi_task_loss(input: list, target: list, loss_functions: list, weight: lis
     appended after the zipped terms in list order (input[index] must be an NLL term's (bs, C, T, E) log-probabilities). Each
     input still receives ONE gradient: the smoothing terms take the inputs by index.
 
-    crf: a list of (index, weight, module), module a LinearChainCRF; term j is weight * crf_loss(input[index], target[index],
-    module), appended after the zipped terms and after the smoothing terms, in list order. input[index] must be an NLL term's
-    (bs, C, T, E) input. A class-count mismatch, a non-NLL index, two CRF terms on one input or a shape beyond
-    kernels.crf_limits() raises ValueError before any launch. dA and dpi come back as the gradients of the module's
-    parameters; a term of weight 0, or one whose parameters and input need no gradient, gets no backward work."""
+    crf: a list of (index, weight, module), module a LinearChainCRF or a SemiMarkovCRF; a term is weight * crf_loss(
+    input[index], target[index], module), or weight * semi_crf_loss(...) for a SemiMarkovCRF, appended after the zipped terms
+    and after the smoothing terms: the linear-chain terms first, then the semi-Markov ones, each in list order. input[index]
+    must be an NLL term's (bs, C, T, E) input. A class-count mismatch, a non-NLL index, two such terms on one input or a shape
+    beyond kernels.crf_limits() / kernels.semicrf_limits() (max_duration included) raises ValueError before any launch. dA and
+    dpi (and ddur) come back as the gradients of the module's parameters; a term of weight 0, or one whose parameters and
+    input need no gradient, gets no backward work."""
     if weight is None:
         weight = [1.0] * len(input)
     n = min(len(input), len(target), len(loss_functions), len(weight))  # zip semantics
@@ -451,10 +576,18 @@ def _crf_keys(dataset_name, cfg, crf):
     return [k for k in allowed if k in crf]
 
 
+def _crf_term_names(keys, crf):
+    """The names of the terms of these keys in the order multi_task_loss appends them: 'CRF_<key>' of the LinearChainCRF
+    modules, then 'SCRF_<key>' of the SemiMarkovCRF ones. crf None: every module counts as a LinearChainCRF."""
+    semi = [crf is not None and isinstance(crf[k], SemiMarkovCRF) for k in keys]
+    return ['CRF_' + k for k, s in zip(keys, semi) if not s] + ['SCRF_' + k for k, s in zip(keys, semi) if s]
+
+
 def select_loss(model_name: str, model_input_type: str, dataset_name: str, cfg, *, crf=None):
     """vhoi/losses.py:8-70 for model '2G-GCN': (criterion, loss_names). cfg needs `.get('misc', default_value={})`.
-    crf: with misc.crf_loss = {add: true, weight: w}, a dict of LinearChainCRF modules keyed by 'SAR', 'SAP', 'OAR', 'OAP':
-    one CRF term per key present, on the final-level NLL term of that name, weighted w times that term's weight."""
+    crf: with misc.crf_loss = {add: true, weight: w}, a dict of LinearChainCRF or SemiMarkovCRF modules keyed by 'SAR', 'SAP',
+    'OAR', 'OAP': one term per key present, on the final-level NLL term of that name, weighted w times that term's weight;
+    named 'CRF_<key>' (linear-chain, first) and 'SCRF_<key>' (semi-Markov, after them)."""
     if model_name != '2G-GCN':
         raise NotImplementedError(f'{model_name}: only the 2G-GCN hot path is built (SURVEY section 8)')
     misc = _misc(cfg)
@@ -507,7 +640,7 @@ def select_loss(model_name: str, model_input_type: str, dataset_name: str, cfg, 
         index = {names[i][len('NLL_'):]: i for i in range(first, len(fns))}
         keys = _crf_keys(dataset_name, cfg, crf)
         options['crf'] = [(index[k], c_weight * weight[index[k]], crf[k]) for k in keys]
-        crf_names = ['CRF_' + k for k in keys]
+        crf_names = _crf_term_names(keys, crf)
     else:
         crf_names = []
     smooth = misc.get('smoothing_loss', {})
@@ -529,11 +662,13 @@ def _n_smoothing_terms(dataset_name, cfg):
 
 
 def select_loss_types(model_name: str, dataset_name: str, cfg, *, crf=None):
-    """vhoi/losses.py:72-80. crf: the dict of modules given to select_loss (None: one CRF term per final-level NLL term)."""
+    """vhoi/losses.py:72-80. crf: the dict of modules given to select_loss (None: one CRF term per final-level NLL term). A
+    linear-chain term is 'crf', a semi-Markov one 'scrf'."""
     if model_name != '2G-GCN':
         raise ValueError(f'Multi-task learning option not implemented for {model_name}')
     types = ['budget'] * 2 + ['bce'] * 2 + ['softmax'] * 8 if dataset_name == 'cad120' else ['budget', 'bce'] + ['softmax'] * 4
-    return types + ['mse'] * _n_smoothing_terms(dataset_name, cfg) + ['crf'] * len(_crf_keys(dataset_name, cfg, crf))
+    kinds = ['scrf' if n.startswith('SCRF_') else 'crf' for n in _crf_term_names(_crf_keys(dataset_name, cfg, crf), crf)]
+    return types + ['mse'] * _n_smoothing_terms(dataset_name, cfg) + kinds
 
 
 def select_loss_learning_mask(model_name: str, dataset_name: str, cfg, *, crf=None):

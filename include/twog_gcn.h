@@ -1400,6 +1400,74 @@ int twog_crf_nll_bwd(const float* input, const int64_t* target, int bs, int n_cl
                      const float* dloss, float* dinput, int accumulate, float* partials, float* dA, float* dpi,
                      int accumulate_params, void* stream);
 
+/* ===============================================================================================================
+ * Semi-Markov CRF loss: the sequence negative log-likelihood over whole segments with learned per-class duration
+ * scores (the reference project has no such term, tests/semicrf_ref.py at fp64 is the
+ * specification). It is the sum-product twin of twog_segdecode, and the three tables it trains go there unchanged.
+ *   input  fp32 [bs][C][T][E] log-probabilities, target int64 [bs][T][E]: as for twog_crf_nll_fwd
+ *   A      fp32 [C][C] scores between consecutive segments, row = from, column = to; the diagonal is an entry like any other
+ *   pi     fp32 [C];   dur fp32 [C][D]: dur[c][l-1] scores a class-c segment of l steps, l = 1 .. D
+ * A sequence is (clip b, entity e); its kept steps t_0 < ... < t_{K-1} follow the NLL terms' rule exactly as for the
+ * linear-chain CRF: removed steps drop out of the chain, K = 0 contributes nothing. With x_k[c] = input[b][c][t_k][e],
+ * y_k = target[b][t_k][e] and S_c(s, l) = x_s[c] + ... + x_{s+l-1}[c]:
+ *     e_0[c]   = pi[c]
+ *     e_k[c]   = logsumexp_{c'} (d_{k-1}[c'] + A[c'][c])                                    k >= 1
+ *     d_k[c]   = logsumexp_{l = 1 .. min(D, k+1)} (e_{k-l+1}[c] + dur[c][l-1] + S_c(k-l+1, l))
+ *     logZ     = logsumexp_c d_{K-1}[c]
+ *     gold     = the score of the gold segmentation: the maximal runs of equal y over the kept steps; a run of n > D steps
+ *                is cut into pieces of D steps from its start with the remainder (1 .. D steps) last, consecutive pieces
+ *                joined by A[c][c]:  pi[c_1] + sum_j (dur[c_j][l_j - 1] + S_{c_j}(s_j, l_j)) + sum_{j >= 2} A[c_{j-1}][c_j]
+ *     nll_seq  = logZ - gold                                                                 (>= 0)
+ *     loss     = weight * (sum over sequences of nll_seq) / (sum over sequences of K)       (0 when no step is kept)
+ * stats[0] = sum of nll_seq, stats[1] = sum of K, as for twog_crf_nll_fwd. Gradients, with g = dloss * weight / stats[1]
+ * (0 when stats[1] <= 0; the caller may have replaced stats[1] by a global count):
+ *     bd_{K-1}[c] = 0;   bd_k[c] = logsumexp_{c'} (A[c][c'] + be_{k+1}[c'])
+ *     be_s[c]     = logsumexp_{l = 1 .. min(D, K-s)} (dur[c][l-1] + S_c(s, l) + bd_{s+l-1}[c])
+ *     mu(s, l, c) = exp(e_s[c] + dur[c][l-1] + S_c(s, l) + bd_{s+l-1}[c] - logZ)           the segment marginal
+ *     End_k[c] = exp(d_k[c] + bd_k[c] - logZ),  Start_k[c] = exp(e_k[c] + be_k[c] - logZ)
+ *     cov_k    = cov_{k+1} + End_k - Start_{k+1}  (cov_K = Start_K = 0): the sum of mu over the segments that cover k
+ *     dinput[b][c][t_k][e] = g * (cov_k[c] - [y_k = c]); every removed step gets 0: the tensor is written completely, with
+ *                            no separate clear (accumulate != 0: the same values are ADDED to what the buffer holds)
+ *     ddur[c][l-1] = g * sum_seq (sum_s mu(s, l, c) - #gold pieces of class c and length l)
+ *     dA[c'][c]    = g * sum_seq (sum_{k>=1} exp(d_{k-1}[c'] + A[c'][c] + be_k[c] - logZ) - #gold joins c' -> c)
+ *     dpi[c]       = g * sum_seq (exp(pi[c] + be_0[c] - logZ) - [c_1 = c])
+ * -inf is in contract in A, pi and dur (a forbidden self-transition, a minimum duration): a logsumexp whose terms are all
+ * -inf is -inf, never NaN, and a -inf entry gets gradient exactly 0.0. Out of contract: +inf and NaN anywhere, and a
+ * sequence whose own gold score is -inf (a gold run longer than D under A[c][c] = -inf, for one): choose D at least the
+ * longest labelled run, or keep the diagonal finite. Out-of-contract inputs cause no access outside the buffers; nll_seq
+ * may then be +inf or NaN.
+ * Arithmetic: the per-sequence recursions run in fp32, every logsumexp in the log domain with the maximum subtracted
+ * (expf / logf of the device library). The sums over sequences (nll_seq, K, dA, dpi, ddur) are carried in fp64 in index
+ * order and rounded to fp32 once. No floating-point atomics: two runs on the same inputs give the same bits, and a
+ * sequence gives the same per-sequence values in any batch.
+ * twog_semicrf_plan (launch-free) states the launches and the workspaces of a shape: out[0] the class template (8, 16, 32
+ * or 64), out[1] / out[2] the waves (= entities) per workgroup and the workgroups per clip of the forward, out[3] / out[4]
+ * those of the backward; the waves are as many (up to 8; backward beyond 32 classes: 4) as the 160 KB LDS budget holds
+ * rings of the last min(D, T) kept steps for (forward: (e, x); backward: (bd, x) and the wave's ddur sums), beside dur and
+ * the staging buffers. bytes[0 .. 3] (all device memory, 8-byte aligned):
+ *   ed       bs * E * T * C float pairs: (e, d) of every kept step, indexed by k; written by the forward, read by the backward
+ *   marks    bs * E * T int32: 1 where a gold piece starts, per step t; written by the forward, read by the backward
+ *   seq      bs * E * TWOG_SEMICRF_SEQ_WORDS floats: logZ, gold, nll_seq, K (the bits of an int32)
+ *   partials bs * E * C * (C + 1 + min(D, T)) floats: the backward's per-sequence sums for dA (C rows), dpi (one row) and
+ *            ddur (min(D, T) rows of C); needed only when the parameter gradients are asked for
+ * twog_semicrf_nll_fwd: two launches (recursion, sums). twog_semicrf_nll_bwd: the recursion (writes dinput when it is not
+ * NULL), then, when dA, dpi and ddur are not NULL (all or none), the reduction over sequences, which stores
+ * (accumulate_params == 0) or adds.
+ * twog_semicrf_limits: those of twog_segdecode_limits. Returns: -1 for a bad size (D < 1 included), -2 beyond the limits
+ * (or C * T * E >= 2^31, bs > 65535), -3 for a missing buffer or workspace.
+ * =============================================================================================================== */
+#define TWOG_SEMICRF_SEQ_WORDS 4
+int twog_semicrf_limits(int* max_classes, int* max_steps, int* max_duration);
+int twog_semicrf_plan(int bs, int n_classes, int T, int E, int D, int32_t* out, size_t* bytes);
+int twog_semicrf_nll_fwd(const float* input, const int64_t* target, int bs, int n_classes, int T, int E, const float* A,
+                         const float* pi, const float* dur, int D, int64_t ignore_index, float weight, float* ed,
+                         int32_t* marks, float* seq, double* stats, float* loss, void* stream);
+int twog_semicrf_nll_bwd(const float* input, const int64_t* target, int bs, int n_classes, int T, int E, const float* A,
+                         const float* dur, int D, int64_t ignore_index, float weight, const float* ed,
+                         const int32_t* marks, const float* seq, const double* stats, const float* dloss, float* dinput,
+                         int accumulate, float* partials, float* dA, float* dpi, float* ddur, int accumulate_params,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
