@@ -60,7 +60,39 @@ struct GateArgs {
     twog_gru_step_bwd_t s[MAXP];
     float* du_part[MAXP];  // [2 * tiles_n][rows] partial row sums of d * (gru - h_prev) for this step, or nullptr
     int gate_of[MAXP];     // per (sorted) problem: index into s, -1 = plain epilogue
+    int vec[MAXP];         // every row set of the step is 16-byte aligned and hidden % 4 == 0: the 16-byte epilogue (gemm_tile)
 };
+
+static_assert(sizeof(Group) + sizeof(GateArgs) <= 4096, "kernel arguments of the gate-fused launches");
+
+// Element-wise GRU gate backward of the fused epilogues (same arithmetic as gru_step_bwd_kernel, gru.hip). One definition
+// for the dword and the 16-byte epilogue, so both contract to the same instructions: bit-identical results.
+struct GateBwdElem { float dr_pre, dz_pre, dn_pre, dn_rg, dprev, du; };
+__device__ __forceinline__ GateBwdElem gate_bwd_elem(float d, float rg, float z, float n, float hn, float h0, float uu, bool has_u) {
+    GateBwdElem e;
+    const float gnew = (1.0f - z) * n + z * h0;
+    e.du = d * (gnew - h0);
+    const float dg = has_u ? uu * d : d;
+    float dprev = has_u ? (1.0f - uu) * d : 0.f;
+    const float dn = dg * (1.0f - z);
+    const float dz = dg * (h0 - n);
+    dprev += dg * z;
+    e.dprev = dprev;
+    e.dn_pre = dn * (1.0f - n * n);
+    e.dr_pre = e.dn_pre * hn * rg * (1.0f - rg);
+    e.dz_pre = dz * z * (1.0f - z);
+    e.dn_rg = e.dn_pre * rg;
+    return e;
+}
+
+// 16-byte access to four consecutive floats of a register array (the arrays the dword epilogues index by MFMA register)
+__device__ __forceinline__ void ld4(float* dst, const float* src) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(src);
+    dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+}
+__device__ __forceinline__ void st4(float* dst, float a, float b, float c, float d) {
+    *reinterpret_cast<f32x4*>(dst) = f32x4{a, b, c, d};
+}
 
 // Tile index -> (row panel, column panel) of a problem. Plain order: major panel by major panel (row panels; column
 // panels for n_major problems), minor index fastest -- the tiles that share the major panel start together and meet its
@@ -981,12 +1013,30 @@ __device__ __forceinline__ void gemm_tile(const Group& g, const GateArgs* ga) {
     float g_dh[GN], g_rg[GN], g_z[GN], g_n[GN], g_hn[GN], g_h0[GN], g_uu[GN];
     int gidx = -1;
     if constexpr (GATE) gidx = ga->gate_of[pi];
+    // GateArgs::vec (uniform over the workgroup): the 16-byte gate epilogue. The wave's 32 x 32 tile goes through LDS after the
+    // reduction, and in pass p = 0 .. 3 a lane owns the columns vc .. vc + 3 of row 8 p + vr: every operand load and result
+    // store moves 16 bytes per lane (eight rows x 128 bytes per instruction) instead of 4. The register arrays above then
+    // hold [pass][column of the quad].
     auto fetch_epilogue = [&]() {
 #pragma unroll
         for (int b = 0; b < TN; ++b)
             bv[b] = (PREFETCH_C && bias && epi_here && kgrp == 0) ? bias[min(n0 + wn + b * 32 + li, N - 1)] : 0.f;
         if constexpr (PREFETCH_C) {
-            if (accumulate && epi_here && kgrp == 0) {
+            bool gvec = false;
+            if constexpr (GATE) gvec = gidx >= 0 && ga->vec[gidx] != 0;
+            if (gvec) {
+                if (accumulate && epi_here && kgrp == 0) {
+                    const int col = min(n0 + wn + (lane & 7) * 4, N - 4);
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const int row = min(m0 + wm + 8 * p + (lane >> 3), M - 1);
+                        ld4(cprev + 4 * p, C.ptr + twog_row_off(C, row) + col);
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) cprev[r] = 0.f;
+                }
+            } else if (accumulate && epi_here && kgrp == 0) {
                 const int col = min(n0 + wn + li, N - 1);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -1010,18 +1060,36 @@ __device__ __forceinline__ void gemm_tile(const Group& g, const GateArgs* ga) {
                 const int hp_lo = has_hp ? (int)S.h_prev.ld_outer : (int)S.dh.ld_outer, hp_li = has_hp ? (int)S.h_prev.ld_inner : (int)S.dh.ld_inner;
                 const float* u_ptr = has_u ? S.u : S.dh.ptr;
                 const int u_lo = has_u ? (int)S.u_ld_outer : 0, u_li = has_u ? (int)S.u_ld_inner : 0;
+                if (ga->vec[gidx]) {
+                    const int vr = lane >> 3, vc = (lane & 7) * 4;
+                    const int col4 = min(n0 + wn + vc, N - 4);   // (N % 4 == 0: a column quad is inside N or beyond it)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int rowc = min(m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * kh, M - 1);
-                    const int o = (int)(((float)rowc + 0.5f) * inv_inner), i = rowc - o * inner;
-                    const float* sv = S.save.ptr + (o * (int)S.save.ld_outer + i * (int)S.save.ld_inner);
-                    g_dh[r] = S.dh.ptr[o * (int)S.dh.ld_outer + i * (int)S.dh.ld_inner + colc];
-                    g_rg[r] = sv[colc];
-                    g_z[r] = sv[H + colc];
-                    g_n[r] = sv[2 * H + colc];
-                    g_hn[r] = sv[3 * H + colc];
-                    g_h0[r] = hp_ptr[o * hp_lo + i * hp_li + colc];
-                    g_uu[r] = u_ptr[o * u_lo + i * u_li];
+                    for (int p = 0; p < 4; ++p) {
+                        const int rowc = min(m0 + wm + 8 * p + vr, M - 1);
+                        const int o = (int)(((float)rowc + 0.5f) * inv_inner), i = rowc - o * inner;
+                        const float* sv = S.save.ptr + (o * (int)S.save.ld_outer + i * (int)S.save.ld_inner);
+                        ld4(g_dh + 4 * p, S.dh.ptr + (o * (int)S.dh.ld_outer + i * (int)S.dh.ld_inner + col4));
+                        ld4(g_rg + 4 * p, sv + col4);
+                        ld4(g_z + 4 * p, sv + (H + col4));
+                        ld4(g_n + 4 * p, sv + (2 * H + col4));
+                        ld4(g_hn + 4 * p, sv + (3 * H + col4));
+                        ld4(g_h0 + 4 * p, hp_ptr + (o * hp_lo + i * hp_li + col4));
+                        g_uu[p] = u_ptr[o * u_lo + i * u_li];
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int rowc = min(m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * kh, M - 1);
+                        const int o = (int)(((float)rowc + 0.5f) * inv_inner), i = rowc - o * inner;
+                        const float* sv = S.save.ptr + (o * (int)S.save.ld_outer + i * (int)S.save.ld_inner);
+                        g_dh[r] = S.dh.ptr[o * (int)S.dh.ld_outer + i * (int)S.dh.ld_inner + colc];
+                        g_rg[r] = sv[colc];
+                        g_z[r] = sv[H + colc];
+                        g_n[r] = sv[2 * H + colc];
+                        g_hn[r] = sv[3 * H + colc];
+                        g_h0[r] = hp_ptr[o * hp_lo + i * hp_li + colc];
+                        g_uu[r] = u_ptr[o * u_lo + i * u_li];
+                    }
                 }
             }
         }
@@ -1225,38 +1293,86 @@ __device__ __forceinline__ void gemm_tile(const Group& g, const GateArgs* ga) {
             const bool has_u = S.u != nullptr, has_hp = S.h_prev.ptr != nullptr;
             const int inner = S.dh.inner > 1 ? S.dh.inner : 1;
             const float inv_inner = 1.0f / (float)inner;
+            float* part = ga->du_part[gidx];
+            if (ga->vec[gidx]) {
+                const int vr = lane >> 3, vc = (lane & 7) * 4;
+                // transpose the wave's tile through LDS: the operand stages are free once every wave has left the reduction
+                // loop. The k-split classes come here from their k-group exchange, whose area [wave][16][64] only this wave
+                // still reads; the others need the one barrier (the last-arriver form has passed it; its ticket is smem[0])
+                float* tp = smem + (KS == 1 ? 64 : 0) + wave * 1024;
+                if constexpr (KS == 1) {
+                    if (!la) __syncthreads();
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tp[((r & 3) + 8 * (r >> 2) + 4 * kh) * 32 + li] = acc[0][0][r];
+                __builtin_amdgcn_wave_barrier();   // (one wave's LDS accesses complete in order)
+                const int col4 = n0 + wn + vc;
+                const int pw = 2 * tn_idx + (wave & 1);
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    const f32x4 a = *reinterpret_cast<const f32x4*>(tp + (8 * p + vr) * 32 + vc);
+                    const int row = m0 + wm + 8 * p + vr;
+                    const bool ok = row < M && col4 < N;
+                    const float uu = has_u ? g_uu[p] : 1.0f;
+                    GateBwdElem e[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int q = 4 * p + j;
+                        const float d = g_dh[q] + a[j] + cprev[q];
+                        e[j] = gate_bwd_elem(d, g_rg[q], g_z[q], g_n[q], g_hn[q], has_hp ? g_h0[q] : 0.f, uu, has_u);
+                    }
+                    if (ok) {
+                        const int o = (int)(((float)row + 0.5f) * inv_inner), i = row - o * inner;
+                        float* dgi = S.dgi.ptr + (o * (int)S.dgi.ld_outer + i * (int)S.dgi.ld_inner + col4);
+                        float* dgh = S.dgh.ptr + (o * (int)S.dgh.ld_outer + i * (int)S.dgh.ld_inner + col4);
+                        st4(dgi, e[0].dr_pre, e[1].dr_pre, e[2].dr_pre, e[3].dr_pre);
+                        st4(dgi + H, e[0].dz_pre, e[1].dz_pre, e[2].dz_pre, e[3].dz_pre);
+                        st4(dgi + 2 * H, e[0].dn_pre, e[1].dn_pre, e[2].dn_pre, e[3].dn_pre);
+                        st4(dgh, e[0].dr_pre, e[1].dr_pre, e[2].dr_pre, e[3].dr_pre);
+                        st4(dgh + H, e[0].dz_pre, e[1].dz_pre, e[2].dz_pre, e[3].dz_pre);
+                        st4(dgh + 2 * H, e[0].dn_rg, e[1].dn_rg, e[2].dn_rg, e[3].dn_rg);
+                        st4(S.dh_prev.ptr + (row * (int)S.dh_prev.ld_outer + col4), e[0].dprev, e[1].dprev, e[2].dprev, e[3].dprev);
+                    }
+                    if (part) {
+                        // row sums over this wave's 32 units in the association of the dword epilogue below (its xor shuffles pair
+                        // columns 16, 8, 4, 2, 1 apart): columns 16, 8, 4 apart are lanes 4, 2, 1 apart here, per column of the
+                        // quad; 2 and 1 apart are in the lane. Same bits; du_reduce_kernel adds the 2 * tiles_n partials per row
+                        float s[4];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            float v = ok ? e[j].du : 0.f;
+                            v += __shfl_xor(v, 4, 64);
+                            v += __shfl_xor(v, 2, 64);
+                            v += __shfl_xor(v, 1, 64);
+                            s[j] = v;
+                        }
+                        const float v = (s[0] + s[2]) + (s[1] + s[3]);
+                        if ((lane & 7) == 0 && row < M) part[(int64_t)pw * S.rows + row] = v;
+                    }
+                }
+                return;
+            }
             float dul[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * kh;
                 const bool ok = row < M && col < N;
                 const float d = g_dh[r] + acc[0][0][r] + cprev[r];
-                const float rg = g_rg[r], z = g_z[r], n = g_n[r], hn = g_hn[r];
-                const float h0 = has_hp ? g_h0[r] : 0.f, uu = has_u ? g_uu[r] : 1.0f;
-                const float gnew = (1.0f - z) * n + z * h0;
-                dul[r] = ok ? d * (gnew - h0) : 0.f;
-                const float dg = has_u ? uu * d : d;
-                float dprev = has_u ? (1.0f - uu) * d : 0.f;
-                const float dn = dg * (1.0f - z);
-                const float dz = dg * (h0 - n);
-                dprev += dg * z;
-                const float dn_pre = dn * (1.0f - n * n);
-                const float dr_pre = dn_pre * hn * rg * (1.0f - rg);
-                const float dz_pre = dz * z * (1.0f - z);
+                const GateBwdElem e = gate_bwd_elem(d, g_rg[r], g_z[r], g_n[r], g_hn[r], has_hp ? g_h0[r] : 0.f, has_u ? g_uu[r] : 1.0f, has_u);
+                dul[r] = ok ? e.du : 0.f;
                 if (ok) {
                     const int o = (int)(((float)row + 0.5f) * inv_inner), i = row - o * inner;
                     float* dgi = S.dgi.ptr + (o * (int)S.dgi.ld_outer + i * (int)S.dgi.ld_inner);
                     float* dgh = S.dgh.ptr + (o * (int)S.dgh.ld_outer + i * (int)S.dgh.ld_inner);
-                    dgi[col] = dr_pre;
-                    dgi[H + col] = dz_pre;
-                    dgi[2 * H + col] = dn_pre;
-                    dgh[col] = dr_pre;
-                    dgh[H + col] = dz_pre;
-                    dgh[2 * H + col] = dn_pre * rg;
-                    S.dh_prev.ptr[row * (int)S.dh_prev.ld_outer + col] = dprev;
+                    dgi[col] = e.dr_pre;
+                    dgi[H + col] = e.dz_pre;
+                    dgi[2 * H + col] = e.dn_pre;
+                    dgh[col] = e.dr_pre;
+                    dgh[H + col] = e.dz_pre;
+                    dgh[2 * H + col] = e.dn_rg;
+                    S.dh_prev.ptr[row * (int)S.dh_prev.ld_outer + col] = e.dprev;
                 }
             }
-            float* part = ga->du_part[gidx];
             if (part) {
                 // row sums over this wave's 32 units (lanes of one half-wave share the rows); the 2 * tiles_n partials
                 // per row are added in fixed order by du_reduce_kernel: deterministic, unlike atomics
@@ -1371,12 +1487,33 @@ struct GruFwdProb {
     int u_ld_outer, u_ld_inner;
     int K2, rows, has_prev, rt_start, inner;
 };
+
+// Element-wise GRU step of the fused forward epilogue (same arithmetic as gru_step_fwd_kernel, gru.hip): ir / iz / in the
+// input side with the accumulated products, hn the W_hn h product. One definition for the dword and the 16-byte epilogue.
+struct GruFwdElem { float h, rg, z, n, hnv; };
+__device__ __forceinline__ GruFwdElem gru_fwd_elem(float ir, float iz, float in_, float hn, float b_r, float b_z, float b_n,
+                                                   float h0, float uu, bool has_u) {
+    GruFwdElem e;
+    const float hr = b_r, hz = b_z;
+    e.hnv = hn + b_n;
+    e.rg = 1.0f / (1.0f + expf(-(ir + hr)));
+    e.z = 1.0f / (1.0f + expf(-(iz + hz)));
+    e.n = tanhf(in_ + e.rg * e.hnv);
+    {
+        // both blends round their two products and the sum separately: the dword epilogue's products are packed multiplies
+        // (v_pk_mul_f32), which do not contract with the add, and this epilogue returns its bits
+#pragma clang fp contract(off)
+        const float gnew = (1.0f - e.z) * e.n + e.z * h0;
+        e.h = has_u ? uu * gnew + (1.0f - uu) * h0 : gnew;
+    }
+    return e;
+}
 struct GruFwdGroup {
     GruFwdProb p[MAXP];
     int n, tiles_n, hidden;
 };
 
-template <int D, int KS, bool X3 = false>
+template <int D, int KS, bool X3 = false, bool EV = false>
 __global__ __launch_bounds__(256 * KS, 1) void gemm_gru_fwd_kernel(const GruFwdGroup g) {
     constexpr int BM = 64, BN = 192, NT = 256 * KS, TM = 1, TN = 3;
     // X3 (bf16 x 3 on the bf16 matrix cores, see gemm_mainloop_x3s): two stages of three bf16 planes of both operand tiles
@@ -1403,23 +1540,56 @@ __global__ __launch_bounds__(256 * KS, 1) void gemm_gru_fwd_kernel(const GruFwdG
     const bool has_u = P.u != nullptr, has_hp = P.has_prev != 0;
     const int inner = P.inner;
     const float inv_inner = 1.0f / (float)inner;
-    const float b_r = P.b_hh ? P.b_hh[unitc] : 0.f, b_z = P.b_hh ? P.b_hh[H + unitc] : 0.f, b_n = P.b_hh ? P.b_hh[2 * H + unitc] : 0.f;
-    float e_r[16], e_z[16], e_n[16], e_h0[16], e_u[16];
+    // EV: the 16-byte epilogue. The four 32 x 32 tiles of the wave go through LDS after the reduction, and in pass p = 0 .. 3 a
+    // lane owns the units vc .. vc + 3 of row 8 p + vr: every operand load and result store moves 16 bytes per lane (eight rows
+    // x 128 bytes per instruction) instead of 4; the register arrays hold [pass][unit of the quad]
+    const int vr = lane >> 3, vc = (lane & 7) * 4;
+    const int unit4 = n0 + (wave & 1) * 32 + vc, unit4c = min(unit4, H - 4);
+    float b_r[EV ? 4 : 1], b_z[EV ? 4 : 1], b_n[EV ? 4 : 1];
+    float e_r[16], e_z[16], e_n[16], e_h0[16], e_u[EV ? 4 : 16];
+    if constexpr (EV) {
+        if (P.b_hh) {
+            ld4(b_r, P.b_hh + unit4c);
+            ld4(b_z, P.b_hh + (H + unit4c));
+            ld4(b_n, P.b_hh + (2 * H + unit4c));
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) b_r[j] = b_z[j] = b_n[j] = 0.f;
+        }
+    } else {
+        b_r[0] = P.b_hh ? P.b_hh[unitc] : 0.f;
+        b_z[0] = P.b_hh ? P.b_hh[H + unitc] : 0.f;
+        b_n[0] = P.b_hh ? P.b_hh[2 * H + unitc] : 0.f;
+    }
     if (kgrp == 0) {
         const float* hp_ptr = has_hp ? P.A.ptr : P.gi.ptr;
         const int hp_lo = has_hp ? (int)P.A.ld_outer : (int)P.gi.ld_outer, hp_li = has_hp ? (int)P.A.ld_inner : (int)P.gi.ld_inner;
         const float* u_ptr = has_u ? P.u : P.gi.ptr;
         const int u_lo = has_u ? P.u_ld_outer : 0, u_li = has_u ? P.u_ld_inner : 0;
+        if constexpr (EV) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int rowc = min(m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * kh, M - 1);
-            const int o = (int)(((float)rowc + 0.5f) * inv_inner), i = rowc - o * inner;
-            const float* gi = P.gi.ptr + (o * (int)P.gi.ld_outer + i * (int)P.gi.ld_inner);
-            e_r[r] = gi[unitc];
-            e_z[r] = gi[H + unitc];
-            e_n[r] = gi[2 * H + unitc];
-            e_h0[r] = hp_ptr[o * hp_lo + i * hp_li + unitc];
-            e_u[r] = u_ptr[o * u_lo + i * u_li];
+            for (int p = 0; p < 4; ++p) {
+                const int rowc = min(m0 + wm + 8 * p + vr, M - 1);
+                const int o = (int)(((float)rowc + 0.5f) * inv_inner), i = rowc - o * inner;
+                const float* gi = P.gi.ptr + (o * (int)P.gi.ld_outer + i * (int)P.gi.ld_inner);
+                ld4(e_r + 4 * p, gi + unit4c);
+                ld4(e_z + 4 * p, gi + (H + unit4c));
+                ld4(e_n + 4 * p, gi + (2 * H + unit4c));
+                ld4(e_h0 + 4 * p, hp_ptr + (o * hp_lo + i * hp_li + unit4c));
+                e_u[p] = u_ptr[o * u_lo + i * u_li];
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rowc = min(m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * kh, M - 1);
+                const int o = (int)(((float)rowc + 0.5f) * inv_inner), i = rowc - o * inner;
+                const float* gi = P.gi.ptr + (o * (int)P.gi.ld_outer + i * (int)P.gi.ld_inner);
+                e_r[r] = gi[unitc];
+                e_z[r] = gi[H + unitc];
+                e_n[r] = gi[2 * H + unitc];
+                e_h0[r] = hp_ptr[o * hp_lo + i * hp_li + unitc];
+                e_u[r] = u_ptr[o * u_lo + i * u_li];
+            }
         }
     }
 
@@ -1456,28 +1626,67 @@ __global__ __launch_bounds__(256 * KS, 1) void gemm_gru_fwd_kernel(const GruFwdG
             hn[r] += red[(48 + r) << 6];
         }
     }
-    if (unit >= H) return;
-    // C/D layout of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+    if constexpr (EV) {
+        // transpose the wave's four tiles through LDS. KS == 2: the exchange area [wave][64][64] above, which only this wave
+        // still reads; KS == 1: the operand stages, free once every wave has left the reduction loops
+        if constexpr (KS == 1) __syncthreads();
+        if (unit >= H) return;   // (H % 32 == 0: whole waves)
+        float* tp = smem + wave * 4096;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * kh;
-        if (row >= M) continue;
-        const float ir = e_r[r] + acc[0][0][r], hr = b_r;
-        const float iz = e_z[r] + acc[0][1][r], hz = b_z;
-        const float in_ = e_n[r] + acc[0][2][r], hnv = hn[r] + b_n;
-        const float rg = 1.0f / (1.0f + expf(-(ir + hr)));
-        const float z = 1.0f / (1.0f + expf(-(iz + hz)));
-        const float n = tanhf(in_ + rg * hnv);
-        const float h0 = has_hp ? e_h0[r] : 0.f;
-        const float gnew = (1.0f - z) * n + z * h0;
-        const float uu = e_u[r];
-        const int o = (int)(((float)row + 0.5f) * inv_inner), i = row - o * inner;
-        P.h_out.ptr[o * (int)P.h_out.ld_outer + i * (int)P.h_out.ld_inner + unit] = has_u ? uu * gnew + (1.0f - uu) * h0 : gnew;
-        float* sv = P.save.ptr + (o * (int)P.save.ld_outer + i * (int)P.save.ld_inner);
-        sv[unit] = rg;
-        sv[H + unit] = z;
-        sv[2 * H + unit] = n;
-        sv[3 * H + unit] = hnv;
+        for (int r = 0; r < 16; ++r) {
+            const int at = ((r & 3) + 8 * (r >> 2) + 4 * kh) * 32 + li;
+            tp[at] = acc[0][0][r];
+            tp[1024 + at] = acc[0][1][r];
+            tp[2048 + at] = acc[0][2][r];
+            tp[3072 + at] = hn[r];
+        }
+        __builtin_amdgcn_wave_barrier();   // (one wave's LDS accesses complete in order)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int at = (8 * p + vr) * 32 + vc;
+            const f32x4 a_r = *reinterpret_cast<const f32x4*>(tp + at), a_z = *reinterpret_cast<const f32x4*>(tp + 1024 + at);
+            const f32x4 a_n = *reinterpret_cast<const f32x4*>(tp + 2048 + at), a_h = *reinterpret_cast<const f32x4*>(tp + 3072 + at);
+            const int row = m0 + wm + 8 * p + vr;
+            if (row >= M) continue;
+            GruFwdElem e[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int q = 4 * p + j;
+                e[j] = gru_fwd_elem(e_r[q] + a_r[j], e_z[q] + a_z[j], e_n[q] + a_n[j], a_h[j], b_r[j], b_z[j], b_n[j],
+                                    has_hp ? e_h0[q] : 0.f, e_u[p], has_u);
+            }
+            const int o = (int)(((float)row + 0.5f) * inv_inner), i = row - o * inner;
+            st4(P.h_out.ptr + (o * (int)P.h_out.ld_outer + i * (int)P.h_out.ld_inner + unit4), e[0].h, e[1].h, e[2].h, e[3].h);
+            float* sv = P.save.ptr + (o * (int)P.save.ld_outer + i * (int)P.save.ld_inner + unit4);
+            st4(sv, e[0].rg, e[1].rg, e[2].rg, e[3].rg);
+            st4(sv + H, e[0].z, e[1].z, e[2].z, e[3].z);
+            st4(sv + 2 * H, e[0].n, e[1].n, e[2].n, e[3].n);
+            st4(sv + 3 * H, e[0].hnv, e[1].hnv, e[2].hnv, e[3].hnv);
+        }
+    } else {
+        if (unit >= H) return;
+        // C/D layout of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * kh;
+            if (row >= M) continue;
+            const float ir = e_r[r] + acc[0][0][r], hr = b_r[0];   // (the arithmetic of gru_fwd_elem)
+            const float iz = e_z[r] + acc[0][1][r], hz = b_z[0];
+            const float in_ = e_n[r] + acc[0][2][r], hnv = hn[r] + b_n[0];
+            const float rg = 1.0f / (1.0f + expf(-(ir + hr)));
+            const float z = 1.0f / (1.0f + expf(-(iz + hz)));
+            const float n = tanhf(in_ + rg * hnv);
+            const float h0 = has_hp ? e_h0[r] : 0.f;
+            const float gnew = (1.0f - z) * n + z * h0;
+            const float uu = e_u[r];
+            const int o = (int)(((float)row + 0.5f) * inv_inner), i = row - o * inner;
+            P.h_out.ptr[o * (int)P.h_out.ld_outer + i * (int)P.h_out.ld_inner + unit] = has_u ? uu * gnew + (1.0f - uu) * h0 : gnew;
+            float* sv = P.save.ptr + (o * (int)P.save.ld_outer + i * (int)P.save.ld_inner);
+            sv[unit] = rg;
+            sv[H + unit] = z;
+            sv[2 * H + unit] = n;
+            sv[3 * H + unit] = hnv;
+        }
     }
 }
 
@@ -2187,13 +2396,23 @@ int twog_internal_gemm_gate_bwd(const twog_gemm_t* pr, int n, const twog_gru_ste
     }
     if (dry_run) return 0;
     GateArgs ga;
+    // the 16-byte epilogue: every row of every operand starts on 16 bytes and hidden is made of whole column quads; any
+    // other step keeps the dword epilogue (TWOG_GATE_EPI_VEC=0: all of them; read per call, tests compare the two)
+    const char* vec_env = getenv("TWOG_GATE_EPI_VEC");
+    const bool vec_on = !vec_env || atoi(vec_env) != 0;
+    auto rows16 = [](const twog_rows_t& m) {
+        return reinterpret_cast<uintptr_t>(m.ptr) % 16 == 0 && m.ld_outer % 4 == 0 && (m.inner <= 1 || m.ld_inner % 4 == 0);
+    };
     for (int i = 0; i < n; ++i) {
         const int src = order[i];
-        ga.gate_of[i] = gates[src].rows > 0 ? i : -1;
-        ga.s[i] = gates[src];
-        ga.du_part[i] = (gates[src].rows > 0 && gates[src].du && du_part) ? du_part[src] : nullptr;
+        const twog_gru_step_bwd_t& G = gates[src];
+        ga.gate_of[i] = G.rows > 0 ? i : -1;
+        ga.s[i] = G;
+        ga.du_part[i] = (G.rows > 0 && G.du && du_part) ? du_part[src] : nullptr;
+        ga.vec[i] = (vec_on && G.rows > 0 && G.hidden % 4 == 0 && rows16(G.dh) && rows16(G.save) && rows16(G.dgi) && rows16(G.dgh) &&
+                     rows16(G.dh_prev) && (!G.h_prev.ptr || rows16(G.h_prev))) ? 1 : 0;
     }
-    for (int i = n; i < MAXP; ++i) { ga.gate_of[i] = -1; ga.du_part[i] = nullptr; }
+    for (int i = n; i < MAXP; ++i) { ga.gate_of[i] = -1; ga.du_part[i] = nullptr; ga.vec[i] = 0; }
     static const int depth = twog_env_int("TWOG_GEMM_DEPTH", 0);
     const int d64 = depth ? ((depth >> 2) & 3) : 2;
     dim3 grid(g.total_tiles, 1), block(256);
@@ -2272,6 +2491,13 @@ int twog_internal_gemm_gru_fwd(const twog_gemm_t* gh, const twog_gemm_t* gim, co
         const int64_t last = (int64_t)((rows - 1) / inner) * m.ld_outer + (int64_t)((rows - 1) % inner) * (m.inner > 1 ? m.ld_inner : 0) + width;
         return m.ld_outer >= 0 && m.ld_inner >= 0 && last < (int64_t(1) << 31);
     };
+    // ev: the instantiations with the 16-byte epilogue, where every row of every problem starts on 16 bytes; any other launch
+    // runs the dword epilogue (TWOG_GRU_FWD_EPI_VEC=0: every launch; read per call, tests compare the two)
+    const char* vec_env = getenv("TWOG_GRU_FWD_EPI_VEC");
+    bool ev = !vec_env || atoi(vec_env) != 0;
+    auto rows16 = [](const twog_rows_t& m) {
+        return reinterpret_cast<uintptr_t>(m.ptr) % 16 == 0 && m.ld_outer % 4 == 0 && (m.inner <= 1 || m.ld_inner % 4 == 0);
+    };
     GruFwdGroup g;
     g.n = n; g.hidden = h; g.tiles_n = (h + 63) / 64;
     int rt = 0;
@@ -2305,6 +2531,8 @@ int twog_internal_gemm_gru_fwd(const twog_gemm_t* gh, const twog_gemm_t* gim, co
         P.b_hh = q.bias; P.u = S.u;
         P.u_ld_outer = (int)S.u_ld_outer; P.u_ld_inner = (int)S.u_ld_inner;
         P.rows = S.rows; P.has_prev = S.h_prev.ptr ? 1 : 0; P.rt_start = rt; P.inner = inner;
+        // (h % 32 == 0 and the rows of A, which are h_prev, are aligned: vec_ok above)
+        ev = ev && rows16(S.gi) && rows16(S.h_out) && rows16(S.save) && reinterpret_cast<uintptr_t>(q.bias) % 16 == 0;
         rt += (S.rows + 63) / 64;
     }
     if (!(mode & 4)) {
@@ -2332,8 +2560,12 @@ int twog_internal_gemm_gru_fwd(const twog_gemm_t* gh, const twog_gemm_t* gim, co
     for (int i = 0; i < n; ++i) x3 = x3 && g.p[i].K2 % 32 == 0;
     if (x3) {
         g_last_class |= TWOG_GEMM_CLASS_X3;
-        hipLaunchKernelGGL((gemm_gru_fwd_kernel<2, 2, true>), dim3(rt * g.tiles_n), dim3(512), 0, (hipStream_t)stream, g);
-    } else if (ksplit == 2) hipLaunchKernelGGL((gemm_gru_fwd_kernel<2, 2>), dim3(rt * g.tiles_n), dim3(512), 0, (hipStream_t)stream, g);
+        if (ev) hipLaunchKernelGGL((gemm_gru_fwd_kernel<2, 2, true, true>), dim3(rt * g.tiles_n), dim3(512), 0, (hipStream_t)stream, g);
+        else hipLaunchKernelGGL((gemm_gru_fwd_kernel<2, 2, true>), dim3(rt * g.tiles_n), dim3(512), 0, (hipStream_t)stream, g);
+    } else if (ksplit == 2) {
+        if (ev) hipLaunchKernelGGL((gemm_gru_fwd_kernel<2, 2, false, true>), dim3(rt * g.tiles_n), dim3(512), 0, (hipStream_t)stream, g);
+        else hipLaunchKernelGGL((gemm_gru_fwd_kernel<2, 2>), dim3(rt * g.tiles_n), dim3(512), 0, (hipStream_t)stream, g);
+    } else if (ev) hipLaunchKernelGGL((gemm_gru_fwd_kernel<2, 1, false, true>), dim3(rt * g.tiles_n), dim3(256), 0, (hipStream_t)stream, g);
     else hipLaunchKernelGGL((gemm_gru_fwd_kernel<2, 1>), dim3(rt * g.tiles_n), dim3(256), 0, (hipStream_t)stream, g);
     TWOG_CHECK_LAUNCH();
     return 0;
