@@ -16,6 +16,7 @@
 // L2 then serves the panel once). Tall reductions (dW = dY^T X, K = rows) use deterministic split-K: partial slabs in
 // the caller's workspace, summed in fixed order by a second kernel.
 #include "bf16x3.h"
+#include "gru_gate.h"
 
 namespace {
 
@@ -64,26 +65,6 @@ struct GateArgs {
 };
 
 static_assert(sizeof(Group) + sizeof(GateArgs) <= 4096, "kernel arguments of the gate-fused launches");
-
-// Element-wise GRU gate backward of the fused epilogues (same arithmetic as gru_step_bwd_kernel, gru.hip). One definition
-// for the dword and the 16-byte epilogue, so both contract to the same instructions: bit-identical results.
-struct GateBwdElem { float dr_pre, dz_pre, dn_pre, dn_rg, dprev, du; };
-__device__ __forceinline__ GateBwdElem gate_bwd_elem(float d, float rg, float z, float n, float hn, float h0, float uu, bool has_u) {
-    GateBwdElem e;
-    const float gnew = (1.0f - z) * n + z * h0;
-    e.du = d * (gnew - h0);
-    const float dg = has_u ? uu * d : d;
-    float dprev = has_u ? (1.0f - uu) * d : 0.f;
-    const float dn = dg * (1.0f - z);
-    const float dz = dg * (h0 - n);
-    dprev += dg * z;
-    e.dprev = dprev;
-    e.dn_pre = dn * (1.0f - n * n);
-    e.dr_pre = e.dn_pre * hn * rg * (1.0f - rg);
-    e.dz_pre = dz * z * (1.0f - z);
-    e.dn_rg = e.dn_pre * rg;
-    return e;
-}
 
 // 16-byte access to four consecutive floats of a register array (the arrays the dword epilogues index by MFMA register)
 __device__ __forceinline__ void ld4(float* dst, const float* src) {
@@ -1286,7 +1267,7 @@ __device__ __forceinline__ void gemm_tile(const Group& g, const GateArgs* ga) {
         static_assert(TM * TN == 1 && PREFETCH_C, "the fused gate epilogue is written for the 64x64 class");
         if (gidx >= 0) {
             // acc + cprev is the complete carried gradient of this (row, unit): run the gate backward of the next chain
-            // step on it (same arithmetic as gru_step_bwd_kernel, gru.hip) and leave the direct path in the carry
+            // step on it (gru_gate.h; the two epilogues round dprev differently, see there) and leave the direct path in the carry
             const twog_gru_step_bwd_t& S = ga->s[gidx];
             const int H = S.hidden;
             const int col = n0 + wn + li;
@@ -1314,12 +1295,12 @@ __device__ __forceinline__ void gemm_tile(const Group& g, const GateArgs* ga) {
                     const int row = m0 + wm + 8 * p + vr;
                     const bool ok = row < M && col4 < N;
                     const float uu = has_u ? g_uu[p] : 1.0f;
-                    GateBwdElem e[4];
+                    GruBwdUnit e[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int q = 4 * p + j;
                         const float d = g_dh[q] + a[j] + cprev[q];
-                        e[j] = gate_bwd_elem(d, g_rg[q], g_z[q], g_n[q], g_hn[q], has_hp ? g_h0[q] : 0.f, uu, has_u);
+                        e[j] = gru_bwd_unit<GruBwdZnRounded>(d, g_rg[q], g_z[q], g_n[q], g_hn[q], has_hp ? g_h0[q] : 0.f, uu, has_u);
                     }
                     if (ok) {
                         const int o = (int)(((float)row + 0.5f) * inv_inner), i = row - o * inner;
@@ -1358,7 +1339,7 @@ __device__ __forceinline__ void gemm_tile(const Group& g, const GateArgs* ga) {
                 const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * kh;
                 const bool ok = row < M && col < N;
                 const float d = g_dh[r] + acc[0][0][r] + cprev[r];
-                const GateBwdElem e = gate_bwd_elem(d, g_rg[r], g_z[r], g_n[r], g_hn[r], has_hp ? g_h0[r] : 0.f, has_u ? g_uu[r] : 1.0f, has_u);
+                const GruBwdUnit e = gru_bwd_unit<GruBwdZnDz>(d, g_rg[r], g_z[r], g_n[r], g_hn[r], has_hp ? g_h0[r] : 0.f, has_u ? g_uu[r] : 1.0f, has_u);
                 dul[r] = ok ? e.du : 0.f;
                 if (ok) {
                     const int o = (int)(((float)row + 0.5f) * inv_inner), i = row - o * inner;
@@ -1474,8 +1455,8 @@ __global__ __launch_bounds__(512, 2) void gemm_gate_bwd_ks_kernel(const Group g,
 // Fused GRU forward step of the recurrent chains (gru.hip, segrnn.hip): one launch per chain step computes
 //   [r | z | n_h] = h_prev W_hh^T            (and  [r | z | n_i] += m W_ih[:, msg]^T  at the segment level)
 // on 64-row x (64 units x 3 gates) tiles and finishes the step in the epilogue -- sigmoid / tanh, the blend with h_prev,
-// the segment gate u -- from the accumulators: no gh round trip through memory, no gate launch. Same arithmetic as
-// gru_step_fwd_kernel (gru.hip); r, z, n and W_hn h + b_hn are saved for the backward chain as before.
+// the segment gate u -- from the accumulators: no gh round trip through memory, no gate launch. The step is gru_gate.h's, with the
+// blends rounded as GruFwdRounded says; r, z, n and W_hn h + b_hn are saved for the backward chain as before.
 // A workgroup stages 64 + 192 operand rows per k-tile (24 FLOP/B instead of the 64x64 tile's 16 -- these launches are
 // bound by the L2 port of their CU, profiles/HISTORY.md section 8) and the unit tile index is the block's XCD, so each L2 keeps
 // one 192-row slice of every weight.
@@ -1488,26 +1469,6 @@ struct GruFwdProb {
     int K2, rows, has_prev, rt_start, inner;
 };
 
-// Element-wise GRU step of the fused forward epilogue (same arithmetic as gru_step_fwd_kernel, gru.hip): ir / iz / in the
-// input side with the accumulated products, hn the W_hn h product. One definition for the dword and the 16-byte epilogue.
-struct GruFwdElem { float h, rg, z, n, hnv; };
-__device__ __forceinline__ GruFwdElem gru_fwd_elem(float ir, float iz, float in_, float hn, float b_r, float b_z, float b_n,
-                                                   float h0, float uu, bool has_u) {
-    GruFwdElem e;
-    const float hr = b_r, hz = b_z;
-    e.hnv = hn + b_n;
-    e.rg = 1.0f / (1.0f + expf(-(ir + hr)));
-    e.z = 1.0f / (1.0f + expf(-(iz + hz)));
-    e.n = tanhf(in_ + e.rg * e.hnv);
-    {
-        // both blends round their two products and the sum separately: the dword epilogue's products are packed multiplies
-        // (v_pk_mul_f32), which do not contract with the add, and this epilogue returns its bits
-#pragma clang fp contract(off)
-        const float gnew = (1.0f - e.z) * e.n + e.z * h0;
-        e.h = has_u ? uu * gnew + (1.0f - uu) * h0 : gnew;
-    }
-    return e;
-}
 struct GruFwdGroup {
     GruFwdProb p[MAXP];
     int n, tiles_n, hidden;
@@ -1648,12 +1609,12 @@ __global__ __launch_bounds__(256 * KS, 1) void gemm_gru_fwd_kernel(const GruFwdG
             const f32x4 a_n = *reinterpret_cast<const f32x4*>(tp + 2048 + at), a_h = *reinterpret_cast<const f32x4*>(tp + 3072 + at);
             const int row = m0 + wm + 8 * p + vr;
             if (row >= M) continue;
-            GruFwdElem e[4];
+            GruFwdUnit e[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int q = 4 * p + j;
-                e[j] = gru_fwd_elem(e_r[q] + a_r[j], e_z[q] + a_z[j], e_n[q] + a_n[j], a_h[j], b_r[j], b_z[j], b_n[j],
-                                    has_hp ? e_h0[q] : 0.f, e_u[p], has_u);
+                e[j] = gru_fwd_unit<GruFwdRounded>(e_r[q] + a_r[j], e_z[q] + a_z[j], e_n[q] + a_n[j], b_r[j], b_z[j], a_h[j] + b_n[j],
+                                                   has_hp ? e_h0[q] : 0.f, e_u[p], has_u);
             }
             const int o = (int)(((float)row + 0.5f) * inv_inner), i = row - o * inner;
             st4(P.h_out.ptr + (o * (int)P.h_out.ld_outer + i * (int)P.h_out.ld_inner + unit4), e[0].h, e[1].h, e[2].h, e[3].h);
@@ -1661,7 +1622,7 @@ __global__ __launch_bounds__(256 * KS, 1) void gemm_gru_fwd_kernel(const GruFwdG
             st4(sv, e[0].rg, e[1].rg, e[2].rg, e[3].rg);
             st4(sv + H, e[0].z, e[1].z, e[2].z, e[3].z);
             st4(sv + 2 * H, e[0].n, e[1].n, e[2].n, e[3].n);
-            st4(sv + 3 * H, e[0].hnv, e[1].hnv, e[2].hnv, e[3].hnv);
+            st4(sv + 3 * H, e[0].hn, e[1].hn, e[2].hn, e[3].hn);
         }
     } else {
         if (unit >= H) return;
@@ -1670,22 +1631,15 @@ __global__ __launch_bounds__(256 * KS, 1) void gemm_gru_fwd_kernel(const GruFwdG
         for (int r = 0; r < 16; ++r) {
             const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * kh;
             if (row >= M) continue;
-            const float ir = e_r[r] + acc[0][0][r], hr = b_r[0];   // (the arithmetic of gru_fwd_elem)
-            const float iz = e_z[r] + acc[0][1][r], hz = b_z[0];
-            const float in_ = e_n[r] + acc[0][2][r], hnv = hn[r] + b_n[0];
-            const float rg = 1.0f / (1.0f + expf(-(ir + hr)));
-            const float z = 1.0f / (1.0f + expf(-(iz + hz)));
-            const float n = tanhf(in_ + rg * hnv);
-            const float h0 = has_hp ? e_h0[r] : 0.f;
-            const float gnew = (1.0f - z) * n + z * h0;
-            const float uu = e_u[r];
+            const GruFwdUnit e = gru_fwd_unit<GruFwdRounded>(e_r[r] + acc[0][0][r], e_z[r] + acc[0][1][r], e_n[r] + acc[0][2][r], b_r[0], b_z[0],
+                                                             hn[r] + b_n[0], has_hp ? e_h0[r] : 0.f, e_u[r], has_u);
             const int o = (int)(((float)row + 0.5f) * inv_inner), i = row - o * inner;
-            P.h_out.ptr[o * (int)P.h_out.ld_outer + i * (int)P.h_out.ld_inner + unit] = has_u ? uu * gnew + (1.0f - uu) * h0 : gnew;
+            P.h_out.ptr[o * (int)P.h_out.ld_outer + i * (int)P.h_out.ld_inner + unit] = e.h;
             float* sv = P.save.ptr + (o * (int)P.save.ld_outer + i * (int)P.save.ld_inner);
-            sv[unit] = rg;
-            sv[H + unit] = z;
-            sv[2 * H + unit] = n;
-            sv[3 * H + unit] = hnv;
+            sv[unit] = e.rg;
+            sv[H + unit] = e.z;
+            sv[2 * H + unit] = e.n;
+            sv[3 * H + unit] = e.hn;
         }
     }
 }
@@ -2357,6 +2311,17 @@ static int gemm_impl(const twog_gemm_t* problems, int n_problems, int a_kmajor, 
     return 0;
 }
 
+// What the fused gate epilogues ask of their operands: they index with 32-bit element offsets. span31: the largest element
+// offset of `rows` rows of `width` floats fits 31 bits (and no stride is negative); u_span31: the same for the segment gate's
+// one float per row, grouped in `inner` rows like the operands.
+static bool span31(const twog_rows_t& m, int rows, int64_t width) {
+    const int inner = m.inner > 1 ? m.inner : 1;
+    const int64_t last = (int64_t)((rows - 1) / inner) * m.ld_outer + (int64_t)((rows - 1) % inner) * (m.inner > 1 ? m.ld_inner : 0) + width;
+    return m.ld_outer >= 0 && m.ld_inner >= 0 && last < (int64_t(1) << 31);
+}
+static bool u_span31(int rows, int inner, int64_t ld_outer, int64_t ld_inner) {
+    return (int64_t)((rows - 1) / inner) * ld_outer + (int64_t)((rows - 1) % inner) * ld_inner < (int64_t(1) << 31);
+}
 
 // Gate-fused launch for the recurrent backward chains (see GateArgs): problems are C += A B with A row-major and B k-major;
 // gates[i].rows > 0 asks for the gate backward `gates[i]` in the epilogue of problem i (its C must be the gate's dh_prev
@@ -2371,11 +2336,6 @@ int twog_internal_gemm_gate_bwd(const twog_gemm_t* pr, int n, const twog_gru_ste
     int bm;
     prepare_group(pr, n, 0, 1, nullptr, 0, g, order, big, bm);
     if (big || g.splitk != 1) return 1;
-    auto span31 = [](const twog_rows_t& m, int rows, int64_t width) {  // largest element offset fits 31 bits
-        const int inner = m.inner > 1 ? m.inner : 1;
-        const int64_t last = (int64_t)((rows - 1) / inner) * m.ld_outer + (int64_t)((rows - 1) % inner) * (m.inner > 1 ? m.ld_inner : 0) + width;
-        return m.ld_outer >= 0 && m.ld_inner >= 0 && last < (int64_t(1) << 31);
-    };
     for (int i = 0; i < n; ++i) {
         if (pr[i].B.inner > 1 || pr[i].batch > 1 || pr[i].bias || pr[i].act) return 1;
         const twog_gru_step_bwd_t& G = gates[i];
@@ -2391,8 +2351,7 @@ int twog_internal_gemm_gate_bwd(const twog_gemm_t* pr, int n, const twog_gru_ste
             !span31(G.dgh, G.rows, H3) || !span31(G.dh_prev, G.rows, G.hidden) ||
             (G.h_prev.ptr && !span31(G.h_prev, G.rows, G.hidden)))
             return 1;
-        if (G.u && ((int64_t)((G.rows - 1) / inner) * G.u_ld_outer + (int64_t)((G.rows - 1) % inner) * G.u_ld_inner >= (int64_t(1) << 31)))
-            return 1;
+        if (G.u && !u_span31(G.rows, inner, G.u_ld_outer, G.u_ld_inner)) return 1;
     }
     if (dry_run) return 0;
     GateArgs ga;
@@ -2400,17 +2359,15 @@ int twog_internal_gemm_gate_bwd(const twog_gemm_t* pr, int n, const twog_gru_ste
     // other step keeps the dword epilogue (TWOG_GATE_EPI_VEC=0: all of them; read per call, tests compare the two)
     const char* vec_env = getenv("TWOG_GATE_EPI_VEC");
     const bool vec_on = !vec_env || atoi(vec_env) != 0;
-    auto rows16 = [](const twog_rows_t& m) {
-        return reinterpret_cast<uintptr_t>(m.ptr) % 16 == 0 && m.ld_outer % 4 == 0 && (m.inner <= 1 || m.ld_inner % 4 == 0);
-    };
     for (int i = 0; i < n; ++i) {
         const int src = order[i];
         const twog_gru_step_bwd_t& G = gates[src];
         ga.gate_of[i] = G.rows > 0 ? i : -1;
         ga.s[i] = G;
         ga.du_part[i] = (G.rows > 0 && G.du && du_part) ? du_part[src] : nullptr;
-        ga.vec[i] = (vec_on && G.rows > 0 && G.hidden % 4 == 0 && rows16(G.dh) && rows16(G.save) && rows16(G.dgi) && rows16(G.dgh) &&
-                     rows16(G.dh_prev) && (!G.h_prev.ptr || rows16(G.h_prev))) ? 1 : 0;
+        ga.vec[i] = (vec_on && G.rows > 0 && G.hidden % 4 == 0 && twog_rows_on_16_bytes(G.dh) && twog_rows_on_16_bytes(G.save) &&
+                     twog_rows_on_16_bytes(G.dgi) && twog_rows_on_16_bytes(G.dgh) && twog_rows_on_16_bytes(G.dh_prev) &&
+                     twog_rows_on_16_bytes(G.h_prev)) ? 1 : 0;   // (h_prev may be absent: a null operand passes)
     }
     for (int i = n; i < MAXP; ++i) { ga.gate_of[i] = -1; ga.du_part[i] = nullptr; ga.vec[i] = 0; }
     static const int depth = twog_env_int("TWOG_GEMM_DEPTH", 0);
@@ -2486,18 +2443,10 @@ int twog_internal_gemm_gru_fwd(const twog_gemm_t* gh, const twog_gemm_t* gim, co
     if (!(mode & (with_msgs ? 2 : 1)) || n <= 0 || n > MAXP) return 1;
     const int h = st[0].hidden;
     if (h < 32 || h % BK) return 1;
-    auto span31 = [](const twog_rows_t& m, int rows, int64_t width) {
-        const int inner = m.inner > 1 ? m.inner : 1;
-        const int64_t last = (int64_t)((rows - 1) / inner) * m.ld_outer + (int64_t)((rows - 1) % inner) * (m.inner > 1 ? m.ld_inner : 0) + width;
-        return m.ld_outer >= 0 && m.ld_inner >= 0 && last < (int64_t(1) << 31);
-    };
     // ev: the instantiations with the 16-byte epilogue, where every row of every problem starts on 16 bytes; any other launch
     // runs the dword epilogue (TWOG_GRU_FWD_EPI_VEC=0: every launch; read per call, tests compare the two)
     const char* vec_env = getenv("TWOG_GRU_FWD_EPI_VEC");
     bool ev = !vec_env || atoi(vec_env) != 0;
-    auto rows16 = [](const twog_rows_t& m) {
-        return reinterpret_cast<uintptr_t>(m.ptr) % 16 == 0 && m.ld_outer % 4 == 0 && (m.inner <= 1 || m.ld_inner % 4 == 0);
-    };
     GruFwdGroup g;
     g.n = n; g.hidden = h; g.tiles_n = (h + 63) / 64;
     int rt = 0;
@@ -2521,8 +2470,7 @@ int twog_internal_gemm_gru_fwd(const twog_gemm_t* gh, const twog_gemm_t* gim, co
         if (!span31(S.gi, S.rows, 3 * h) || !span31(S.h_out, S.rows, h) || !span31(S.save, S.rows, 4 * h) ||
             (S.h_prev.ptr && !span31(S.h_prev, S.rows, h)))
             return 1;
-        if (S.u && ((int64_t)((S.rows - 1) / inner) * S.u_ld_outer + (int64_t)((S.rows - 1) % inner) * S.u_ld_inner >= (int64_t(1) << 31)))
-            return 1;
+        if (S.u && !u_span31(S.rows, inner, S.u_ld_outer, S.u_ld_inner)) return 1;
         GruFwdProb& P = g.p[i];
         P.A = q.A; P.B = q.B;
         if (m2) { P.A2 = gim[i].A; P.B2 = gim[i].B; P.K2 = gim[i].K; }
@@ -2532,7 +2480,7 @@ int twog_internal_gemm_gru_fwd(const twog_gemm_t* gh, const twog_gemm_t* gim, co
         P.u_ld_outer = (int)S.u_ld_outer; P.u_ld_inner = (int)S.u_ld_inner;
         P.rows = S.rows; P.has_prev = S.h_prev.ptr ? 1 : 0; P.rt_start = rt; P.inner = inner;
         // (h % 32 == 0 and the rows of A, which are h_prev, are aligned: vec_ok above)
-        ev = ev && rows16(S.gi) && rows16(S.h_out) && rows16(S.save) && reinterpret_cast<uintptr_t>(q.bias) % 16 == 0;
+        ev = ev && twog_rows_on_16_bytes(S.gi) && twog_rows_on_16_bytes(S.h_out) && twog_rows_on_16_bytes(S.save) && reinterpret_cast<uintptr_t>(q.bias) % 16 == 0;
         rt += (S.rows + 63) / 64;
     }
     if (!(mode & 4)) {

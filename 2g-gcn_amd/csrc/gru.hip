@@ -11,6 +11,7 @@
 // r, z, n and W_hn h are saved for the backward pass, which walks the chain in reverse with the transposed GEMM.
 #include "twog_common.h"
 #include "graph_cache.h"
+#include "gru_gate.h"
 
 namespace {
 
@@ -23,19 +24,6 @@ __device__ __forceinline__ float gate_u(const float* u, int64_t ldo, int64_t ldi
     if (inner <= 1) return u[(int64_t)r * ldo];
     const int o = r / inner;
     return u[(int64_t)o * ldo + (int64_t)(r - o * inner) * ldi];
-}
-
-// One hidden unit of the gated step, for both forward kernels below. Every multiply-add is written out and the compiler may
-// not regroup them (contraction off): the scalar and the 16-byte kernel then round alike whatever the code around the call
-// looks like. Left to the compiler, the two kernels contracted (1 - z) * n + z * h0 differently and were NOT bit-identical.
-__device__ __forceinline__ float gru_gate_unit(float ir, float iz, float in_, float hr, float hz, float hn, float h0, bool has_u,
-                                               float uu, float& rg, float& z, float& n) {
-#pragma clang fp contract(off)
-    rg = 1.0f / (1.0f + expf(-(ir + hr)));
-    z = 1.0f / (1.0f + expf(-(iz + hz)));
-    n = tanhf(fmaf(rg, hn, in_));
-    const float gnew = fmaf(z, h0, (1.0f - z) * n);
-    return has_u ? fmaf(uu, gnew, (1.0f - uu) * h0) : gnew;
 }
 
 __global__ __launch_bounds__(256) void gru_step_fwd_kernel(const FwdGroup g) {
@@ -60,19 +48,19 @@ __global__ __launch_bounds__(256) void gru_step_fwd_kernel(const FwdGroup g) {
         }
         const float hr = gh[j], hz = gh[H + j], hn = gh[2 * H + j];
         const float h0 = hp ? hp[j] : 0.f;
-        float rg, z, n;
-        ho[j] = gru_gate_unit(ir, iz, in_, hr, hz, hn, h0, S.u != nullptr, uu, rg, z, n);
+        const GruFwdUnit e = gru_fwd_unit<GruFwdZhUg>(ir, iz, in_, hr, hz, hn, h0, uu, S.u != nullptr);
+        ho[j] = e.h;
         if (sv) {
-            sv[j] = rg;
-            sv[H + j] = z;
-            sv[2 * H + j] = n;
-            sv[3 * H + j] = hn;
+            sv[j] = e.rg;
+            sv[H + j] = e.z;
+            sv[2 * H + j] = e.n;
+            sv[3 * H + j] = e.hn;
         }
     }
 }
 
 // The same step, four hidden units per thread (16-byte accesses; round 6): the launch of the segment level's forward chain
-// at a real batch moves 39 MB per step and was at 3.4 TB/s with scalar accesses. Same arithmetic per element (gru_gate_unit): bit-identical.
+// at a real batch moves 39 MB per step and was at 3.4 TB/s with scalar accesses. Same unit of gru_gate.h per element: bit-identical.
 // Host-side condition: hidden % 4 == 0, hidden / 4 <= 256, every row pointer 16-byte aligned (gru_step_vec_ok).
 __global__ __launch_bounds__(256) void gru_step_fwd_vec_kernel(const FwdGroup g) {
     const twog_gru_step_t& S = g.s[blockIdx.y];
@@ -97,9 +85,8 @@ __global__ __launch_bounds__(256) void gru_step_fwd_vec_kernel(const FwdGroup g)
     f32x4 rg, z, n, ho;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        float rk, zk, nk;
-        ho[k] = gru_gate_unit(ir[k], iz[k], in_[k], hr[k], hz[k], hn[k], h0[k], S.u != nullptr, uu, rk, zk, nk);
-        rg[k] = rk; z[k] = zk; n[k] = nk;
+        const GruFwdUnit e = gru_fwd_unit<GruFwdZhUg>(ir[k], iz[k], in_[k], hr[k], hz[k], hn[k], h0[k], uu, S.u != nullptr);
+        ho[k] = e.h; rg[k] = e.rg; z[k] = e.z; n[k] = e.n;
     }
     *reinterpret_cast<f32x4*>(twog_row_ptr(S.h_out, r) + j) = ho;
     if (S.save.ptr) {
@@ -111,13 +98,10 @@ __global__ __launch_bounds__(256) void gru_step_fwd_vec_kernel(const FwdGroup g)
     }
 }
 
-inline bool rows_vec_ok(const twog_rows_t& m) {
-    if (!m.ptr) return true;
-    return (reinterpret_cast<uintptr_t>(m.ptr) & 15) == 0 && (m.ld_outer & 3) == 0 && (m.inner <= 1 || (m.ld_inner & 3) == 0);
-}
 inline bool gru_step_vec_ok(const twog_gru_step_t& S) {
-    return (S.hidden & 3) == 0 && S.hidden >= 64 && (S.hidden >> 2) <= 256 && 256 % (S.hidden >> 2) == 0 && rows_vec_ok(S.gi) &&
-           rows_vec_ok(S.gi2) && rows_vec_ok(S.gh) && rows_vec_ok(S.h_prev) && rows_vec_ok(S.h_out) && rows_vec_ok(S.save);
+    return (S.hidden & 3) == 0 && S.hidden >= 64 && (S.hidden >> 2) <= 256 && 256 % (S.hidden >> 2) == 0 &&
+           twog_rows_on_16_bytes(S.gi) && twog_rows_on_16_bytes(S.gi2) && twog_rows_on_16_bytes(S.gh) &&
+           twog_rows_on_16_bytes(S.h_prev) && twog_rows_on_16_bytes(S.h_out) && twog_rows_on_16_bytes(S.save);
 }
 
 __global__ __launch_bounds__(256) void gru_step_bwd_kernel(const BwdGroup g) {
@@ -141,23 +125,15 @@ __global__ __launch_bounds__(256) void gru_step_bwd_kernel(const BwdGroup g) {
         if (dh2) d += dh2[j];
         const float rg = sv[j], z = sv[H + j], n = sv[2 * H + j], hn = sv[3 * H + j];
         const float h0 = hp ? hp[j] : 0.f;
-        const float gnew = (1.0f - z) * n + z * h0;
-        du += d * (gnew - h0);
-        const float dg = S.u ? uu * d : d;
-        float dprev = S.u ? (1.0f - uu) * d : 0.f;
-        const float dn = dg * (1.0f - z);
-        const float dz = dg * (h0 - n);
-        dprev += dg * z;
-        const float dn_pre = dn * (1.0f - n * n);
-        const float dr_pre = dn_pre * hn * rg * (1.0f - rg);
-        const float dz_pre = dz * z * (1.0f - z);
-        dgi[j] = dr_pre;
-        dgi[H + j] = dz_pre;
-        dgi[2 * H + j] = dn_pre;
-        dgh[j] = dr_pre;
-        dgh[H + j] = dz_pre;
-        dgh[2 * H + j] = dn_pre * rg;
-        dhp[j] = S.dh_prev_accumulate ? dhp[j] + dprev : dprev;
+        const GruBwdUnit e = gru_bwd_unit<GruBwdZnDzSum>(d, rg, z, n, hn, h0, uu, S.u != nullptr, du);
+        du = e.du;
+        dgi[j] = e.dr_pre;
+        dgi[H + j] = e.dz_pre;
+        dgi[2 * H + j] = e.dn_pre;
+        dgh[j] = e.dr_pre;
+        dgh[H + j] = e.dz_pre;
+        dgh[2 * H + j] = e.dn_rg;
+        dhp[j] = S.dh_prev_accumulate ? dhp[j] + e.dprev : e.dprev;
     }
     if (S.du) {  // uniform per block
         const float t = block_sum(du, red);

@@ -25,6 +25,7 @@
 // With 8 combinations (the bench shape) the 32 workgroups of a combination share blockIdx mod 8, i.e. an XCD: their
 // exchange stays in that XCD's L2 -- a matter of speed, never of correctness. Bit-reproducible: fixed summation order.
 #include "bf16x3.h"
+#include "gru_gate.h"
 #include "persist_common.h"
 
 namespace {
@@ -216,11 +217,10 @@ __global__ __launch_bounds__(256, 1) void bigru_persist_fwd_kernel(const PArgs P
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float hr = hi[i][0][r] + lo[i][0][r] + bias[0], hz = hi[i][1][r] + lo[i][1][r] + bias[1];
-                    hn4[i][r] = hi[i][2][r] + lo[i][2][r] + bias[2];
-                    rg[i][r] = 1.0f / (1.0f + expf(-(gi[i][r][0] + hr)));
-                    zz[i][r] = 1.0f / (1.0f + expf(-(gi[i][r][1] + hz)));
-                    nn[i][r] = tanhf(gi[i][r][2] + rg[i][r] * hn4[i][r]);
-                    scratch[(4 * g4 + r) * 20 + i16] = (1.0f - zz[i][r]) * nn[i][r] + zz[i][r] * h0[i][r];
+                    const GruFwdUnit e = gru_fwd_unit<GruFwdRounded>(gi[i][r][0], gi[i][r][1], gi[i][r][2], hr, hz,
+                                                                     hi[i][2][r] + lo[i][2][r] + bias[2], h0[i][r], 1.0f, false);
+                    rg[i][r] = e.rg; zz[i][r] = e.z; nn[i][r] = e.n; hn4[i][r] = e.hn;
+                    scratch[(4 * g4 + r) * 20 + i16] = e.h;
                 }
                 lanes_sync();
                 // the tile's 16 x 16 states: one 16-byte write-through store per lane (row = lane / 4, 4 units)
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(256, 1) void bigru_persist_fwd_kernel(const PArgs P
 // Backward through time, small-batch form (one 16-row tile per wave at most). A workgroup owns 16 hidden units of one
 // (type, direction): the carried gradient of those units lives in registers for the whole sequence, and the 3h x 16
 // slice of W_hh that produces it (d h_prev[:, u] = sum_k d_gh[:, k] W_hh[k][u], k over the 3h gate rows) in LDS as
-// B fragments. Per step: gate backward of the own units (gru.hip's arithmetic) -> d_gi, d_gh columns (d_gh
+// B fragments. Per step: gate backward of the own units (gru_gate.h) -> d_gi, d_gh columns (d_gh
 // write-through: it is the next product's operand for EVERY slice) -> signal -> wait for all slices -> the complete
 // d_gh rows x the slice -> carried gradient of the next step. Same hand-off rules as the forward kernel.
 // ---------------------------------------------------------------------------------------------------------------
@@ -341,20 +341,15 @@ __global__ __launch_bounds__(256, 1) void bigru_persist_bwd_kernel(const BArgs P
     fetch_gate(T - 1, cur);
     for (int s = T - 1; s >= 0; --s) {
         const int t = dir == 0 ? s : T - 1 - s;
-        // ---- gate backward of the own 4 x 1 outputs per lane (torch.nn.GRU, gate order r z n; see gru_step_bwd_kernel)
-        float dgi_[3][4], dgh_[3][4], direct[4];
+        // ---- gate backward of the own 4 x 1 outputs per lane (gru_gate.h)
+        float dgi_[3][4], dgh_[3][4], dd[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float d = cur.d[r] + carry[r];
-            const float rg = cur.rg[r], z = cur.z[r], n = cur.n[r], hn = cur.hn[r], h0 = cur.h0[r];
-            const float dn = d * (1.0f - z);
-            const float dz = d * (h0 - n);
-            direct[r] = d * z;
-            const float dn_pre = dn * (1.0f - n * n);
-            const float dr_pre = dn_pre * hn * rg * (1.0f - rg);
-            const float dz_pre = dz * z * (1.0f - z);
-            dgi_[0][r] = dr_pre; dgi_[1][r] = dz_pre; dgi_[2][r] = dn_pre;
-            dgh_[0][r] = dr_pre; dgh_[1][r] = dz_pre; dgh_[2][r] = dn_pre * rg;
+            const GruBwdUnit e = gru_bwd_unit<GruBwdZnDzSum>(d, cur.rg[r], cur.z[r], cur.n[r], cur.hn[r], cur.h0[r], 1.0f, false);
+            dgi_[0][r] = e.dr_pre; dgi_[1][r] = e.dz_pre; dgi_[2][r] = e.dn_pre;
+            dgh_[0][r] = e.dr_pre; dgh_[1][r] = e.dz_pre; dgh_[2][r] = e.dn_rg;
+            dd[r] = d;
         }
         // d_gh first (write-through: the other slices wait for it), then d_gi: 16 x 16 blocks through the wave's scratch,
         // one 16-byte store per lane and gate
@@ -409,8 +404,9 @@ __global__ __launch_bounds__(256, 1) void bigru_persist_bwd_kernel(const BArgs P
             mac(kb, ring[kb % D]);
             if (kb + D < NKB) load_a(kb + D, ring[kb % D]);
         }
+        // (the direct path d z, dprev of gru_gate.h, stays exact inside the sum: what the compiler had made of direct + (hi + lo))
 #pragma unroll
-        for (int r = 0; r < 4; ++r) carry[r] = direct[r] + (acc.hi[r] + acc.lo[r]);
+        for (int r = 0; r < 4; ++r) carry[r] = fmaf(dd[r], cur.z[r], acc.hi[r] + acc.lo[r]);
         cur = nxt;
     }
 }

@@ -30,6 +30,7 @@
 // through LDS in wave order: fixed summation order, bit-reproducible. Weights are streamed from L2 / Infinity Cache
 // every step (704 KB per slice and direction at h = 512: more than LDS holds), 160-192 KB per workgroup and step.
 #include "bf16x3.h"
+#include "gru_gate.h"
 #include "persist_common.h"
 
 // The wave index is read through a SCALAR register: every per-wave condition (`kb = wave + 4 j < nkb`: is this k-block slot
@@ -606,7 +607,7 @@ __device__ __forceinline__ bool p2_step(const SegArgs& P, const Geo& G, int s, f
         for (int c = 0; c < 3; ++c) put_part1(part, NTILES, wave, i * 3 + c, lane, acc[i][c]);
     combine_parts(part, res, NTILES, min(4, nkb));
     SP_STAMP(2);   // combine
-    // ---- gates (gru.hip, gru_step_fwd_kernel: same arithmetic), states write-through, then what the backward pass reads
+    // ---- gates (gru_gate.h), states write-through, then what the backward pass reads
     const __amdgpu_buffer_rsrc_t rs_hs = rsrc_of(P.hs[K]);
 #pragma unroll
     for (int ps = 0; ps < NPASS; ++ps) {
@@ -621,13 +622,11 @@ __device__ __forceinline__ bool p2_step(const SegArgs& P, const Geo& G, int s, f
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float ir = gi[ps][0][k] + gim[0][k], iz = gi[ps][1][k] + gim[1][k], in_ = gi[ps][2][k] + gim[2][k];
-                const float hr = gh[ps][0][k], hz = gh[ps][1][k], hn = gh[ps][2][k];
-                rg[k] = 1.0f / (1.0f + expf(-(ir + hr)));
-                zz[k] = 1.0f / (1.0f + expf(-(iz + hz)));
-                nn[k] = tanhf(in_ + rg[k] * hn);
-                const float h0 = h_own[ps][k];
-                const float gnew = (1.0f - zz[k]) * nn[k] + zz[k] * h0;
-                hnew[k] = uu[ps] * gnew + (1.0f - uu[ps]) * h0;
+                const float hr = gh[ps][0][k], hz = gh[ps][1][k], hn = gh[ps][2][k], h0 = h_own[ps][k];
+                // (units 0 and 1 of the quad round the u blend unlike units 2 and 3: gru_gate.h)
+                const GruFwdUnit e = k < 2 ? gru_fwd_unit<GruFwdZnRounded>(ir, iz, in_, hr, hz, hn, h0, uu[ps], true)
+                                           : gru_fwd_unit<GruFwdZnUh>(ir, iz, in_, hr, hz, hn, h0, uu[ps], true);
+                rg[k] = e.rg; zz[k] = e.z; nn[k] = e.n; hnew[k] = e.h;
             }
             h_own[ps] = hnew;
             st_sc1(rs_hs, 4u * (uint32_t)((((int64_t)b * T + t) * E_K + e) * (2 * h) + dir * h + col), hnew);
@@ -1104,7 +1103,7 @@ __device__ __forceinline__ bool q2_step(const SegBwdArgs& P, const Geo& G, int s
         }
     }
     SP_STAMP(2);   // softmax backward, coefficients, carry
-    // ---- gate backward of the own units (gru.hip, gru_step_bwd_kernel: same arithmetic)
+    // ---- gate backward of the own units (gru_gate.h)
     const __amdgpu_buffer_rsrc_t rs_gi = rsrc_of(P.d_gi[K]), rs_gh = rsrc_of(P.d_gh[K]);
 #pragma unroll
     for (int ps = 0; ps < NPASS; ++ps) {
@@ -1114,20 +1113,11 @@ __device__ __forceinline__ bool q2_step(const SegBwdArgs& P, const Geo& G, int s
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float d = dout[ps][k] + carry[ps][k];
-            const float rg = sr[ps][k], z = sz[ps][k], n = sn[ps][k], hn = shn[ps][k], hp = h0[ps][k];
-            const float gnew = (1.0f - z) * n + z * hp;
-            du += d * (gnew - hp);
-            const float dg = uu[ps] * d;
-            float dp = (1.0f - uu[ps]) * d;
-            const float dn = dg * (1.0f - z);
-            const float dz = dg * (hp - n);
-            dp += dg * z;
-            const float dn_pre = dn * (1.0f - n * n);
-            const float dr_pre = dn_pre * hn * rg * (1.0f - rg);
-            const float dz_pre = dz * z * (1.0f - z);
-            gi_[0][k] = dr_pre; gi_[1][k] = dz_pre; gi_[2][k] = dn_pre;
-            gh_[0][k] = dr_pre; gh_[1][k] = dz_pre; gh_[2][k] = dn_pre * rg;
-            dprev[k] = dp;
+            const GruBwdUnit e = gru_bwd_unit<GruBwdZhUdSum>(d, sr[ps][k], sz[ps][k], sn[ps][k], shn[ps][k], h0[ps][k], uu[ps], true, du);
+            du = e.du;
+            gi_[0][k] = e.dr_pre; gi_[1][k] = e.dz_pre; gi_[2][k] = e.dn_pre;
+            gh_[0][k] = e.dr_pre; gh_[1][k] = e.dz_pre; gh_[2][k] = e.dn_rg;
+            dprev[k] = e.dprev;
         }
         direct[ps] = dprev;
         // the sum over this slice's 16 units of a row: the four quads of a row are adjacent lanes

@@ -95,6 +95,12 @@ __device__ __forceinline__ int64_t twog_row_off(const twog_rows_t& m, int r) {
     return (int64_t)o * m.ld_outer + (int64_t)(r - o * m.inner) * m.ld_inner;
 }
 __device__ __forceinline__ float* twog_row_ptr(const twog_rows_t& m, int r) { return m.ptr + twog_row_off(m, r); }
+// host: every row of m starts on 16 bytes, what the kernels with 16-byte accesses ask of an operand. An absent operand
+// (null pointer) passes.
+inline bool twog_rows_on_16_bytes(const twog_rows_t& m) {
+    if (!m.ptr) return true;
+    return (reinterpret_cast<uintptr_t>(m.ptr) & 15) == 0 && (m.ld_outer & 3) == 0 && (m.inner <= 1 || (m.ld_inner & 3) == 0);
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
